@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: ADMM iterations/s (+ B&B nodes/s) on random_miqp n=500 m=1000 p=250.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 Workload (BASELINE.json configs[1]): the random MIQP of the reference's own generator recipe
 (/root/reference/examples/random_miqp/run_example.py:71-83, seed 0, density 0.7) at n=500,
@@ -17,7 +17,15 @@ library on device-resident leaves (miosqp_amd/search.py; a 96-byte record per no
 34 KB each way), and the `python_loop` leg reports that form next to `value`.  N > 1 shards the open leaves over the
 ranks (miosqp_amd/dist.py), one process per GPU, RCCL only for the incumbent: weak scaling.
 
-Extra legs in the same JSON line (none of them is part of `value`):
+A plain run sets up, warms up, times the K steps and prints the line: `value`, `ms_per_step` (one timed step) and the
+roofline of the timed region's own launches.  --full adds everything else: the extra legs below (--legs picks them), the
+back-to-back kernel probes of the roofline, one whole tree timed after the timed region.  --dump-outputs DIR writes what
+the search holds after the last timed step, float64 and finite: counts.npy (nodes and ADMM iterations of the timed region,
+open leaves dumped); open_leaves_x0.npy / open_leaves_lower.npy (up to 64 open leaves, shallowest first: the relaxed solution
+and objective of the node that branched into each); incumbent_x.npy / incumbent_value.npy.  A quantity that does not exist
+yet (no incumbent, no solved leaf) has no file.  Same arguments, same inputs.
+
+Extra legs in the same JSON line with --full (none of them is part of `value`):
   batched   BASELINE configs[2]: waves of up to 256 leaves per device call
   stream    the same node-at-a-time workload on the STREAMING forms of the engine (factor re-read from memory every
             iteration): the persistent solver (one launch per node) and the two-launch form beside it -- what the
@@ -45,6 +53,7 @@ sys.path.insert(0, ROOT)
 KERNELS = ["k_panel_fwd", "k_tail_fwd", "k_tail_bwd", "k_panel_bwd"]
 HBM_PEAK_GBS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8 TB/s (spec)
 ALL_LEGS = ("batched", "stream", "config5", "config4", "config1", "cpu", "pyloop", "rho_auto")
+DUMP_LEAVES = 64  # --dump-outputs: at most this many open leaves (the shallowest), 64 x 8 B x n of their warm starts
 
 
 def pmc_traffic(kernel, tag="", nodes_per_launch=None):
@@ -576,9 +585,20 @@ def main():
                     help="skip the back-to-back kernel timing launches (profiling runs: every dispatch of the hot "
                          "kernel is then a node relaxation of the timed workload)")
     ap.add_argument("--legs", default="all",
-                    help="comma list of extra legs to run: batched,stream,config5,config4,config1,cpu,pyloop,rho_auto ('none' = headline only)")
+                    help="with --full: comma list of extra legs to run: batched,stream,config5,config4,config1,cpu,pyloop,rho_auto "
+                         "('none' = headline only)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the extra legs (--legs), the CPU baseline, the "
+                         "back-to-back kernel probes and one whole tree after the timed region")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the search holds after the last timed step as DIR/<name>.npy (float64, finite): "
+                         "counts, open leaves, incumbent")
     args = ap.parse_args()
-    legs = set(ALL_LEGS) if args.legs == "all" else set(x for x in args.legs.split(",") if x and x != "none")
+    if not args.full and args.legs not in ("all", "none"):
+        ap.error("--legs %s needs --full" % args.legs)
+    legs = set() if not args.full else set(ALL_LEGS) if args.legs == "all" else \
+        set(x for x in args.legs.split(",") if x and x != "none")
+    probes = args.full and not args.no_probes
     if args.no_cpu_baseline:
         legs.discard("cpu")
     if args.no_large_leg:
@@ -771,6 +791,30 @@ def main():
         s0, d0 = getattr(head, "_s0", 0), getattr(head, "_d0", 0)
         per_rank = comm.gather([float(rank), float(head.nodes - n0), float(head.iters - i0), float(head.steps_done - s0),
                                 float(head.idle_steps - d0), float(getattr(head.sh, "moved", 0)), dt, float(tree_group)])
+    if args.dump_outputs and rank == 0:
+        # what a caller of the search receives after the last timed step: the open leaves (taken out of the search, as
+        # the sharded search hands them over -- nothing below steps this search again), the incumbent, the work done
+        w = model.work
+        leaves = []  # (x0, lower): x0 is the relaxed solution of the node that branched into the leaf, lower its objective
+        if hosted:
+            while len(leaves) < DUMP_LEAVES and head.hs.givable():
+                rec = head.hs.give_leaf()  # (shallowest first)
+                leaves.append((rec[2], rec[5]))
+        else:
+            for lf in sorted(w.leaves, key=lambda lf: lf.depth)[:DUMP_LEAVES]:
+                leaves.append((lf.x, lf.lower))
+        # (a root that has not been solved yet carries no result: lower = -inf, x0 = 0)
+        leaves = [(x, lo) for x, lo in leaves if np.isfinite(lo) and np.all(np.isfinite(x))]
+        dump = dict(counts=np.array([tot[1], tot[0], len(leaves)], dtype=np.float64))
+        if leaves:
+            dump.update(open_leaves_x0=np.array([x for x, _ in leaves], dtype=np.float64),
+                        open_leaves_lower=np.array([lo for _, lo in leaves], dtype=np.float64))
+        if np.isfinite(w.upper_glob):
+            dump.update(incumbent_x=np.asarray(w.x, dtype=np.float64), incumbent_value=np.array([w.upper_glob]))
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, arr in dump.items():
+            assert np.all(np.isfinite(arr)), name
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), arr)
     if hosted:
         model.work.leaves = []  # the open leaves of this instance live in device slots
     if rpt < world:
@@ -794,9 +838,9 @@ def main():
 
     # A driver-sized run (--steps 20 .. 150) ends before the first tree of the timed region closes (seed 0: ~220 nodes):
     # one more tree, from its root to the end, timed on its own -- what branch and bound buys, next to the rates
-    # (config 2 only: a tree of the n = 5000 / 8000 shapes is thousands of 15-40 ms nodes; never more than 20 s; not with
-    #  --no-probes: the profiled node-only runs hold the launches of the timed workload and nothing else)
-    if hosted and world == 1 and len(closed) < 2 and args.config == "cfg2" and not args.no_probes:
+    # (config 2 only: a tree of the n = 5000 / 8000 shapes is thousands of 15-40 ms nodes; never more than 20 s; only with
+    #  --full and not with --no-probes: the profiled node-only runs hold the launches of the timed workload and nothing else)
+    if hosted and world == 1 and len(closed) < 2 and args.config == "cfg2" and probes:
         next_instance(head)
         torch.cuda.synchronize()
         tn0, ti0 = head.hs.nodes, head.hs.iters
@@ -1010,19 +1054,19 @@ def main():
                     launches=wu_launches + launches, nodes=wu_nodes + nodes_here, iterations=tot_it, usec_total=round(tot_us, 1),
                     usec_per_node=round(tot_us / max(1, wu_nodes + nodes_here), 3),
                     frac=round(fs["bytes_per_iter"] * tot_it / max(tot_us, 1e-9) * 1e-3 / HBM_PEAK_GBS, 4),
-                    what="warm-up + timed region (with --legs none --no-probes nothing else launches the kernel): compare "
-                         "usec_total with calls x average of the rocprofv3 kernel table of the same command")
-            it_us, it_bytes = (0.0, 0.0) if args.no_probes else eng.time_kernel(4, 2000)
+                    what="warm-up + timed region (without --full, or with --legs none --no-probes, nothing else launches the "
+                         "kernel): compare usec_total with calls x average of the rocprofv3 kernel table of the same command")
+            it_us, it_bytes = (0.0, 0.0) if not probes else eng.time_kernel(4, 2000)
         elif fs["pers"]:  # likewise one launch per node
             launches = max(1, nodes_here)
             us, by = 1e3 * loop_ms / launches, fs["bytes_per_iter"] * loop_iters / launches
             kern.append(dict(kernel="k_pers_small" if fs["pers_small"] else "k_pers", usec=round(us, 3), bytes=round(by),
                              gbs=round(by / max(us, 1e-9) * 1e-3, 1), bytes_moved=round(fs["bytes_moved_per_iter"] * loop_iters / launches),
                              launches=launches, iterations_per_launch=round(loop_iters / launches, 1)))
-            it_us, it_bytes = (0.0, 0.0) if args.no_probes else eng.time_kernel(4, 200)
+            it_us, it_bytes = (0.0, 0.0) if not probes else eng.time_kernel(4, 200)
         else:
             names = ["k_fold_fwd", "k_fold_bwd"] if fs["fold"] else KERNELS
-            if args.no_probes:  # no extra launches: the whole iteration from the loop's own events
+            if not probes:  # no extra launches: the whole iteration from the loop's own events
                 us = 1e3 * loop_ms / max(1, loop_iters)
                 kern.append(dict(kernel="+".join(names), usec=round(us, 3), bytes=fs["bytes_per_iter"],
                                  gbs=round(fs["bytes_per_iter"] / max(1e-9, us) * 1e-3, 1)))
@@ -1106,7 +1150,7 @@ def main():
             out["python_loop"] = pyloop
         if batched is not None and batched["lockstep_iters"] > 0:
             bk = []
-            if not args.no_probes:
+            if probes:
                 bnames = ["kbm_fwd", "kbm_bwd"] if fs["fold"] else ["kb_" + k[2:] for k in KERNELS]
                 for k, nm in enumerate(bnames):
                     us, by = eng.time_kernel(10 + k, 30)
@@ -1115,7 +1159,7 @@ def main():
             batched["sweeps"] = ("one persistent launch per chunk of check_termination iterations, factor in registers and LDS "
                                  "(kbp1)" if fs.get("batch_pers") else "two launches per lock-step iteration (kbm_fwd, kbm_bwd)")
             batched["persistent_fallbacks"] = eng.batch_pers_fallbacks()
-            if fs.get("batch_pers") and not args.no_probes:
+            if fs.get("batch_pers") and probes:
                 us, _ = eng.time_kernel(15, 100)
                 batched["persistent_sweeps_us_per_lockstep_iter"] = round(us, 2)
             # SURVEY 8d's config-3 accounting: matrix terms once per lock-step iteration, vector terms per column;

@@ -1,5 +1,5 @@
 """The bench line the driver parses: the committed record of the last measured round carries every field of
-the contract, with consistent values (CPU check of a file produced on the GPU box by `python bench.py`)."""
+the contract, with consistent values (CPU check of a file produced on the GPU box by `python bench.py --full`)."""
 import glob
 import json
 import os
@@ -168,3 +168,12 @@ def test_streaming_form_fractions_can_be_recomputed_from_profiles():
         assert 0.8 * moved <= per_iter <= 1.6 * moved, (name, per_iter, moved)
         if beyond:
             assert moved > 256 * 2 ** 20  # more than the Infinity Cache holds, per iteration (the symmetric tiles: 289 MB at n = 8000)
+
+
+def test_extra_legs_need_full():
+    """A plain run is the headline alone: asking for an extra leg without --full is refused before anything is set up."""
+    import subprocess
+    import sys
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--legs", "batched"], cwd=ROOT,
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and "--legs batched needs --full" in r.stderr, (r.returncode, r.stderr[-500:])

@@ -1393,6 +1393,45 @@ def test_single_rank_torchrun_goes_through_rccl(tmp_path):
     assert b["n_gpus"] == 1 and b["roofline"]["kernel"] == a["roofline"]["kernel"]
 
 
+def test_plain_bench_is_the_headline_alone_and_dumps_its_outputs(tmp_path):
+    """`bench.py --gpus 1 --steps N --warmup W --dump-outputs DIR`: the line carries the contract's fields and none of what
+    --full adds; DIR holds what the search holds after the last timed step (float64, every value finite): its counts are of
+    exactly N steps (one node each) and agree with the line, the open leaves carry solved relaxations (the tree of seed 0 is
+    still open after 45 nodes); a second run with the same arguments writes the same files with the same arrays."""
+    import glob, json, subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    runs = []
+    for k in range(2):
+        d = str(tmp_path / ("out%d" % k))
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "40", "--warmup", "5",
+                            "--dump-outputs", d], cwd=root, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads(r.stdout.strip().splitlines()[-1])
+        runs.append((line, {os.path.basename(f)[:-4]: np.load(f) for f in glob.glob(os.path.join(d, "*.npy"))}))
+    line, arr = runs[0]
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup"):
+        assert key in line, key
+    assert line["steps"] == 40 and line["warmup"] == 5 and line["ms_per_step"] > 0 and line["dtype"] == "f64"
+    for leg in ("batched", "stream", "config5", "config4", "config1", "cpu_baseline", "python_loop", "rho_auto", "by_rho"):
+        assert leg not in line, leg
+    assert "one_tree_after_the_timed_region" not in line["trees"]
+    for name, a in arr.items():
+        assert a.dtype == np.float64 and a.size > 0 and np.all(np.isfinite(a)), name
+    assert sum(a.nbytes for a in arr.values()) <= 64 << 20
+    c = arr["counts"]
+    assert c.shape == (3,) and c[0] == line["nodes"] == 40
+    assert abs(c[1] - line["iters_per_node"] * line["nodes"]) <= 0.05 * line["nodes"] + 1e-6
+    # value and ms_per_step describe the same timed steps
+    assert abs(line["value"] - c[1] * 1e3 / (line["ms_per_step"] * line["steps"])) <= 0.01 * line["value"]
+    k = int(c[2])
+    assert 1 <= k <= 64 and arr["open_leaves_x0"].shape == (k, 500) and arr["open_leaves_lower"].shape == (k,)
+    if "incumbent_x" in arr:
+        assert arr["incumbent_x"].shape == (500,) and arr["incumbent_value"].shape == (1,)
+    assert sorted(arr) == sorted(runs[1][1])
+    for n in arr:
+        np.testing.assert_array_equal(arr[n], runs[1][1][n])
+
+
 def _stream_checker(pr, stride, seen, ref=None, oracle_mod=None, oracle_stride=0, oracle_seen=None):
     """observer for StreamSearch: every `stride`-th decided node is replayed through solve_node on a SECOND engine
     from what the pool holds for it (its integer-row bounds, its parent's solution as warm start) and must
@@ -1619,7 +1658,7 @@ def test_two_ranks_stream_on_one_device(tmp_path):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0", MIOSQP_BENCH_ONE_DEVICE="1")
     tr = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                          "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(root, "bench.py"),
-                         "--gpus", "2", "--steps", "20", "--warmup", "5", "--legs", "batched", "--no-probes",
+                         "--gpus", "2", "--steps", "20", "--warmup", "5", "--full", "--legs", "batched", "--no-probes",
                          "--stream-warmup", "60", "--stream-chunks", "60", "--batch-width", "64",
                          "--batch-waves", "2"],
                         env=env, cwd=root, capture_output=True, text=True, timeout=900)
@@ -1688,7 +1727,7 @@ def test_bench_with_four_ranks_on_one_device_prints_the_line_the_driver_parses(t
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0", MIOSQP_BENCH_ONE_DEVICE="1")
     tr = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4",
                          "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(root, "bench.py"),
-                         "--gpus", "4", "--steps", "20", "--warmup", "5", "--legs", "batched", "--no-probes",
+                         "--gpus", "4", "--steps", "20", "--warmup", "5", "--full", "--legs", "batched", "--no-probes",
                          "--stream-warmup", "40", "--stream-chunks", "40", "--batch-width", "64", "--batch-waves", "2"],
                         env=env, cwd=root, capture_output=True, text=True, timeout=1500)
     assert tr.returncode == 0, tr.stderr[-3000:]

@@ -1,9 +1,10 @@
 #!/bin/bash
 # kernel-level timeline of one streaming chunk (eager launches: MIOSQP_POOL_NOGRAPH=1; rocprofv3 --kernel-trace, csv):
 # start offsets, durations, gaps of the kernels between the last sweep of one chunk and the first sweep of the next
+REPO=$(cd "$(dirname "$0")/../.." && pwd)
 cd /tmp && export TMPDIR=/tmp
 export MIOSQP_POOL_NOGRAPH=1
-rm -rf /tmp/ctl && rocprofv3 --kernel-trace --output-format csv -d /tmp/ctl -- python $GRAFT_REPO_ROOT/bench.py --legs batched --no-probes --steps 5 --warmup 2 --pools 1 --stream-warmup 120 --stream-chunks 60 > /tmp/ctl.log 2>&1
+rm -rf /tmp/ctl && rocprofv3 --kernel-trace --output-format csv -d /tmp/ctl -- python $REPO/bench.py --full --legs batched --no-probes --steps 5 --warmup 2 --pools 1 --stream-warmup 120 --stream-chunks 60 > /tmp/ctl.log 2>&1
 python3 - <<'PY'
 import csv, glob
 rows=[]

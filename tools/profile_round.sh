@@ -24,9 +24,9 @@ prof() {
   python $R/tools/pmc_merge.py $O/pmc_${NAME}_FETCH_SIZE.json $O/pmc_${NAME}_WRITE_SIZE.json "$HDR python bench.py $ARGS" $O/pmc_${NAME}_FETCH_SIZE.bench.json > $O/pmc_traffic_$NAME.json
 }
 
-# 1. the line the driver records, and the BASELINE.md node budget (999 nodes)
+# 1. the full line (every leg, the CPU baseline: what tests/test_bench_contract.py reads), and the BASELINE.md node budget (999 nodes)
 if want default; then
-timeout 400 python bench.py > $O/bench_default.json 2> $O/bench_default.err
+timeout 400 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 timeout 400 python bench.py --steps 999 --legs none > $O/bench_999_nodes.json 2> $O/bench_999.err
 # the driver's command (BENCH_rNN.json): 20 timed nodes after 3
 timeout 400 python bench.py --gpus 1 --steps 20 --warmup 3 > $O/bench_driver_slice.json 2> $O/bench_driver_slice.err
@@ -38,8 +38,8 @@ cd /tmp
 #    hipGraphLaunch after ~230 replays of that graph); same kernels, same device time
 if want all_legs; then
 export MIOSQP_POOL_NOGRAPH=1
-timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/p_all -o all -- python $R/bench.py --no-cpu-baseline > $O/ks_all_bench.json 2> $O/ks_all.err
-python $R/tools/rocpd_stats.py $(db /tmp/p_all) "rocprofv3 --kernel-trace --stats -- python bench.py --no-cpu-baseline   (MI355X, $TAG, all legs)" "durations in ns; profiled runs are slower than un-profiled ones" > $O/rocprofv3_kernel_stats.txt
+timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/p_all -o all -- python $R/bench.py --full --no-cpu-baseline > $O/ks_all_bench.json 2> $O/ks_all.err
+python $R/tools/rocpd_stats.py $(db /tmp/p_all) "rocprofv3 --kernel-trace --stats -- python bench.py --full --no-cpu-baseline   (MI355X, $TAG, all legs)" "durations in ns; profiled runs are slower than un-profiled ones" > $O/rocprofv3_kernel_stats.txt
 unset MIOSQP_POOL_NOGRAPH
 fi
 
@@ -81,9 +81,9 @@ fi
 if want batched; then
 export MIOSQP_POOL_NOGRAPH=1
 # ONE pool only (--pools 1): with the two-pool leg in the same table the test kernels' maxima are contention, not the kernel
-prof batched "--steps 20 --warmup 5 --legs batched --no-probes --pools 1" "MIOSQP_POOL_NOGRAPH=1"
+prof batched "--steps 20 --warmup 5 --full --legs batched --no-probes --pools 1" "MIOSQP_POOL_NOGRAPH=1"
 # ... and the stream by itself (no waves of the wave form in the table: what is not the persistent kernel is the stream's own)
-prof batched_stream "--steps 20 --warmup 5 --legs batched --no-probes --pools 1 --batch-waves 0" "MIOSQP_POOL_NOGRAPH=1"
+prof batched_stream "--steps 20 --warmup 5 --full --legs batched --no-probes --pools 1 --batch-waves 0" "MIOSQP_POOL_NOGRAPH=1"
 unset MIOSQP_POOL_NOGRAPH
 fi
 ls -la $O
