@@ -171,6 +171,29 @@ int miosqp_qp_solve_batch(miosqp_qp_engine *e, int32_t B, const double *l, const
                           const double *x0, const double *y0, double *x_out, double *y_out,
                           miosqp_qp_info *info);
 
+/* ---- strong branching: the 2K children of one node solved together and scored on the device ----------------
+ * For K candidates (ascending positions in i_idx, 1 <= K <= 32) of a solved parent (l, u: its bounds; x, y: its
+ * clamped x and its y), child k (down) has u[m + cand[k]] = floor(x[i_idx[cand[k]]]) and child K + k (up) has
+ * l[m + cand[k]] = ceil(x[i_idx[cand[k]]]); every child is warm-started from (x, y) and solved like solve_node with
+ * max_iter iterations (a positive multiple of check_termination).  The children are built on the device from the one
+ * parent uploaded and run as one batch (the solve_batch path); only the record below comes back.
+ * lower_out[2K]: the children's lower (NaN where infeasible); status_out / iter_out [2K]; score_out[K]:
+ * max(gain_down, eps) * max(gain_up, eps), gain = max(lower - parent_lower, 0), 1e30 for an infeasible child;
+ * info->chosen: the argmax (ties to the lowest k), an index into cand.  Needs miosqp_qp_set_integer_rows.
+ * MIOSQP_EARG: K, max_iter or a candidate out of range; MIOSQP_EBOUNDS: l > u in the parent or in a child. */
+typedef struct miosqp_sb_info {
+  int32_t chosen;      /* index into cand */
+  int32_t children;    /* 2K */
+  int32_t iters;       /* ADMM iterations of all children */
+  double device_time;  /* seconds between the events around the call */
+  double run_time;     /* wall seconds of the call */
+} miosqp_sb_info;
+
+int miosqp_qp_strong_branch(miosqp_qp_engine *e, const double *l, const double *u, const double *x, const double *y,
+                            double parent_lower, int32_t K, const int32_t *cand, int32_t max_iter, double eps,
+                            double *lower_out, int32_t *status_out, int32_t *iter_out, double *score_out,
+                            miosqp_sb_info *info);
+
 /* ---- a whole tree search in one launch (small problems) ------------------------------------------------
  * the MPC re-solve path (/root/reference/miosqp/solver.py:65-172 per MIQP,
  * examples/power_converter/power_converter.py:421-508 per sampling step).  For problems the LDS-resident solver

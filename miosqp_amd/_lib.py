@@ -48,6 +48,11 @@ class StreamInfo(C.Structure):
                 ("improved", C.c_int32), ("active", C.c_int32), ("upper_glob", C.c_double)]
 
 
+class SbInfo(C.Structure):
+    _fields_ = [("chosen", C.c_int32), ("children", C.c_int32), ("iters", C.c_int32), ("device_time", C.c_double),
+                ("run_time", C.c_double)]
+
+
 class PoolDigest(C.Structure):
     _fields_ = [("slot", C.c_int32), ("status_val", C.c_int32), ("iter", C.c_int32), ("int_inf", C.c_int32),
                 ("nextvar", C.c_int32), ("reserved", C.c_int32), ("lower", C.c_double), ("heur_viol", C.c_double),
@@ -67,6 +72,8 @@ SYMBOLS = {
     "miosqp_qp_set_integer_rows": (C.c_int, [C.c_void_p, C.c_int32, ip, C.c_int32]),
     "miosqp_qp_set_root": (C.c_int, [C.c_void_p, dp, dp, C.c_double, C.c_double]),
     "miosqp_qp_solve_node": (C.c_int, [C.c_void_p, dp, dp, dp, dp, dp, dp, C.POINTER(Info)]),
+    "miosqp_qp_strong_branch": (C.c_int, [C.c_void_p, dp, dp, dp, dp, C.c_double, C.c_int32, ip, C.c_int32, C.c_double,
+                                          dp, ip, ip, dp, C.POINTER(SbInfo)]),
     "miosqp_qp_solve_trees": (C.c_int, [C.c_void_p, C.c_int32, dp, dp, dp, dp, dp, dp, dp, C.c_int32, C.c_int32, dp,
                                         C.POINTER(TreeInfo)]),
     "miosqp_qp_search_create": (C.c_int, [C.c_void_p, C.c_int32]),

@@ -26,6 +26,8 @@ from __future__ import print_function
 
 from time import time
 
+import types
+
 import numpy as np
 import scipy.sparse as spa
 
@@ -41,6 +43,45 @@ MI_MAX_ITER_UNSOLVED = 'Max-iter unsolved'
 def _default_backend():
     from miosqp_amd import qp  # raises if the HIP library cannot be loaded
     return qp
+
+
+def branching_settings(settings, qp_settings):
+    """The branching rule and its strong-branching parameters, checked (MIOSQP.setup calls this before anything is
+    built).  Rule 0: most fractional (the reference's only rule); 1: strong branching; 2: reliability branching."""
+    rule = settings.get('branching_rule', 0)
+    if rule not in (0, 1, 2):
+        raise ValueError('No variable selection rule recognized!')
+    K = settings.get('sb_candidates', 8)
+    if int(K) != K or not 1 <= K <= 32:
+        raise ValueError('sb_candidates must be in 1..32')
+    check = (qp_settings or {}).get('check_termination', (qp_settings or {}).get('early_terminate_interval', 25))
+    cap = settings.get('sb_max_iter', 50)
+    if rule != 0 or 'sb_max_iter' in settings:
+        if int(cap) != cap or cap <= 0 or check <= 0 or cap % check != 0:
+            raise ValueError('sb_max_iter must be a positive multiple of check_termination (%r)' % check)
+    rel = settings.get('sb_reliability', 4)
+    if int(rel) != rel or rel < 0:
+        raise ValueError('sb_reliability must be a non-negative integer')
+    eps = float(settings.get('sb_eps', 1e-6))
+    if not eps > 0:
+        raise ValueError('sb_eps must be positive')
+    return dict(rule=rule, K=int(K), max_iter=int(cap), reliability=int(rel), eps=eps)
+
+
+def sb_scores(lower, status, parent_lower, eps, ok):
+    """Scores of K strong-branching candidates from their 2K children (K down, then K up): the gain of a child is
+    max(L - L_parent, 0), 1e30 without a lower value (status not in `ok`); score = max(gain_d, eps) * max(gain_u, eps).
+    Returns (gains [2K], scores [K], argmax with ties to the lowest candidate)."""
+    K = len(lower) // 2
+    gain = np.empty(2 * K)
+    for b in range(2 * K):
+        g = lower[b] - parent_lower if status[b] in ok else 1e30
+        gain[b] = g if g > 0.0 else 0.0
+    score = np.empty(K)
+    for k in range(K):
+        gd, gu = gain[k], gain[K + k]
+        score[k] = (gd if gd > eps else eps) * (gu if gu > eps else eps)
+    return gain, score, int(np.argmax(score))
 
 
 def add_bounds(i_idx, l_new, u_new, A, l, u):
@@ -105,6 +146,7 @@ class Node(object):
         self.nextvar_idx = None
         self.constr_idx = None
         self.digest = None  # filled by the device epilogue (miosqp_qp_set_root) when available
+        self.pc = None  # reliability branching: (parent lower, position, direction 0 down / 1 up, distance f) of the branching
 
     def _absorb(self, status, num_iter, run_time, x, y, lower):
         self.status = status
@@ -151,6 +193,8 @@ class Workspace(object):
     def __init__(self, data, settings, qp_settings=None, backend=None):
         self.data = data
         self.settings = settings
+        self.sb = branching_settings(settings, qp_settings)
+        self._sb_solver = None
         self.backend = backend if backend is not None else _default_backend()
         self.constant = self.backend.constant
         self.solver = self.backend.OSQP()
@@ -187,6 +231,11 @@ class Workspace(object):
         self.lower_glob = -np.inf
         self.defer_lower = False
         self.status = MI_UNSOLVED
+        # strong branching's own work (node relaxations stay in osqp_iter / osqp_solve_time) and the pseudo-costs of
+        # reliability branching: per position and direction (0 down, 1 up), sum and count of gains per unit distance
+        self.sb_stats = dict(calls=0, children=0, osqp_iter=0, solve_time=0.)
+        self.pc_sum = np.zeros((2, self.data.n_int))
+        self.pc_cnt = np.zeros((2, self.data.n_int), dtype=np.int64)
 
     def _make_root(self):
         return Node(self.data, self.data.l, self.data.u, self.solver, constant=self.constant)
@@ -240,13 +289,146 @@ class Workspace(object):
         self._child(leaf, l, u)
 
     def pick_nextvar(self, leaf):
-        # workspace.py:205-230: largest fractional part among the still-fractional integers
-        if self.settings['branching_rule'] != 0:
+        # workspace.py:205-230: largest fractional part among the still-fractional integers (rule 0); rules 1 and 2
+        # decide from strong-branching children (select_branching)
+        rule = self.settings['branching_rule']
+        if rule == 0:
+            xf = leaf.x[self.data.i_idx[leaf.frac_idx]]
+            nextvar = leaf.frac_idx[int(np.argmax(abs(xf - np.round(xf))))]
+        elif rule in (1, 2):
+            nextvar = self.select_branching(leaf)
+        else:
             raise ValueError('No variable selection rule recognized!')
-        xf = leaf.x[self.data.i_idx[leaf.frac_idx]]
-        nextvar = leaf.frac_idx[int(np.argmax(abs(xf - np.round(xf))))]
         leaf.constr_idx = self.data.m + nextvar
         leaf.nextvar_idx = self.data.i_idx[nextvar]
+
+    # -- strong and reliability branching ---------------------------------------------------------
+    def _most_fractional(self, leaf, cand, count):
+        """`count` positions of `cand` with the largest |x - round(x)| (ties to the lower position), ascending."""
+        xf = leaf.x[self.data.i_idx[cand]]
+        fr = abs(xf - np.round(xf))
+        order = sorted(range(len(cand)), key=lambda j: (-fr[j], cand[j]))[:count]
+        return sorted(cand[j] for j in order)
+
+    def select_branching(self, leaf):
+        """Branching position of a solved leaf under rule 1 (strong branching on the sb_candidates most fractional) or
+        rule 2 (reliability branching: strong branching on the unreliable candidates only, pseudo-costs for the rest)."""
+        sb = self.sb
+        cand = sorted(leaf.frac_idx)
+        if sb['rule'] == 1:
+            if len(cand) == 1:
+                return cand[0]
+            cc = self._most_fractional(leaf, cand, sb['K'])
+            return cc[self.strong_branch(leaf, cc).chosen]
+        x = leaf.x[self.data.i_idx[cand]]
+        fd, fu = x - np.floor(x), np.ceil(x) - x
+        cnt = self.pc_cnt[:, cand]
+        unrel = [c for j, c in enumerate(cand) if min(cnt[0, j], cnt[1, j]) < sb['reliability']]
+        score = dict()
+        if unrel:
+            cc = self._most_fractional(leaf, unrel, sb['K'])
+            r = self.strong_branch(leaf, cc)
+            ok = (self.constant('OSQP_SOLVED'), self.constant('OSQP_MAX_ITER_REACHED'))
+            K = len(cc)
+            for j, c in enumerate(cc):
+                v = leaf.x[self.data.i_idx[c]]
+                for side, f in ((0, v - np.floor(v)), (1, np.ceil(v) - v)):
+                    b = side * K + j
+                    if r.status[b] in ok:
+                        self.record_gain(c, side, r.lower[b] - leaf.lower, f)
+                score[c] = r.score[j]
+        psi = self.pseudo_costs()
+        eps = sb['eps']
+        best, best_s = None, -np.inf
+        for j, c in enumerate(cand):
+            s = score.get(c)
+            if s is None:
+                sd, su = psi[0, c] * fd[j], psi[1, c] * fu[j]
+                s = (sd if sd > eps else eps) * (su if su > eps else eps)
+            if s > best_s:
+                best, best_s = c, s
+        return best
+
+    def record_gain(self, pos, side, delta, f):
+        """One pseudo-cost observation: gain max(delta, 0) per unit distance f of position `pos`, direction `side`."""
+        self.pc_sum[side, pos] += (delta if delta > 0.0 else 0.0) / f
+        self.pc_cnt[side, pos] += 1
+
+    def pseudo_costs(self):
+        """Mean gain per unit [2, n_int]; a position without observations in a direction gets the mean over the
+        positions that have some there, or 1.0."""
+        psi = np.ones((2, self.data.n_int))
+        for side in (0, 1):
+            have = self.pc_cnt[side] > 0
+            if np.any(have):
+                mean = self.pc_sum[side, have] / self.pc_cnt[side, have]
+                psi[side, have] = mean
+                psi[side, ~have] = np.mean(mean)
+        return psi
+
+    def strong_branch(self, leaf, cand):
+        """The 2K children of `leaf` for the ascending candidate positions `cand`, each solved with sb_max_iter
+        iterations: one device call on an engine with `strong_branch`, otherwise the reference's four calls per child
+        on a second solver instance (set up like the first, max_iter = sb_max_iter).  Returns chosen (index into cand),
+        lower / status / iter [2K: K down, then K up] and score [K]."""
+        sb, st = self.sb, self.sb_stats
+        data = self.data
+        if hasattr(self.solver, 'strong_branch'):
+            r = self.solver.strong_branch(leaf.l, leaf.u, leaf.x, leaf.y, leaf.lower, cand, sb['max_iter'], sb['eps'])
+            st['calls'] += 1
+            st['children'] += 2 * len(cand)
+            st['osqp_iter'] += int(r.iters)
+            st['solve_time'] += r.run_time
+            return r
+        solver = self.sb_solver()
+        K, m, k_int, ii = len(cand), data.m, data.n_int, data.i_idx
+        lower, status, iters = np.full(2 * K, np.nan), np.empty(2 * K, dtype=np.int32), np.empty(2 * K, dtype=np.int32)
+        ok = (self.constant('OSQP_SOLVED'), self.constant('OSQP_MAX_ITER_REACHED'))
+        for side in (0, 1):
+            for j, c in enumerate(cand):
+                b = side * K + j
+                l, u = np.copy(leaf.l), np.copy(leaf.u)
+                if side == 0:
+                    u[m + c] = np.floor(leaf.x[ii[c]])
+                else:
+                    l[m + c] = np.ceil(leaf.x[ii[c]])
+                if np.any(l > u):
+                    raise RuntimeError('branching produced l > u')
+                solver.update(l=l, u=u)
+                solver.warm_start(x=leaf.x, y=leaf.y)
+                res = solver.solve()
+                status[b], iters[b] = res.info.status_val, res.info.iter
+                st['solve_time'] += res.info.run_time
+                if status[b] in ok:
+                    x = res.x
+                    x[ii] = np.minimum(np.maximum(x[ii], l[-k_int:]), u[-k_int:])
+                    lower[b] = data.compute_obj_val(x)
+        _, score, chosen = sb_scores(lower, status, leaf.lower, sb['eps'], ok)
+        st['calls'] += 1
+        st['children'] += 2 * K
+        st['osqp_iter'] += int(np.sum(iters))
+        return types.SimpleNamespace(chosen=chosen, lower=lower, status=status, iter=iters, score=score,
+                                     iters=int(np.sum(iters)))
+
+    def sb_solver(self):
+        """The second relaxation solver of the host-side strong branching (created on first use)."""
+        if self._sb_solver is None:
+            qs = dict(self.qp_settings, max_iter=self.sb['max_iter'])
+            d = self.data
+            self._sb_solver = self.backend.OSQP()
+            self._sb_solver.setup(d.P, d.q, d.A, d.l, d.u, **qs)
+        return self._sb_solver
+
+    def branch_children(self, leaf):
+        """Both children of `leaf` on its chosen position; under rule 2 each remembers what its own solve will tell
+        the pseudo-costs."""
+        self.add_left(leaf)
+        self.add_right(leaf)
+        if self.sb['rule'] == 2:
+            c = leaf.constr_idx - self.data.m
+            v = leaf.x[leaf.nextvar_idx]
+            self.leaves[-2].pc = (leaf.lower, c, 0, v - np.floor(v))
+            self.leaves[-1].pc = (leaf.lower, c, 1, np.ceil(v) - v)
 
     def satisfies_lin_constraints(self, x, l, u):
         # workspace.py:232-243 (needs 'eps_abs' in qp_settings)
@@ -295,8 +477,7 @@ class Workspace(object):
 
     def branch(self, leaf):
         self.pick_nextvar(leaf)
-        self.add_left(leaf)
-        self.add_right(leaf)
+        self.branch_children(leaf)
 
     def update_lower_glob(self):
         # workspace.py:334: after every branching; a wave defers it to its end (`defer_lower`), the value is
@@ -308,6 +489,9 @@ class Workspace(object):
         # workspace.py:282-334
         self.osqp_iter += leaf.num_iter
         self.osqp_solve_time += leaf.osqp_solve_time
+        if leaf.pc is not None and self._is(leaf, 'OSQP_SOLVED', 'OSQP_MAX_ITER_REACHED'):
+            lp, c, side, f = leaf.pc
+            self.record_gain(c, side, leaf.lower - lp, f)
         if self._is(leaf, 'OSQP_PRIMAL_INFEASIBLE', 'OSQP_DUAL_INFEASIBLE'):
             return
         if leaf.lower > self.upper_glob:
@@ -320,7 +504,8 @@ class Workspace(object):
             # only when the digest says the incumbent improves), exactly as workspace.py:321-327 computes
             # it.  `leaf.lower` is the device value on this path by design (node.py:143 fused into the
             # epilogue; 1e-9 relative, DESIGN.md "tolerances").
-            if self.settings['branching_rule'] != 0:
+            rule = self.settings['branching_rule']
+            if rule not in (0, 1, 2):
                 raise ValueError('No variable selection rule recognized!')
             leaf.intinf = dg.int_inf
             if dg.int_inf == 0:
@@ -338,10 +523,10 @@ class Workspace(object):
                     self.prune()
             xi = leaf.x[self.data.i_idx]
             leaf.frac_idx = np.where(abs(xi - np.round(xi)) > self.settings['eps_int_feas'])[0].tolist()
-            leaf.constr_idx = self.data.m + dg.nextvar
-            leaf.nextvar_idx = self.data.i_idx[dg.nextvar]
-            self.add_left(leaf)
-            self.add_right(leaf)
+            nextvar = dg.nextvar if rule == 0 else self.select_branching(leaf)
+            leaf.constr_idx = self.data.m + nextvar
+            leaf.nextvar_idx = self.data.i_idx[nextvar]
+            self.branch_children(leaf)
             self.update_lower_glob()
             return
         if self.is_int_feas(leaf.x, leaf):
@@ -618,6 +803,8 @@ class MIOSQP(object):
         work.data.update_vectors(q, l, u)
         if q is not None:
             work.solver.update(q=q)
+            if work._sb_solver is not None:
+                work._sb_solver.update(q=q)
         work.push_root()
         work.leaves = [work._make_root()]
         work._reset_counters()

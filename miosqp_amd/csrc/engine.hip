@@ -230,6 +230,7 @@ struct CoopNode {
 #include "kernels_tree.inc"  // a whole branch-and-bound tree in one launch (LDS-resident problems)
 #include "kernels_pool.inc"  // device-resident leaf pool, streaming batch (refill / harvest between chunks)
 #include "kernels_bstream.inc"  // the streaming batch as ONE persistent launch: iterations, test, harvest and refill per column group (kbs)
+#include "kernels_sb.inc"  // strong branching: 2K children built from one parent on the device, scored after the batch solve
 #include "host.inc"  // host side: engine object, allocation, launches, graph capture, solve loops
 #include "host_pool.inc"  // host side of the leaf pool (C ABI miosqp_qp_pool_*)
 #include "host_search.inc"  // node-at-a-time branch and bound driven from the host in C++ (C ABI miosqp_qp_search_*)
@@ -352,6 +353,8 @@ int miosqp_qp_cleanup(miosqp_qp_engine *e) {
   if (e->hb_out) hipHostFree(e->hb_out);
   if (e->hb_int) hipHostFree(e->hb_int);
   if (e->hb_dbl) hipHostFree(e->hb_dbl);
+  if (e->hsb_in) hipHostFree(e->hsb_in);
+  if (e->hsb_rec) hipHostFree(e->hsb_rec);
   for (int k = 0; k < 16; k++) {
     if (e->xb_full[k]) hipGraphExecDestroy(e->xb_full[k]);
     if (e->xb_tail[k]) hipGraphExecDestroy(e->xb_tail[k]);
@@ -1157,6 +1160,92 @@ int miosqp_qp_solve_batch(miosqp_qp_engine *e, int32_t B, const double *l, const
                          info + s0);
     if (rc) return rc;
   }
+  return 0;
+}
+
+int miosqp_qp_strong_branch(miosqp_qp_engine *e, const double *l, const double *u, const double *x, const double *y,
+                            double parent_lower, int32_t K, const int32_t *cand, int32_t max_iter, double eps,
+                            double *lower_out, int32_t *status_out, int32_t *iter_out, double *score_out,
+                            miosqp_sb_info *info) {
+  if (!e || !l || !u || !x || !y || !cand || !lower_out || !status_out || !iter_out || !score_out || !info)
+    return MIOSQP_EARG;
+  ENTER(e);
+  if (!e->have_int) {
+    g_err = "strong_branch: call miosqp_qp_set_integer_rows first";
+    return MIOSQP_EARG;
+  }
+  if (K < 1 || K > SB_MAX_K) {
+    g_err = "strong_branch: K must be in 1..32";
+    return MIOSQP_EARG;
+  }
+  if (max_iter <= 0 || max_iter % e->chunk != 0) {
+    g_err = "strong_branch: max_iter must be a positive multiple of check_termination";
+    return MIOSQP_EARG;
+  }
+  const int n_int = (int)e->h_iidx.size();
+  for (int k = 0; k < K; k++)
+    if (cand[k] < 0 || cand[k] >= n_int || (k > 0 && cand[k] <= cand[k - 1])) {
+      g_err = "strong_branch: candidates must be ascending positions in 0..n_int-1";
+      return MIOSQP_EARG;
+    }
+  const size_t n = e->n, M = e->M, m_orig = (size_t)e->d.m_orig;
+  for (size_t j = 0; j < M; j++)
+    if (l[j] > u[j]) return MIOSQP_EBOUNDS;
+  // a child whose new bound crosses the other one (Workspace.add_left / add_right refuse it too)
+  for (int k = 0; k < K; k++) {
+    const double v = x[e->h_iidx[cand[k]]];
+    if (std::floor(v) < l[m_orig + cand[k]] || std::ceil(v) > u[m_orig + cand[k]]) return MIOSQP_EBOUNDS;
+  }
+  if (e->Bcap == 0) {
+    int cap = e->st.max_batch > 1 ? e->st.max_batch : 64;
+    if (cap > 1024) cap = 1024;
+    int rc = alloc_batch(e, cap);
+    if (rc) return rc;
+  }
+  const size_t nin = 3 * M + n + SB_MAX_K / 2;
+  if (!e->sb_in) {
+    int rc = dalloc(e, &e->sb_in, nin);
+    if (!rc) rc = dalloc(e, &e->sb_rec, 1);
+    if (rc) return rc;
+    HIPCHK(hipHostMalloc((void **)&e->hsb_in, sizeof(double) * nin, hipHostMallocDefault));
+    HIPCHK(hipHostMalloc((void **)&e->hsb_rec, sizeof(SbRec), hipHostMallocDefault));
+  }
+  const double t0 = wall();
+  const int B = 2 * K;
+  if (int rc = slice_begin(e, B)) return rc;
+  double *h = e->hsb_in;
+  memcpy(h, l, sizeof(double) * M);
+  memcpy(h + M, u, sizeof(double) * M);
+  memcpy(h + 2 * M, x, sizeof(double) * n);
+  memcpy(h + 2 * M + n, y, sizeof(double) * M);
+  memcpy(h + 3 * M + n, cand, sizeof(int32_t) * K);
+  const Dev &d = e->d;
+  HIPCHK(hipEventRecord(e->ev0, e->stream));
+  HIPCHK(hipMemcpyAsync(e->sb_in, h, sizeof(double) * nin, hipMemcpyHostToDevice, e->stream));
+  const int big = (int)(n > M ? n : M);
+  hipLaunchKernelGGL(k_sb_children, dim3((big + 255) / 256, B), dim3(256), 0, e->stream, d, e->sb_in,
+                     (const int *)(e->sb_in + 3 * M + n), K);
+  if (int rc = slice_run(e, B, max_iter)) return rc;
+  hipLaunchKernelGGL(k_sb_score, dim3(1), dim3(64), 0, e->stream, d, e->sb_rec, K, parent_lower, eps);
+  HIPCHK(hipMemcpyAsync(e->hsb_rec, e->sb_rec, sizeof(SbRec), hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipEventRecord(e->ev1, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  const SbRec &r = *e->hsb_rec;
+  int64_t iters = 0;
+  for (int b = 0; b < B; b++) {
+    lower_out[b] = r.lower[b];
+    status_out[b] = r.status[b];
+    iter_out[b] = r.iter[b];
+    iters += r.iter[b];
+  }
+  for (int k = 0; k < K; k++) score_out[k] = r.score[k];
+  float ms = 0;
+  HIPCHK(hipEventElapsedTime(&ms, e->ev0, e->ev1));
+  info->chosen = r.chosen;
+  info->children = B;
+  info->iters = (int32_t)iters;
+  info->device_time = 1e-3 * ms;
+  info->run_time = wall() - t0;
   return 0;
 }
 

@@ -172,6 +172,10 @@ struct miosqp_qp_engine {
   double *hb_in = nullptr, *hb_out = nullptr;
   int *hb_int = nullptr;       // status | iter
   double *hb_dbl = nullptr;    // pri | dua | obj | lower
+  // strong branching: the parent (l | u | x | y, 3M + n doubles) and 32 candidate positions (int32, 16 doubles' room)
+  // staged in, the score record out; device / pinned host
+  double *sb_in = nullptr, *hsb_in = nullptr;
+  SbRec *sb_rec = nullptr, *hsb_rec = nullptr;
   hipGraphExec_t xb_full[16] = {}, xb_tail[16] = {};
   hipGraph_t gb_full[16] = {}, gb_tail[16] = {};
   bool compact = true;   // compaction of converged columns in solve_batch (MIOSQP_COMPACT=0 disables)
@@ -1456,12 +1460,8 @@ int alloc_batch(miosqp_qp_engine *e, int cap) {
   return 0;
 }
 
-// one slice of at most Bcap nodes
-int solve_slice(miosqp_qp_engine *e, int B, const double *l, const double *u, const double *x0, const double *y0,
-                double *x_out, double *y_out, miosqp_qp_info *info) {
-  const Dev &d = e->d;
-  const size_t n = e->n, M = e->M;
-  const double t0 = wall();
+// Before a slice of B columns is queued: the checks and the chunk graphs of its width (captured on an idle stream)
+int slice_begin(miosqp_qp_engine *e, int B) {
   const int ntiles = (B + 63) / 64;
   if (ntiles > 16) { g_err = "solve_batch: more than 1024 columns per slice"; return MIOSQP_EARG; }
   if (e->pool_pending) { g_err = "solve_batch: streaming chunks are still in flight (pool_collect first)"; return MIOSQP_EARG; }
@@ -1473,18 +1473,23 @@ int solve_slice(miosqp_qp_engine *e, int B, const double *l, const double *u, co
       rc = capture_chunk_b(e, e->tail_iters, ntiles, &e->gb_tail[ntiles - 1], &e->xb_tail[ntiles - 1]);
     if (rc) return rc;
   }
-  double *h = e->hb_in;
-  memcpy(h, l, sizeof(double) * B * M);
-  memcpy(h + B * M, u, sizeof(double) * B * M);
-  memcpy(h + 2 * B * M, x0, sizeof(double) * B * n);
-  memcpy(h + 2 * B * M + B * n, y0, sizeof(double) * B * M);
-  HIPCHK(hipEventRecord(e->ev0, e->stream));
-  HIPCHK(hipMemcpyAsync(d.b_raw, h, sizeof(double) * B * (3 * M + n), hipMemcpyHostToDevice, e->stream));
+  return 0;
+}
+
+// The lock-step solve of the B nodes staged in d.b_raw (node-major l | u | x0 | y0), up to `max_iter` iterations:
+// full chunks of check_termination iterations, then the tail graph for the rest only when max_iter is the engine's own
+// (a strong-branching cap is a multiple of check_termination: no tail).  Ends with the per-column epilogue
+// (unscale, clamp, digest, objective) in c_status / c_iter / c_lower / b_xfin / b_yfin, node order through c_node.
+int slice_run(miosqp_qp_engine *e, int B, int max_iter) {
+  const Dev &d = e->d;
+  const size_t n = e->n, M = e->M;
+  const int ntiles = (B + 63) / 64;
   hipLaunchKernelGGL(kb_reset, dim3((d.Bs + 255) / 256), dim3(256), 0, e->stream, d, B);
   const int big = (int)(n > M ? n : M);
   hipLaunchKernelGGL(kb_prepare, dim3((big + 3) / 4, ntiles), dim3(256), 0, e->stream, d, B);
   hipLaunchKernelGGL(kb_warm_z, dim3((d.M + 3) / 4, ntiles), dim3(256), 0, e->stream, d);
-  const int nfull = e->st.max_iter / e->chunk;
+  const int nfull = max_iter / e->chunk;
+  const bool tail = max_iter == e->st.max_iter && e->tail_iters > 0;
   bool done = false;
   int decided = 0;
   int cur = ntiles;  // tiles still launched; shrinks as the wave is compacted
@@ -1553,7 +1558,7 @@ int solve_slice(miosqp_qp_engine *e, int B, const double *l, const double *u, co
       e->compactions++;
     }
   }
-  while (!done && e->tail_iters > 0) {
+  while (!done && tail) {
     // the last max_iter % check_termination iterations: the same call-off handling as a full chunk -- a persistent
     // launch that was called off iterated nothing and its test decided nothing, so the tail is redone as launches
     {
@@ -1576,6 +1581,26 @@ int solve_slice(miosqp_qp_engine *e, int B, const double *l, const double *u, co
   if (d.digest) hipLaunchKernelGGL(kb_heur_rows, dim3((d.M + 3) / 4, ntiles), dim3(256), 0, e->stream, d);
   hipLaunchKernelGGL(kb_obj_rows, dim3((d.n + 3) / 4, ntiles), dim3(256), 0, e->stream, d);
   hipLaunchKernelGGL(kb_obj_sum, dim3(ntiles), dim3(1024), 0, e->stream, d);
+  return 0;
+}
+
+// one slice of at most Bcap nodes
+int solve_slice(miosqp_qp_engine *e, int B, const double *l, const double *u, const double *x0, const double *y0,
+                double *x_out, double *y_out, miosqp_qp_info *info) {
+  const Dev &d = e->d;
+  const size_t n = e->n, M = e->M;
+  const double t0 = wall();
+  const int ntiles = (B + 63) / 64;
+  if (int rcb = slice_begin(e, B)) return rcb;
+  double *h = e->hb_in;
+  memcpy(h, l, sizeof(double) * B * M);
+  memcpy(h + B * M, u, sizeof(double) * B * M);
+  memcpy(h + 2 * B * M, x0, sizeof(double) * B * n);
+  memcpy(h + 2 * B * M + B * n, y0, sizeof(double) * B * M);
+  HIPCHK(hipEventRecord(e->ev0, e->stream));
+  HIPCHK(hipMemcpyAsync(d.b_raw, h, sizeof(double) * B * (3 * M + n), hipMemcpyHostToDevice, e->stream));
+  if (int rcr = slice_run(e, B, e->st.max_iter)) return rcr;
+  const int big = (int)(n > M ? n : M);
   hipLaunchKernelGGL(kb_export, dim3((big + 3) / 4, ntiles), dim3(256), 0, e->stream, d, B);
   HIPCHK(hipMemcpyAsync(e->hb_out, d.b_out, sizeof(double) * B * (n + M), hipMemcpyDeviceToHost, e->stream));
   HIPCHK(hipMemcpyAsync(e->hb_int, d.c_status, sizeof(int) * B, hipMemcpyDeviceToHost, e->stream));

@@ -569,6 +569,8 @@ class ShardedStream(object):
         interface, e.g. search.HostedSearch (node-at-a-time relaxations, loop in the C++ library); step_kwargs: what
         its step() is called with (HostedSearch: nodes=, budget=)."""
         from miosqp_amd import stream
+        if model.work.settings.get('branching_rule', 0) != 0:
+            raise ValueError("sharded stream: branching_rule 0 only (strong / reliability branching run in MIOSQP.solve)")
         self.model, self.work = model, model.work
         self.comm = comm if comm is not None else LocalComm()
         self.seq = ShardedSearch(model, self.comm)  # replicated ramp-up (its _visit / _agree / counters)

@@ -224,6 +224,27 @@ class OSQP(object):
             iter=np.array([i.iter for i in infos]), lower=np.array([i.lower for i in infos]),
             run_time=np.array([i.run_time for i in infos]), infos=infos)
 
+    def strong_branch(self, l, u, x, y, parent_lower, cand, max_iter, eps):
+        """The 2K children of one solved node (bounds l, u; clamped x; y) for the K candidate positions `cand` (ascending
+        positions in i_idx), solved together with `max_iter` iterations each and scored on the device
+        (miosqp_qp_strong_branch).  lower / status / iter: K down children, then K up children; score: per candidate;
+        chosen: the argmax, an index into cand."""
+        l, u = _f64(l, self.m, "l"), _f64(u, self.m, "u")
+        x, y = _f64(x, self.n, "x"), _f64(y, self.m, "y")
+        c = np.ascontiguousarray(cand, dtype=np.int32)
+        K = len(c)
+        lower, score = np.empty(2 * K), np.empty(max(K, 1))
+        status, iters = np.empty(2 * K, dtype=np.int32), np.empty(2 * K, dtype=np.int32)
+        info = _lib.SbInfo()
+        rc = _check(self._lib.miosqp_qp_strong_branch(self._h, _lib.as_d(l), _lib.as_d(u), _lib.as_d(x), _lib.as_d(y),
+                                                      float(parent_lower), K, _lib.as_i(c), int(max_iter), float(eps),
+                                                      _lib.as_d(lower), _lib.as_i(status), _lib.as_i(iters),
+                                                      _lib.as_d(score), C.byref(info)), "strong_branch")
+        if rc == 1:
+            raise ValueError("Lower bound must be lower than or equal to upper bound")
+        return types.SimpleNamespace(chosen=info.chosen, lower=lower, status=status, iter=iters, score=score[:K],
+                                     iters=info.iters, device_time=info.device_time, run_time=info.run_time)
+
     def solve_tree(self, l, u, x0, y0, upper0, x_inc0, tree_explor_rule, max_iter_bb):
         """A whole tree search in one launch (small problems); None when the engine does not cover this size."""
         l, u = _f64(l, self.m, "l"), _f64(u, self.m, "u")
