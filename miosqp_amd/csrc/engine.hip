@@ -130,7 +130,7 @@ struct Dev {
   const double *W;               // N x ldw, N = M + n, ordering [constraints ; variables]
   int ldw;
   unsigned *coop_tag;            // tag of the last exchange round that completed
-  unsigned long long *coop_buf;  // 2 parities x N x {lo32|tag, hi32|tag}
+  unsigned long long *coop_buf;  // the exchange ring: 4 buffers of COOP_RING_WORDS, pair units (kernels_coop.inc)
   unsigned long long *coop_chk;  // 2 x coop_half: the test's operands [y ; x] and [proj(dy) ; dx]
   unsigned long long *coop_q;    // (256 + 16) x COOP_QS: per-workgroup, then per-group norms / sums of the test
   unsigned long long *coop_reg;  // start-up registration counter (grows by the grid size per launch); +64: launches with testers
@@ -812,7 +812,8 @@ int miosqp_qp_setup(miosqp_qp_engine **out, int32_t n, int32_t M, const int32_t 
           if (!rc) rc = dalloc(e, &d.coop_tag, 64);
           d.coop_stride = 2 * rw;
           d.coop_half = 2 * (size_t)((N + 1 + 15) & ~15);  // two words per entry (one more than rows: the testers' decision), room for either row-block size
-          if (!rc) rc = dalloc(e, &d.coop_buf, 2 * d.coop_half + 64);
+          if (!rc) rc = dalloc(e, &d.coop_buf, 4 * COOP_RING_WORDS + 64);
+          if (!rc) hipLaunchKernelGGL(k_coop_ring_fill, dim3(16), dim3(256), 0, e->stream, d.coop_buf);
           if (!rc) rc = dalloc(e, &d.coop_chk, 2 * d.coop_half + 64);
           if (!rc) rc = dalloc(e, &d.coop_q, (size_t)(256 + 16) * COOP_QS + 64);
           if (!rc) rc = dalloc(e, &d.coop_reg, 128);
@@ -1633,6 +1634,7 @@ int miosqp_qp_debug_iterate(miosqp_qp_engine *e, int32_t k, double *x, double *z
         hipLaunchKernelGGL(k_reset_ctrl, dim3(1), dim3(1), 0, e->stream, e->d);
         for (int i = 0; i < k; i++) launch_iteration(e);
       } else if (e->h_ctrl->pad) {
+        reset_registration(e);
         g_err = "cooperative solver: exchange timed out, stage " + std::to_string(e->h_ctrl->pad);
         return MIOSQP_EHIP;
       }

@@ -605,6 +605,9 @@ int inverse_guard(miosqp_qp_engine *e) {
 // the registration words of the single-launch solvers start from zero again (after a launch that was called off)
 void reset_registration(miosqp_qp_engine *e) {
   if (e->d.coop_reg) (void)hipMemsetAsync(e->d.coop_reg, 0, 128 * sizeof(unsigned long long), e->stream);
+  // (and the exchange ring starts afresh: all sentinel is in phase with any round -- a launch that timed out may have
+  //  left it half way through one, a changed layout leaves slots behind that its owners no longer reset)
+  if (e->d.coop_buf) hipLaunchKernelGGL(k_coop_ring_fill, dim3(16), dim3(256), 0, e->stream, e->d.coop_buf);
   if (e->pp.reg) (void)hipMemsetAsync(e->pp.reg, 0, 128 * sizeof(unsigned long long), e->stream);
 }
 
@@ -1008,6 +1011,7 @@ int coop_set_layout(miosqp_qp_engine *e, int NR, int mg, const double *W, int ld
   d.coop_nt = coop_decision_slot(NR, cpt) ? coop_pick_testers(e->coop_cus - e->coop_T) : 0;
   coop_pick_lag(e);
   if (grid_changed) reset_registration(e);  // a launch's registration target is a multiple of ITS grid size
+  else hipLaunchKernelGGL(k_coop_ring_fill, dim3(16), dim3(256), 0, e->stream, d.coop_buf);  // (slots of the old layout)
   return 0;
 }
 int coop_drop_identity_rows(miosqp_qp_engine *e, int n_int, const int32_t *i_idx, int m_orig) {

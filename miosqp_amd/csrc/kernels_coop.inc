@@ -5,12 +5,15 @@
 // Workgroup b keeps rows [b RW, (b+1) RW) of W in registers for the whole launch (thread t holds
 // columns t + k*COOP_B, COOP_B = 512 threads per workgroup), owns the iterates of those rows, and
 // after every step publishes its RW new entries of [wh ; rx]; every workgroup then gathers the whole
-// vector.  The exchange needs no barrier and no flag: an entry travels as two 8-byte words
-// {low half | tag}, {high half | tag} (8-byte stores are single-copy atomic), written at agent scope
-// into the buffer of the round's parity; a reader sleeps through the first part of the hand-off
-// (an early poll would only pull the stale line back into its XCD's L2 and slow the writer down;
-// the length is calibrated at setup) and then polls its own CPT entries until both tags match.  A
-// workgroup can only reach round k+1 after it has seen every entry of round k, so two buffers suffice.
+// vector.  The exchange needs no barrier and no flag: a value travels as its bare 8 bytes (8-byte stores are
+// single-copy atomic), written at agent scope into the buffer of the round, one of a ring of four whose slots
+// say "not yet written" by a sentinel no iterate can equal ("pair units" below: two columns per 16-byte poll); a
+// reader sleeps through the first part of the hand-off (an early poll would only pull the stale line back into
+// its XCD's L2 and slow the writer down; the length is calibrated at setup) and then polls its own CPT columns
+// until none holds the sentinel.  A workgroup can only reach round k+1 after it has seen every value of round k;
+// why that makes four buffers enough, and three too few, is written down at the ring's definition.
+// (Everything off the per-iteration path -- the test's operands, the mailbox, the record, the epilogue -- keeps
+// tagged 16-byte entries {lo, tag, hi, tag}: ll_publish / ll_peek.)
 // The termination test runs inside the same launch (every `check_every` iterations): the owners
 // also publish [y ; x] and [proj(dy) ; dx], every workgroup applies ITS rows of
 //   Kc = [ 0  Abar ; Abar^T  Pbar ]   (read from HBM, only at a test)
@@ -52,6 +55,52 @@ __device__ __forceinline__ ll_u4 ll_peek(const unsigned long long *slot) {
   ll_u4 w;
   asm volatile("global_load_dwordx4 %0, %1, off sc1" : "=v"(w) : "v"(slot) : "memory");
   return w;
+}
+
+// ---- the exchange ring of the iteration (coop_grid): pair units.  A value travels as its bare 8 bytes; column
+// c = t + k COOP_B of a buffer lives in 16-byte unit (k / 2) COOP_B + t, half k & 1, so a thread polls its columns
+// k = 0, 1 with ONE 16-byte load and k = 2, 3 with a second one (the halves of a unit are written by two workgroups, 8
+// bytes each: byte enables keep them apart, and an 8-byte store is single-copy atomic).
+// "Not yet written" is COOP_SENTINEL, a signalling NaN (exponent all ones, quiet bit clear, payload non-zero): no IEEE
+// operation RETURNS a signalling NaN -- every arithmetic result that is a NaN is quiet -- so no iterate can equal it,
+// those of a diverged solve included, and the host validates what the user passes in.
+// FOUR buffers, indexed by round & 3 (the running tag).  In round k an owner stores its value into buffer k & 3 and
+// then the sentinel into ITS OWN slot of buffer (k + 2) & 3.  Invariant: an owner that computes round k has gathered all
+// of round k - 1, so every workgroup has published k - 1 -- which it does behind its barrier, reached by every wave
+// after its gather of k - 2: nobody reads buffer (k + 2) & 3 = (k - 2) & 3 any more.  The reset is acknowledged before
+// the same lane publishes round k + 1 (its gather of round k ends in s_waitcnt vmcnt(0), and stores count in vmcnt on
+// gfx9), and a reader polls buffer (k + 2) & 3 only after it has seen this owner's value of round k + 1.  THREE
+// buffers are not enough: the reset would hit buffer (k - 1) % 3 while slower workgroups still gather round k - 1.
+// A launch leaves the ring in phase for the next one (every workgroup publishes the same rounds; a launch that is
+// called off publishes none); the host refills it when the layout changes or a launch timed out (k_coop_ring_fill).
+// The testers' decision (column NR of the round it is picked up in) has no owner that could reset it in step: it
+// travels as {status, tag of that round} in the same 8 bytes and is accepted by its tag.
+constexpr unsigned long long COOP_SENTINEL = 0x7FF0000000005EA7ull;
+constexpr unsigned COOP_SENT_LO = 0x00005EA7u, COOP_SENT_HI = 0x7FF00000u;
+constexpr size_t COOP_RING_WORDS = 4096;  // 8-byte words per buffer of the ring: 2 x 512 units, column 2048 and a margin
+template <int COOP_B>
+__host__ __device__ __forceinline__ size_t coop_ring_slot(int c) {  // 8-byte word of column c in a buffer
+  return 2 * (size_t)((c / (2 * COOP_B)) * COOP_B + c % COOP_B) + (size_t)((c / COOP_B) & 1);
+}
+__device__ __forceinline__ unsigned long long *coop_ring_buf(unsigned long long *ring, unsigned round) {
+  return ring + (size_t)(round & 3u) * COOP_RING_WORDS;
+}
+__device__ __forceinline__ void ll_publish8(unsigned long long *slot, unsigned long long bits) {
+  // (s_nop 1: see ll_publish)
+  asm volatile("global_store_dwordx2 %0, %1, off sc1\n\ts_nop 1" ::"v"(slot), "v"(bits) : "memory");
+}
+// (the same with the buffer in scalar registers and a 32-bit byte offset per lane: no 64-bit address arithmetic in the loop)
+__device__ __forceinline__ void ll_publish8(unsigned long long *buf, unsigned byte_off, unsigned long long bits) {
+  asm volatile("global_store_dwordx2 %0, %1, %2 sc1\n\ts_nop 1" ::"v"(byte_off), "v"(bits), "s"(buf) : "memory");
+}
+__device__ __forceinline__ ll_u4 ll_peek(const unsigned long long *buf, unsigned byte_off) {
+  ll_u4 w;
+  asm volatile("global_load_dwordx4 %0, %1, %2 sc1" : "=v"(w) : "v"(byte_off), "s"(buf) : "memory");
+  return w;
+}
+__global__ void k_coop_ring_fill(unsigned long long *ring) {
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < 4 * COOP_RING_WORDS; i += (size_t)gridDim.x * blockDim.x)
+    ring[i] = COOP_SENTINEL;
 }
 
 // The loads above are asynchronous and the compiler does not know it: between an ll_peek and the s_waitcnt that
@@ -111,8 +160,10 @@ __device__ __forceinline__ void ll_peek_wait3(const unsigned long long *(&p)[3 *
 
 template <int CPT>
 __device__ __forceinline__ void ll_peek_waitn(const unsigned long long *(&p)[CPT], ll_u4 (&w)[CPT]) {
-  static_assert(CPT >= 2 && CPT <= 4, "columns per thread");
-  if constexpr (CPT == 2) {
+  static_assert(CPT >= 1 && CPT <= 4, "loads per thread");
+  if constexpr (CPT == 1) {
+    asm volatile("global_load_dwordx4 %0, %1, off sc1\n\ts_waitcnt vmcnt(0)" : "=&v"(w[0]) : "v"(p[0]) : "memory");
+  } else if constexpr (CPT == 2) {
     asm volatile("global_load_dwordx4 %0, %2, off sc1\n\tglobal_load_dwordx4 %1, %3, off sc1\n\ts_waitcnt vmcnt(0)"
                  : "=&v"(w[0]), "=&v"(w[1]) : "v"(p[0]), "v"(p[1]) : "memory");
   } else if constexpr (CPT == 3) {
@@ -1217,7 +1268,8 @@ __device__ __attribute__((noinline)) void coop_tester(const CoopTesterArgs *dp, 
           const int last_free = final_check ? max_iter - 1 : max_iter;
           const int pick = it + d.lag < last_free ? it + d.lag : (it > last_free ? it : last_free);
           const unsigned ptag = base + 1u + (unsigned)pick;
-          ll_publish(d.coop_buf + ((ptag & 1u) ? d.coop_half : 0ull) + 2 * (size_t)d.NR, (double)st, ptag);
+          // ({status, tag}: accepted by its tag, see the ring's description)
+          ll_publish8(coop_ring_buf(d.coop_buf, ptag) + coop_ring_slot<COOP_B>(d.NR), ((unsigned long long)ptag << 32) | (unsigned)st);
         }
         ll_publish(d.coop_dec, (double)st, tag);
         Ctrl *c = d.ctrl;
@@ -1679,44 +1731,58 @@ __device__ __forceinline__ int coop_grid(const DV &d, const NV &nd, const int ma
   // spilled to vector lanes and restored sixteen at a time in the middle of the publish path
   double rho = d.rho, rinv = d.rho_inv, alpha = d.alpha, sigma = d.sigma;
   asm volatile("" : "+s"(rho), "+s"(rinv), "+s"(alpha), "+s"(sigma));
-  unsigned long long *buf_even = d.coop_buf, *buf_odd = d.coop_buf + d.coop_half;
-  asm volatile("" : "+s"(buf_even), "+s"(buf_odd));
+  unsigned long long *ring = d.coop_buf;
+  asm volatile("" : "+s"(ring));
   int nap = d.coop_nap;
   asm volatile("" : "+s"(nap));
-  const size_t my_slot = 2 * (size_t)(own ? r : 0);                       // exchange buffer: reduced index
+  const unsigned my_slot = 8u * (unsigned)coop_ring_slot<COOP_B>(own ? r : 0);  // exchange ring: reduced index (bytes)
+  const unsigned my_unit = 16u * (unsigned)t;
   const size_t chk_c = 4 * (size_t)(con ? o.rowc : 0), chk_v = 4 * (size_t)(var ? M + o.var : 0);  // test operands: full index
 
-  // all CPT entries of this thread's columns from one exchange buffer
-  // cnt: entries of the round -- NR, or NR + 1 in the round a decision of the testers is picked up (see the loop)
+  // all CPT values of this thread's columns from one buffer of the ring: (CPT + 1) / 2 units of two columns
+  // cnt: values of the round -- NR, or NR + 1 in the round a decision of the testers is picked up (see the loop):
+  // column NR then holds {status, tag} and is accepted by its tag; it leaves as those bits (the caller takes the status)
   auto gather = [&](const unsigned long long *buf, unsigned tag, double (&out)[CPT], const int cnt) {
-    bool have[CPT];
+    constexpr int NU = (CPT + 1) / 2;
+    bool have[2 * NU];
 #pragma unroll
-    for (int k = 0; k < CPT; k++) have[k] = t + k * COOP_B >= cnt;
+    for (int k = 0; k < 2 * NU; k++) have[k] = k >= CPT || t + k * COOP_B >= cnt;  // (a padding half is never waited for)
+    // the decision's column, when it is one of this thread's: its high word must EQUAL the tag, where a value's 64 bits
+    // must differ from the sentinel -- one comparison against eh[k] either way, the sense turned by isd[k]
+    bool isd[CPT];
+    unsigned eh[CPT];
+#pragma unroll
+    for (int k = 0; k < CPT; k++) {
+      isd[k] = TST && cnt > NR && t + k * COOP_B == NR;
+      eh[k] = isd[k] ? tag : COOP_SENT_HI;
+    }
     unsigned spins = 0;
     unsigned long long since = 0;
     for (;;) {
-      ll_u4 w[CPT];
+      ll_u4 w[NU];
       if constexpr (TST) {
         // (loads whose completion the compiler cannot see, then the wait: nothing may be spilled in between --
         //  tools/check_coop_isa.py checks these instantiations)
 #pragma unroll
-        for (int k = 0; k < CPT; k++)
-          if (!have[k]) w[k] = ll_peek(buf + 2 * (size_t)(t + k * COOP_B));
+        for (int u = 0; u < NU; u++)
+          if (!(have[2 * u] && have[2 * u + 1])) w[u] = ll_peek(buf + 2 * (size_t)(u * COOP_B), my_unit);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       } else {
         // the in-grid test shares this function's registers: loads and wait as ONE statement (see ll_peek_wait);
-        // an entry that has arrived, or lies beyond the problem, reads entry 0 of the buffer instead
-        const unsigned long long *ptr[CPT];
+        // a unit that has arrived, or lies beyond the problem, reads unit 0 of the buffer instead
+        const unsigned long long *ptr[NU];
 #pragma unroll
-        for (int k = 0; k < CPT; k++) ptr[k] = buf + (have[k] ? 0 : 2 * (size_t)(t + k * COOP_B));
-        ll_peek_waitn<CPT>(ptr, w);
+        for (int u = 0; u < NU; u++) ptr[u] = buf + ((have[2 * u] && have[2 * u + 1]) ? 0 : 2 * (size_t)(t + u * COOP_B));
+        ll_peek_waitn<NU>(ptr, w);
       }
       bool all = true;
 #pragma unroll
       for (int k = 0; k < CPT; k++)
         if (!have[k]) {
-          if (w[k].y == tag && w[k].w == tag) {
-            out[k] = __hiloint2double((int)w[k].z, (int)w[k].x);
+          const unsigned lo = (k & 1) ? w[k / 2].z : w[k / 2].x, hi = (k & 1) ? w[k / 2].w : w[k / 2].y;
+          const bool c1 = hi != eh[k], c2 = lo != COOP_SENT_LO;
+          if ((c1 | (c2 & !isd[k])) ^ isd[k]) {
+            out[k] = __hiloint2double((int)hi, (int)lo);
             have[k] = true;
           } else {
             all = false;
@@ -1739,10 +1805,11 @@ __device__ __forceinline__ int coop_grid(const DV &d, const NV &nd, const int ma
     if (own) {
       const double rx0 = var ? sigma * o.x - o.q : 0.0;
       const double pub0 = var ? (con ? fma(o.aint, o.sw, rx0) : rx0) : o.sw;
-      ll_publish(((tag0 & 1u) ? buf_odd : buf_even) + my_slot, pub0, tag0);
+      ll_publish8(coop_ring_buf(ring, tag0), my_slot, (unsigned long long)__double_as_longlong(pub0));
+      ll_publish8(coop_ring_buf(ring, tag0 + 2u), my_slot, COOP_SENTINEL);
     }
     for (int k = 0; k < nap; k++) __builtin_amdgcn_s_sleep(1);
-    gather((tag0 & 1u) ? buf_odd : buf_even, tag0, v, NR);
+    gather(coop_ring_buf(ring, tag0), tag0, v, NR);
     GRID_STAMP(2);
   }
 
@@ -1804,7 +1871,7 @@ __device__ __forceinline__ int coop_grid(const DV &d, const NV &nd, const int ma
       }
     }
     const long long c1 = prof ? clock64() : 0;
-    unsigned long long *buf = (tag & 1u) ? buf_odd : buf_even;
+    unsigned long long *buf = coop_ring_buf(ring, tag);
     if (own) {
       double pub = 0.0, sc = s;  // sc: (nu + rho wh) of the constraint part
       if (var) {
@@ -1824,14 +1891,16 @@ __device__ __forceinline__ int coop_grid(const DV &d, const NV &nd, const int ma
         const double zn = fmin(fmax(vv, o.lo), o.up);
         const double whn = 2.0 * zn - vv;
         pub = var ? fma(o.aint, whn, pub) : whn;
-        ll_publish(buf + my_slot, pub, tag);
+        ll_publish8(buf, my_slot, (unsigned long long)__double_as_longlong(pub));
         o.dy = rho * (zr - zn);
         o.z = zn;
         o.y += o.dy;
         o.sw = whn;
       } else {
-        ll_publish(buf + my_slot, pub, tag);
+        ll_publish8(buf, my_slot, (unsigned long long)__double_as_longlong(pub));
       }
+      // (this owner's slot two rounds on: nobody reads that buffer any more, see the ring's description)
+      ll_publish8(coop_ring_buf(ring, tag + 2u), my_slot, COOP_SENTINEL);
       if (chk) {  // the test's operands travel with the same round: [y ; x] and [proj(dy) ; dx], full indices
         if (con) {
           ll_publish(d.coop_chk + chk_c, o.y, tag);
@@ -1867,8 +1936,9 @@ __device__ __forceinline__ int coop_grid(const DV &d, const NV &nd, const int ma
 #pragma unroll
         for (int k = 0; k < CPT; k++)
           if (t + k * COOP_B == NR) {
-            const int dv = (int)v[k];
+            const int dv = __double2loint(v[k]);  // {status, tag}
             if (dv) s_dec = dv;
+            v[k] = 0.0;  // (its column of W' is zero, but the bits could be a NaN's)
           }
         last = pend;
         pend = 0;
