@@ -194,6 +194,35 @@ int miosqp_qp_strong_branch(miosqp_qp_engine *e, const double *l, const double *
                             double *lower_out, int32_t *status_out, int32_t *iter_out, double *score_out,
                             miosqp_sb_info *info);
 
+/* ---- round and fix: a primal heuristic on K rounded-and-fixed candidates of one node ----------------------------
+ * Extends the reference's rounding heuristic (/root/reference/miosqp/workspace.py:266-272 rounds the node's x,
+ * workspace.py:321-327 adopts it when it satisfies the root's linear constraints), which with continuous variables
+ * almost never passes: here the integers are rounded, FIXED, and the continuous variables re-solved.
+ * For a solved parent (l, u: its bounds; x, y: its clamped x and its y) candidate k = 0 .. K-1 (1 <= K <= 32) has, on
+ * every integer row, l = u = min(max(floor(x_i + theta_k), l_row), u_row) with theta_k = (k + 1) / (K + 1) (one double
+ * division); every other row and the warm start (x, y) are the parent's.  The candidates are built on the device from
+ * the one parent uploaded and run as one batch (the solve_batch path) with at most max_iter iterations: a positive
+ * multiple of check_termination, or the engine's own max_iter.
+ * status_out / iter_out / obj_out / viol_out [K]: per candidate; obj is the objective of its rounded point, viol that
+ * point's worst violation of the ROOT bounds with the eps_abs slack included (<= 0: satisfies_lin_constraints), both
+ * NaN for an infeasible candidate.  A candidate counts when its status is SOLVED or MAX_ITER_REACHED, viol <= 0 and
+ * obj < upper.  info->chosen: the counting candidate of lowest obj (ties to the lowest k), -1 when none counts;
+ * x_out (n doubles): its rounded point, integer entries exact -- left untouched when chosen is -1.
+ * Needs miosqp_qp_set_integer_rows and miosqp_qp_set_root (MIOSQP_EARG otherwise, as for K or max_iter out of range);
+ * MIOSQP_EBOUNDS: l > u in the parent.  Leaves no state behind: solve_node answers the same before and after. */
+typedef struct miosqp_rf_info {
+  int32_t chosen;      /* the winning candidate, -1: none */
+  int32_t feasible;    /* candidates with an x and viol <= 0 (whatever their objective) */
+  int32_t candidates;  /* K */
+  int32_t iters;       /* ADMM iterations of all candidates */
+  double device_time;  /* seconds between the events around the call */
+  double run_time;     /* wall seconds of the call */
+} miosqp_rf_info;
+
+int miosqp_qp_round_and_fix(miosqp_qp_engine *e, const double *l, const double *u, const double *x, const double *y,
+                            double upper, int32_t K, int32_t max_iter, double *x_out, int32_t *status_out,
+                            int32_t *iter_out, double *obj_out, double *viol_out, miosqp_rf_info *info);
+
 /* ---- a whole tree search in one launch (small problems) ------------------------------------------------
  * the MPC re-solve path (/root/reference/miosqp/solver.py:65-172 per MIQP,
  * examples/power_converter/power_converter.py:421-508 per sampling step).  For problems the LDS-resident solver

@@ -53,6 +53,11 @@ class SbInfo(C.Structure):
                 ("run_time", C.c_double)]
 
 
+class RfInfo(C.Structure):
+    _fields_ = [("chosen", C.c_int32), ("feasible", C.c_int32), ("candidates", C.c_int32), ("iters", C.c_int32),
+                ("device_time", C.c_double), ("run_time", C.c_double)]
+
+
 class PoolDigest(C.Structure):
     _fields_ = [("slot", C.c_int32), ("status_val", C.c_int32), ("iter", C.c_int32), ("int_inf", C.c_int32),
                 ("nextvar", C.c_int32), ("reserved", C.c_int32), ("lower", C.c_double), ("heur_viol", C.c_double),
@@ -74,6 +79,8 @@ SYMBOLS = {
     "miosqp_qp_solve_node": (C.c_int, [C.c_void_p, dp, dp, dp, dp, dp, dp, C.POINTER(Info)]),
     "miosqp_qp_strong_branch": (C.c_int, [C.c_void_p, dp, dp, dp, dp, C.c_double, C.c_int32, ip, C.c_int32, C.c_double,
                                           dp, ip, ip, dp, C.POINTER(SbInfo)]),
+    "miosqp_qp_round_and_fix": (C.c_int, [C.c_void_p, dp, dp, dp, dp, C.c_double, C.c_int32, C.c_int32, dp, ip, ip, dp, dp,
+                                          C.POINTER(RfInfo)]),
     "miosqp_qp_solve_trees": (C.c_int, [C.c_void_p, C.c_int32, dp, dp, dp, dp, dp, dp, dp, C.c_int32, C.c_int32, dp,
                                         C.POINTER(TreeInfo)]),
     "miosqp_qp_search_create": (C.c_int, [C.c_void_p, C.c_int32]),

@@ -68,6 +68,42 @@ def branching_settings(settings, qp_settings):
     return dict(rule=rule, K=int(K), max_iter=int(cap), reliability=int(rel), eps=eps)
 
 
+def heuristic_settings(settings, qp_settings):
+    """The primal heuristic and its parameters, checked (MIOSQP.setup calls this before anything is built).
+    primal_heuristic 0: the reference's rounding only; 1: round and fix (Workspace.round_and_fix)."""
+    qs = qp_settings or {}
+    on = settings.get('primal_heuristic', 0)
+    if on not in (0, 1):
+        raise ValueError('No primal heuristic recognized!')
+    K = settings.get('rf_candidates', 7)
+    if int(K) != K or not 1 <= K <= 32:
+        raise ValueError('rf_candidates must be in 1..32')
+    check = qs.get('check_termination', qs.get('early_terminate_interval', 25))
+    qp_cap = qs.get('max_iter', 4000)
+    if 'rf_max_iter' in settings:
+        cap = settings['rf_max_iter']
+        if int(cap) != cap or cap <= 0 or (cap != qp_cap and (check <= 0 or cap % check != 0)):
+            raise ValueError("rf_max_iter must be a positive multiple of check_termination (%r) or the QP's max_iter"
+                             % check)
+    else:
+        # the QP's own cap, rounded down to whole termination checks (a cap below one check stays as it is)
+        cap = qp_cap if check <= 0 or qp_cap % check == 0 or qp_cap < check else qp_cap - qp_cap % check
+    every = settings.get('rf_every', 10)
+    if int(every) != every or every < 1:
+        raise ValueError('rf_every must be at least 1')
+    return dict(on=int(on), K=int(K), max_iter=int(cap), every=int(every))
+
+
+def rf_roundings(xi, lo, hi, K):
+    """The K rounding vectors of round and fix for the integer entries xi inside the node's bounds lo, hi:
+    row k is min(max(floor(xi + theta_k), lo), hi) with theta_k = (k + 1) / (K + 1) as one double division."""
+    out = np.empty((K, len(xi)))
+    for k in range(K):
+        theta = float(k + 1) / float(K + 1)
+        out[k] = np.minimum(np.maximum(np.floor(xi + theta), lo), hi)
+    return out
+
+
 def sb_scores(lower, status, parent_lower, eps, ok):
     """Scores of K strong-branching candidates from their 2K children (K down, then K up): the gain of a child is
     max(L - L_parent, 0), 1e30 without a lower value (status not in `ok`); score = max(gain_d, eps) * max(gain_u, eps).
@@ -194,7 +230,8 @@ class Workspace(object):
         self.data = data
         self.settings = settings
         self.sb = branching_settings(settings, qp_settings)
-        self._sb_solver = None
+        self.rf = heuristic_settings(settings, qp_settings)
+        self._second = {}  # second relaxation solvers of the host-side restatements, by iteration cap
         self.backend = backend if backend is not None else _default_backend()
         self.constant = self.backend.constant
         self.solver = self.backend.OSQP()
@@ -217,8 +254,10 @@ class Workspace(object):
         """Hands the root bounds and the two tolerances to the engine so that the x-only part of
         bound_and_branch (integrality test, branching variable, rounding heuristic) is evaluated on
         the device at the end of each node (settings['device_digest'] = False keeps it on the host)."""
+        self.root_on_device = False
         if hasattr(self.solver, 'set_root') and self.settings.get('device_digest', True) \
                 and 'eps_abs' in self.qp_settings and self.data.n_int > 0:
+            self.root_on_device = True
             self.solver.set_root(self.data.l, self.data.u, self.settings['eps_int_feas'],
                                  self.qp_settings['eps_abs'])
 
@@ -236,6 +275,10 @@ class Workspace(object):
         self.sb_stats = dict(calls=0, children=0, osqp_iter=0, solve_time=0.)
         self.pc_sum = np.zeros((2, self.data.n_int))
         self.pc_cnt = np.zeros((2, self.data.n_int), dtype=np.int64)
+        # round and fix: its own work, and the count of fractional nodes that reached the branching (it fires on every
+        # rf_every-th of them, the first included)
+        self.rf_stats = dict(calls=0, candidates=0, feasible=0, improved=0, osqp_iter=0, solve_time=0.)
+        self.rf_nodes = 0
 
     def _make_root(self):
         return Node(self.data, self.data.l, self.data.u, self.solver, constant=self.constant)
@@ -410,14 +453,93 @@ class Workspace(object):
         return types.SimpleNamespace(chosen=chosen, lower=lower, status=status, iter=iters, score=score,
                                      iters=int(np.sum(iters)))
 
-    def sb_solver(self):
-        """The second relaxation solver of the host-side strong branching (created on first use)."""
-        if self._sb_solver is None:
-            qs = dict(self.qp_settings, max_iter=self.sb['max_iter'])
+    def sb_solver(self, max_iter=None):
+        """The second relaxation solver of the host-side restatements (strong branching, round and fix), created on
+        first use.  The `osqp` surface the backends share fixes the iteration cap at setup, so a call that asks for
+        another cap than sb_max_iter gets the instance kept for that cap."""
+        cap = self.sb['max_iter'] if max_iter is None else int(max_iter)
+        if cap not in self._second:
+            qs = dict(self.qp_settings, max_iter=cap)
             d = self.data
-            self._sb_solver = self.backend.OSQP()
-            self._sb_solver.setup(d.P, d.q, d.A, d.l, d.u, **qs)
-        return self._sb_solver
+            self._second[cap] = self.backend.OSQP()
+            self._second[cap].setup(d.P, d.q, d.A, d.l, d.u, **qs)
+        return self._second[cap]
+
+    # -- round and fix ------------------------------------------------------------------------------------------
+    def round_and_fix(self, leaf):
+        """Round and fix on a solved, fractional leaf: rf_candidates copies of the node with every integer row fixed
+        to a rounding of leaf.x (rf_roundings), warm-started from the leaf and solved with at most rf_max_iter
+        iterations.  One device call on an engine with `round_and_fix` that holds the root bounds, otherwise the
+        reference's four calls per candidate on the second solver instance.  Returns status / iter / obj / viol per
+        candidate (objective of the rounded point, its worst violation of the ROOT's constraints with eps_abs slack:
+        <= 0 is satisfies_lin_constraints), feasible (count), chosen (the feasible candidate of lowest objective below
+        upper_glob, ties to the lowest, or -1) and its rounded point x (None without one)."""
+        rf, st = self.rf, self.rf_stats
+        data = self.data
+        K = rf['K']
+        if hasattr(self.solver, 'round_and_fix') and self.root_on_device:
+            r = self.solver.round_and_fix(leaf.l, leaf.u, leaf.x, leaf.y, self.upper_glob, K, rf['max_iter'])
+            st['solve_time'] += r.run_time
+        else:
+            solver = self.sb_solver(rf['max_iter'])
+            k_int, ii = data.n_int, data.i_idx
+            ok = (self.constant('OSQP_SOLVED'), self.constant('OSQP_MAX_ITER_REACHED'))
+            tol = self.qp_settings['eps_abs']
+            fix = rf_roundings(leaf.x[ii], leaf.l[-k_int:], leaf.u[-k_int:], K)
+            status, iters = np.empty(K, dtype=np.int32), np.empty(K, dtype=np.int32)
+            obj, viol = np.full(K, np.nan), np.full(K, np.nan)
+            xs = [None] * K
+            for k in range(K):
+                l, u = np.copy(leaf.l), np.copy(leaf.u)
+                l[-k_int:] = fix[k]
+                u[-k_int:] = fix[k]
+                solver.update(l=l, u=u)
+                solver.warm_start(x=leaf.x, y=leaf.y)
+                res = solver.solve()
+                status[k], iters[k] = res.info.status_val, res.info.iter
+                st['solve_time'] += res.info.run_time
+                if status[k] in ok:
+                    x = res.x
+                    x[ii] = np.minimum(np.maximum(x[ii], l[-k_int:]), u[-k_int:])
+                    x = self.get_integer_solution(x)
+                    z = data.A.dot(x)
+                    viol[k] = max(np.max(data.l - tol - z), np.max(z - data.u - tol))
+                    obj[k] = data.compute_obj_val(x)
+                    xs[k] = x
+            chosen, feasible = -1, 0
+            for k in range(K):
+                if xs[k] is None or not viol[k] <= 0.0:
+                    continue
+                feasible += 1
+                if obj[k] < self.upper_glob and (chosen < 0 or obj[k] < obj[chosen]):
+                    chosen = k
+            r = types.SimpleNamespace(chosen=chosen, x=xs[chosen] if chosen >= 0 else None, status=status, iter=iters,
+                                      obj=obj, viol=viol, feasible=feasible, iters=int(np.sum(iters)))
+        st['calls'] += 1
+        st['candidates'] += K
+        st['feasible'] += int(r.feasible)
+        st['osqp_iter'] += int(r.iters)
+        return r
+
+    def primal_heuristic(self, leaf):
+        """bound_and_branch calls this on every fractional node it is about to branch: round and fix on every
+        rf_every-th of them (the first included); the winner's objective is recomputed on the host before it becomes
+        the incumbent, as the rounding heuristic's is."""
+        if not self.rf['on']:
+            return
+        fire = self.rf_nodes % self.rf['every'] == 0
+        self.rf_nodes += 1
+        if not fire:
+            return
+        r = self.round_and_fix(leaf)
+        if r.chosen < 0:
+            return
+        obj = self.data.compute_obj_val(r.x)
+        if obj < self.upper_glob:
+            self.upper_glob = obj
+            self.x = r.x
+            self.rf_stats['improved'] += 1
+            self.prune()
 
     def branch_children(self, leaf):
         """Both children of `leaf` on its chosen position; under rule 2 each remembers what its own solve will tell
@@ -521,6 +643,7 @@ class Workspace(object):
                     self.upper_glob = obj_int
                     self.x = x_int
                     self.prune()
+            self.primal_heuristic(leaf)
             xi = leaf.x[self.data.i_idx]
             leaf.frac_idx = np.where(abs(xi - np.round(xi)) > self.settings['eps_int_feas'])[0].tolist()
             nextvar = dg.nextvar if rule == 0 else self.select_branching(leaf)
@@ -541,6 +664,7 @@ class Workspace(object):
                 self.upper_glob = obj_int
                 self.x = x_int
                 self.prune()
+        self.primal_heuristic(leaf)
         self.branch(leaf)
         self.update_lower_glob()
 
@@ -651,7 +775,7 @@ class MIOSQP(object):
         if not hasattr(work.solver, 'solve_tree') or getattr(work, '_no_tree', False) or not st.get('device_tree', True):
             self._solve_hosted(work)
             return
-        if st['branching_rule'] != 0 or st['tree_explor_rule'] not in (0, 1) or len(work.leaves) != 1 \
+        if st['branching_rule'] != 0 or work.rf['on'] or st['tree_explor_rule'] not in (0, 1) or len(work.leaves) != 1 \
                 or work.iter_num != 1 or work.data.n_int == 0 or 'eps_abs' not in work.qp_settings \
                 or not st.get('device_digest', True):
             return
@@ -684,7 +808,7 @@ class MIOSQP(object):
         st = work.settings
         if not st.get('device_search', True) or not hasattr(work.solver, 'search_create'):
             return
-        if st['branching_rule'] != 0 or st['tree_explor_rule'] not in (0, 1) or len(work.leaves) != 1 \
+        if st['branching_rule'] != 0 or work.rf['on'] or st['tree_explor_rule'] not in (0, 1) or len(work.leaves) != 1 \
                 or work.iter_num != 1 or work.data.n_int == 0 or 'eps_abs' not in work.qp_settings \
                 or not st.get('device_digest', True):
             return
@@ -718,6 +842,7 @@ class MIOSQP(object):
             return []
         n, m, M = data.n, data.m, data.m + data.n_int
         ok_engine = hasattr(work.solver, 'solve_trees') and st.get('device_tree', True) and st['branching_rule'] == 0 \
+            and not work.rf['on'] \
             and st['tree_explor_rule'] in (0, 1) and data.n_int > 0 and 'eps_abs' in work.qp_settings \
             and st.get('device_digest', True) and not getattr(work, '_no_trees', False)
         Q = np.empty((B, n)); L = np.empty((B, M)); U = np.empty((B, M))
@@ -803,8 +928,8 @@ class MIOSQP(object):
         work.data.update_vectors(q, l, u)
         if q is not None:
             work.solver.update(q=q)
-            if work._sb_solver is not None:
-                work._sb_solver.update(q=q)
+            for second in work._second.values():
+                second.update(q=q)
         work.push_root()
         work.leaves = [work._make_root()]
         work._reset_counters()

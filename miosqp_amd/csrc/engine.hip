@@ -231,6 +231,7 @@ struct CoopNode {
 #include "kernels_pool.inc"  // device-resident leaf pool, streaming batch (refill / harvest between chunks)
 #include "kernels_bstream.inc"  // the streaming batch as ONE persistent launch: iterations, test, harvest and refill per column group (kbs)
 #include "kernels_sb.inc"  // strong branching: 2K children built from one parent on the device, scored after the batch solve
+#include "kernels_rf.inc"  // round and fix: K rounded-and-fixed candidates of one parent, judged from the batch epilogue
 #include "host.inc"  // host side: engine object, allocation, launches, graph capture, solve loops
 #include "host_pool.inc"  // host side of the leaf pool (C ABI miosqp_qp_pool_*)
 #include "host_search.inc"  // node-at-a-time branch and bound driven from the host in C++ (C ABI miosqp_qp_search_*)
@@ -355,6 +356,7 @@ int miosqp_qp_cleanup(miosqp_qp_engine *e) {
   if (e->hb_dbl) hipHostFree(e->hb_dbl);
   if (e->hsb_in) hipHostFree(e->hsb_in);
   if (e->hsb_rec) hipHostFree(e->hsb_rec);
+  if (e->hrf_rec) hipHostFree(e->hrf_rec);
   for (int k = 0; k < 16; k++) {
     if (e->xb_full[k]) hipGraphExecDestroy(e->xb_full[k]);
     if (e->xb_tail[k]) hipGraphExecDestroy(e->xb_tail[k]);
@@ -1244,6 +1246,83 @@ int miosqp_qp_strong_branch(miosqp_qp_engine *e, const double *l, const double *
   HIPCHK(hipEventElapsedTime(&ms, e->ev0, e->ev1));
   info->chosen = r.chosen;
   info->children = B;
+  info->iters = (int32_t)iters;
+  info->device_time = 1e-3 * ms;
+  info->run_time = wall() - t0;
+  return 0;
+}
+
+int miosqp_qp_round_and_fix(miosqp_qp_engine *e, const double *l, const double *u, const double *x, const double *y,
+                            double upper, int32_t K, int32_t max_iter, double *x_out, int32_t *status_out,
+                            int32_t *iter_out, double *obj_out, double *viol_out, miosqp_rf_info *info) {
+  if (!e || !l || !u || !x || !y || !x_out || !status_out || !iter_out || !obj_out || !viol_out || !info)
+    return MIOSQP_EARG;
+  ENTER(e);
+  if (!e->have_int || !e->d.digest) {
+    g_err = "round_and_fix: call miosqp_qp_set_integer_rows and miosqp_qp_set_root first";
+    return MIOSQP_EARG;
+  }
+  if (K < 1 || K > RF_MAX_K) {
+    g_err = "round_and_fix: K must be in 1..32";
+    return MIOSQP_EARG;
+  }
+  if (max_iter <= 0 || (max_iter % e->chunk != 0 && max_iter != e->st.max_iter)) {
+    g_err = "round_and_fix: max_iter must be a positive multiple of check_termination or the engine's max_iter";
+    return MIOSQP_EARG;
+  }
+  const size_t n = e->n, M = e->M;
+  for (size_t j = 0; j < M; j++)
+    if (l[j] > u[j]) return MIOSQP_EBOUNDS;
+  if (e->Bcap == 0) {
+    int cap = e->st.max_batch > 1 ? e->st.max_batch : 64;
+    if (cap > 1024) cap = 1024;
+    int rc = alloc_batch(e, cap);
+    if (rc) return rc;
+  }
+  const size_t nin = 3 * M + n, nrec = RF_REC_DOUBLES + n;
+  if (!e->rf_in) {
+    int rc = dalloc(e, &e->rf_in, nin);
+    if (!rc) rc = dalloc(e, &e->rf_rec, nrec);
+    if (rc) return rc;
+    HIPCHK(hipHostMalloc((void **)&e->hrf_rec, sizeof(double) * (nin > nrec ? nin : nrec), hipHostMallocDefault));
+  }
+  const double t0 = wall();
+  const int B = K;
+  if (int rc = slice_begin(e, B)) return rc;
+  // the pinned block carries the parent in and, once the stream has drained, the record and the winner's x out
+  double *h = e->hrf_rec;
+  memcpy(h, l, sizeof(double) * M);
+  memcpy(h + M, u, sizeof(double) * M);
+  memcpy(h + 2 * M, x, sizeof(double) * n);
+  memcpy(h + 2 * M + n, y, sizeof(double) * M);
+  const Dev &d = e->d;
+  HIPCHK(hipEventRecord(e->ev0, e->stream));
+  HIPCHK(hipMemcpyAsync(e->rf_in, h, sizeof(double) * nin, hipMemcpyHostToDevice, e->stream));
+  const int big = (int)(n > M ? n : M);
+  hipLaunchKernelGGL(k_rf_candidates, dim3((big + 255) / 256, B), dim3(256), 0, e->stream, d, e->rf_in, K);
+  if (int rc = slice_run(e, B, max_iter)) return rc;
+  RfRec *drec = (RfRec *)e->rf_rec;
+  hipLaunchKernelGGL(k_rf_pick, dim3(1), dim3(64), 0, e->stream, d, drec, K, upper);
+  hipLaunchKernelGGL(k_rf_gather, dim3(((int)n + 255) / 256), dim3(256), 0, e->stream, d, drec,
+                     e->rf_rec + RF_REC_DOUBLES);
+  HIPCHK(hipMemcpyAsync(h, e->rf_rec, sizeof(double) * nrec, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipEventRecord(e->ev1, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  const RfRec &r = *(const RfRec *)h;
+  int64_t iters = 0;
+  for (int k = 0; k < K; k++) {
+    status_out[k] = r.status[k];
+    iter_out[k] = r.iter[k];
+    obj_out[k] = r.obj[k];
+    viol_out[k] = r.viol[k];
+    iters += r.iter[k];
+  }
+  if (r.chosen >= 0) memcpy(x_out, h + RF_REC_DOUBLES, sizeof(double) * n);
+  float ms = 0;
+  HIPCHK(hipEventElapsedTime(&ms, e->ev0, e->ev1));
+  info->chosen = r.chosen;
+  info->feasible = r.feasible;
+  info->candidates = K;
   info->iters = (int32_t)iters;
   info->device_time = 1e-3 * ms;
   info->run_time = wall() - t0;

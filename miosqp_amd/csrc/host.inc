@@ -176,6 +176,9 @@ struct miosqp_qp_engine {
   // staged in, the score record out; device / pinned host
   double *sb_in = nullptr, *hsb_in = nullptr;
   SbRec *sb_rec = nullptr, *hsb_rec = nullptr;
+  // round and fix: the parent (l | u | x | y) on the device, the record with the winner's x behind it (doubles); one
+  // pinned host block serves both directions
+  double *rf_in = nullptr, *rf_rec = nullptr, *hrf_rec = nullptr;
   hipGraphExec_t xb_full[16] = {}, xb_tail[16] = {};
   hipGraph_t gb_full[16] = {}, gb_tail[16] = {};
   bool compact = true;   // compaction of converged columns in solve_batch (MIOSQP_COMPACT=0 disables)

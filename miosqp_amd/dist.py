@@ -213,6 +213,8 @@ class ShardedSearch(object):
     once (on rank 0) in `nodes` / `iters`."""
 
     def __init__(self, model, comm=None):
+        if model.work.settings.get('primal_heuristic', 0) != 0:
+            raise ValueError("sharded search: primal_heuristic 0 only (round and fix runs in MIOSQP.solve)")
         self.model = model
         self.work = model.work
         self.comm = comm if comm is not None else LocalComm()
@@ -571,6 +573,8 @@ class ShardedStream(object):
         from miosqp_amd import stream
         if model.work.settings.get('branching_rule', 0) != 0:
             raise ValueError("sharded stream: branching_rule 0 only (strong / reliability branching run in MIOSQP.solve)")
+        if model.work.settings.get('primal_heuristic', 0) != 0:
+            raise ValueError("sharded stream: primal_heuristic 0 only (round and fix runs in MIOSQP.solve)")
         self.model, self.work = model, model.work
         self.comm = comm if comm is not None else LocalComm()
         self.seq = ShardedSearch(model, self.comm)  # replicated ramp-up (its _visit / _agree / counters)

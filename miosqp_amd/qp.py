@@ -245,6 +245,29 @@ class OSQP(object):
         return types.SimpleNamespace(chosen=info.chosen, lower=lower, status=status, iter=iters, score=score[:K],
                                      iters=info.iters, device_time=info.device_time, run_time=info.run_time)
 
+    def round_and_fix(self, l, u, x, y, upper, K, max_iter):
+        """The round-and-fix heuristic on one solved node (bounds l, u; clamped x; y): K candidates with every integer
+        row fixed to min(max(floor(x_i + (k + 1) / (K + 1)), l), u), solved together with at most `max_iter` iterations
+        each and judged on the device (miosqp_qp_round_and_fix).  status / iter / obj / viol: per candidate (objective of
+        the rounded point and its worst violation of the root's constraints, <= 0 feasible); chosen: the feasible
+        candidate of lowest objective below `upper`, -1 without one; x: its rounded point, None without one."""
+        l, u = _f64(l, self.m, "l"), _f64(u, self.m, "u")
+        x, y = _f64(x, self.n, "x"), _f64(y, self.m, "y")
+        K = int(K)
+        kk = max(K, 1)
+        xo, obj, viol = np.empty(self.n), np.empty(kk), np.empty(kk)
+        status, iters = np.empty(kk, dtype=np.int32), np.empty(kk, dtype=np.int32)
+        info = _lib.RfInfo()
+        rc = _check(self._lib.miosqp_qp_round_and_fix(self._h, _lib.as_d(l), _lib.as_d(u), _lib.as_d(x), _lib.as_d(y),
+                                                      float(upper), K, int(max_iter), _lib.as_d(xo), _lib.as_i(status),
+                                                      _lib.as_i(iters), _lib.as_d(obj), _lib.as_d(viol),
+                                                      C.byref(info)), "round_and_fix")
+        if rc == 1:
+            raise ValueError("Lower bound must be lower than or equal to upper bound")
+        return types.SimpleNamespace(chosen=info.chosen, x=xo if info.chosen >= 0 else None, status=status[:K],
+                                     iter=iters[:K], obj=obj[:K], viol=viol[:K], feasible=info.feasible,
+                                     iters=info.iters, device_time=info.device_time, run_time=info.run_time)
+
     def solve_tree(self, l, u, x0, y0, upper0, x_inc0, tree_explor_rule, max_iter_bb):
         """A whole tree search in one launch (small problems); None when the engine does not cover this size."""
         l, u = _f64(l, self.m, "l"), _f64(u, self.m, "u")

@@ -143,6 +143,8 @@ class StreamSearch(object):
             raise TypeError("the streaming search needs the HIP engine (miosqp_amd.qp)")
         if w.settings.get('branching_rule', 0) != 0:
             raise ValueError("streaming search: branching_rule 0 only (strong / reliability branching run in MIOSQP.solve)")
+        if w.settings.get('primal_heuristic', 0) != 0:
+            raise ValueError("streaming search: primal_heuristic 0 only (round and fix runs in MIOSQP.solve)")
         self.columns = int(columns)
         self.p = w.data.n_int
         # every column dives on its own, and until the first incumbent nothing can be pruned: on config 2 the first
@@ -419,6 +421,8 @@ class NativeStreamSearch(object):
             raise TypeError("the native streaming search needs the HIP engine (miosqp_amd.qp)")
         if w.settings.get('branching_rule', 0) != 0:
             raise ValueError("streaming search: branching_rule 0 only (strong / reliability branching run in MIOSQP.solve)")
+        if w.settings.get('primal_heuristic', 0) != 0:
+            raise ValueError("streaming search: primal_heuristic 0 only (round and fix runs in MIOSQP.solve)")
         if w.settings['tree_explor_rule'] not in (0, 1):
             raise ValueError('Tree exploring strategy not recognized')
         self.columns, self.p, self.rounds = int(columns), w.data.n_int, int(rounds)
