@@ -94,6 +94,15 @@ def heuristic_settings(settings, qp_settings):
     return dict(on=int(on), K=int(K), max_iter=int(cap), every=int(every))
 
 
+def require_plain_search(settings, who, rule=True, heuristic=True):
+    """The searches beside MIOSQP.solve branch on the most fractional variable and run no primal heuristic: `who`
+    (the search's name in the message) refuses the settings that ask for more."""
+    if rule and settings.get('branching_rule', 0) != 0:
+        raise ValueError("%s: branching_rule 0 only (strong / reliability branching run in MIOSQP.solve)" % who)
+    if heuristic and settings.get('primal_heuristic', 0) != 0:
+        raise ValueError("%s: primal_heuristic 0 only (round and fix runs in MIOSQP.solve)" % who)
+
+
 def rf_roundings(xi, lo, hi, K):
     """The K rounding vectors of round and fix for the integer entries xi inside the node's bounds lo, hi:
     row k is min(max(floor(xi + theta_k), lo), hi) with theta_k = (k + 1) / (K + 1) as one double division."""
@@ -234,6 +243,7 @@ class Workspace(object):
         self._second = {}  # second relaxation solvers of the host-side restatements, by iteration cap
         self.backend = backend if backend is not None else _default_backend()
         self.constant = self.backend.constant
+        self.ok = (self.constant('OSQP_SOLVED'), self.constant('OSQP_MAX_ITER_REACHED'))  # the statuses with an x
         self.solver = self.backend.OSQP()
         self.qp_settings = {} if qp_settings is None else qp_settings
         # workspace.py:67-68 expands the *argument*: qp_settings=None is a TypeError there too
@@ -371,13 +381,12 @@ class Workspace(object):
         if unrel:
             cc = self._most_fractional(leaf, unrel, sb['K'])
             r = self.strong_branch(leaf, cc)
-            ok = (self.constant('OSQP_SOLVED'), self.constant('OSQP_MAX_ITER_REACHED'))
             K = len(cc)
             for j, c in enumerate(cc):
                 v = leaf.x[self.data.i_idx[c]]
                 for side, f in ((0, v - np.floor(v)), (1, np.ceil(v) - v)):
                     b = side * K + j
-                    if r.status[b] in ok:
+                    if r.status[b] in self.ok:
                         self.record_gain(c, side, r.lower[b] - leaf.lower, f)
                 score[c] = r.score[j]
         psi = self.pseudo_costs()
@@ -424,9 +433,8 @@ class Workspace(object):
             st['solve_time'] += r.run_time
             return r
         solver = self.sb_solver()
-        K, m, k_int, ii = len(cand), data.m, data.n_int, data.i_idx
+        K, m, ii = len(cand), data.m, data.i_idx
         lower, status, iters = np.full(2 * K, np.nan), np.empty(2 * K, dtype=np.int32), np.empty(2 * K, dtype=np.int32)
-        ok = (self.constant('OSQP_SOLVED'), self.constant('OSQP_MAX_ITER_REACHED'))
         for side in (0, 1):
             for j, c in enumerate(cand):
                 b = side * K + j
@@ -437,21 +445,30 @@ class Workspace(object):
                     l[m + c] = np.ceil(leaf.x[ii[c]])
                 if np.any(l > u):
                     raise RuntimeError('branching produced l > u')
-                solver.update(l=l, u=u)
-                solver.warm_start(x=leaf.x, y=leaf.y)
-                res = solver.solve()
-                status[b], iters[b] = res.info.status_val, res.info.iter
-                st['solve_time'] += res.info.run_time
-                if status[b] in ok:
-                    x = res.x
-                    x[ii] = np.minimum(np.maximum(x[ii], l[-k_int:]), u[-k_int:])
+                status[b], iters[b], x = self.capped_child(leaf, l, u, solver, st)
+                if x is not None:
                     lower[b] = data.compute_obj_val(x)
-        _, score, chosen = sb_scores(lower, status, leaf.lower, sb['eps'], ok)
+        _, score, chosen = sb_scores(lower, status, leaf.lower, sb['eps'], self.ok)
         st['calls'] += 1
         st['children'] += 2 * K
         st['osqp_iter'] += int(np.sum(iters))
         return types.SimpleNamespace(chosen=chosen, lower=lower, status=status, iter=iters, score=score,
                                      iters=int(np.sum(iters)))
+
+    def capped_child(self, leaf, l, u, solver, stats):
+        """Host restatement of one capped child solve: the node `leaf` with the bounds l, u, warm-started from the
+        leaf, by the reference's calls on the second solver; its run time goes to stats['solve_time'].  Returns status,
+        iterations and x with its integer entries clamped into their rows of l, u (None when the status has no x)."""
+        k_int, ii = self.data.n_int, self.data.i_idx
+        solver.update(l=l, u=u)
+        solver.warm_start(x=leaf.x, y=leaf.y)
+        res = solver.solve()
+        stats['solve_time'] += res.info.run_time
+        x = None
+        if res.info.status_val in self.ok:
+            x = res.x
+            x[ii] = np.minimum(np.maximum(x[ii], l[-k_int:]), u[-k_int:])
+        return res.info.status_val, res.info.iter, x
 
     def sb_solver(self, max_iter=None):
         """The second relaxation solver of the host-side restatements (strong branching, round and fix), created on
@@ -483,7 +500,6 @@ class Workspace(object):
         else:
             solver = self.sb_solver(rf['max_iter'])
             k_int, ii = data.n_int, data.i_idx
-            ok = (self.constant('OSQP_SOLVED'), self.constant('OSQP_MAX_ITER_REACHED'))
             tol = self.qp_settings['eps_abs']
             fix = rf_roundings(leaf.x[ii], leaf.l[-k_int:], leaf.u[-k_int:], K)
             status, iters = np.empty(K, dtype=np.int32), np.empty(K, dtype=np.int32)
@@ -493,14 +509,8 @@ class Workspace(object):
                 l, u = np.copy(leaf.l), np.copy(leaf.u)
                 l[-k_int:] = fix[k]
                 u[-k_int:] = fix[k]
-                solver.update(l=l, u=u)
-                solver.warm_start(x=leaf.x, y=leaf.y)
-                res = solver.solve()
-                status[k], iters[k] = res.info.status_val, res.info.iter
-                st['solve_time'] += res.info.run_time
-                if status[k] in ok:
-                    x = res.x
-                    x[ii] = np.minimum(np.maximum(x[ii], l[-k_int:]), u[-k_int:])
+                status[k], iters[k], x = self.capped_child(leaf, l, u, solver, st)
+                if x is not None:
                     x = self.get_integer_solution(x)
                     z = data.A.dot(x)
                     viol[k] = max(np.max(data.l - tol - z), np.max(z - data.u - tol))

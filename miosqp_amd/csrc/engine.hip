@@ -230,8 +230,7 @@ struct CoopNode {
 #include "kernels_tree.inc"  // a whole branch-and-bound tree in one launch (LDS-resident problems)
 #include "kernels_pool.inc"  // device-resident leaf pool, streaming batch (refill / harvest between chunks)
 #include "kernels_bstream.inc"  // the streaming batch as ONE persistent launch: iterations, test, harvest and refill per column group (kbs)
-#include "kernels_sb.inc"  // strong branching: 2K children built from one parent on the device, scored after the batch solve
-#include "kernels_rf.inc"  // round and fix: K rounded-and-fixed candidates of one parent, judged from the batch epilogue
+#include "kernels_derived.inc"  // nodes derived from one parent on the device, judged after the batch solve: strong branching, round and fix
 #include "host.inc"  // host side: engine object, allocation, launches, graph capture, solve loops
 #include "host_pool.inc"  // host side of the leaf pool (C ABI miosqp_qp_pool_*)
 #include "host_search.inc"  // node-at-a-time branch and bound driven from the host in C++ (C ABI miosqp_qp_search_*)
@@ -354,9 +353,7 @@ int miosqp_qp_cleanup(miosqp_qp_engine *e) {
   if (e->hb_out) hipHostFree(e->hb_out);
   if (e->hb_int) hipHostFree(e->hb_int);
   if (e->hb_dbl) hipHostFree(e->hb_dbl);
-  if (e->hsb_in) hipHostFree(e->hsb_in);
-  if (e->hsb_rec) hipHostFree(e->hsb_rec);
-  if (e->hrf_rec) hipHostFree(e->hrf_rec);
+  if (e->h_der) hipHostFree(e->h_der);
   for (int k = 0; k < 16; k++) {
     if (e->xb_full[k]) hipGraphExecDestroy(e->xb_full[k]);
     if (e->xb_tail[k]) hipGraphExecDestroy(e->xb_tail[k]);
@@ -1151,12 +1148,7 @@ int miosqp_qp_solve_batch(miosqp_qp_engine *e, int32_t B, const double *l, const
   const size_t n = e->n, M = e->M;
   for (size_t k = 0; k < (size_t)B * M; k++)
     if (l[k] > u[k]) return MIOSQP_EBOUNDS;
-  if (e->Bcap == 0) {
-    int cap = e->st.max_batch > 1 ? e->st.max_batch : 64;
-    if (cap > 1024) cap = 1024;
-    int rc = alloc_batch(e, cap);
-    if (rc) return rc;
-  }
+  if (int rc = ensure_batch(e)) return rc;
   for (int s0 = 0; s0 < B; s0 += e->Bcap) {
     const int nb = B - s0 < e->Bcap ? B - s0 : e->Bcap;
     int rc = solve_slice(e, nb, l + s0 * M, u + s0 * M, x0 + s0 * n, y0 + s0 * M, x_out + s0 * n, y_out + s0 * M,
@@ -1192,48 +1184,22 @@ int miosqp_qp_strong_branch(miosqp_qp_engine *e, const double *l, const double *
       return MIOSQP_EARG;
     }
   const size_t n = e->n, M = e->M, m_orig = (size_t)e->d.m_orig;
-  for (size_t j = 0; j < M; j++)
-    if (l[j] > u[j]) return MIOSQP_EBOUNDS;
   // a child whose new bound crosses the other one (Workspace.add_left / add_right refuse it too)
   for (int k = 0; k < K; k++) {
     const double v = x[e->h_iidx[cand[k]]];
     if (std::floor(v) < l[m_orig + cand[k]] || std::ceil(v) > u[m_orig + cand[k]]) return MIOSQP_EBOUNDS;
   }
-  if (e->Bcap == 0) {
-    int cap = e->st.max_batch > 1 ? e->st.max_batch : 64;
-    if (cap > 1024) cap = 1024;
-    int rc = alloc_batch(e, cap);
-    if (rc) return rc;
-  }
-  const size_t nin = 3 * M + n + SB_MAX_K / 2;
-  if (!e->sb_in) {
-    int rc = dalloc(e, &e->sb_in, nin);
-    if (!rc) rc = dalloc(e, &e->sb_rec, 1);
-    if (rc) return rc;
-    HIPCHK(hipHostMalloc((void **)&e->hsb_in, sizeof(double) * nin, hipHostMallocDefault));
-    HIPCHK(hipHostMalloc((void **)&e->hsb_rec, sizeof(SbRec), hipHostMallocDefault));
-  }
-  const double t0 = wall();
   const int B = 2 * K;
-  if (int rc = slice_begin(e, B)) return rc;
-  double *h = e->hsb_in;
-  memcpy(h, l, sizeof(double) * M);
-  memcpy(h + M, u, sizeof(double) * M);
-  memcpy(h + 2 * M, x, sizeof(double) * n);
-  memcpy(h + 2 * M + n, y, sizeof(double) * M);
-  memcpy(h + 3 * M + n, cand, sizeof(int32_t) * K);
+  double t0;
+  if (int rc = derived_begin(e, B, l, u, x, y, cand, sizeof(int32_t) * K, &t0)) return rc;
   const Dev &d = e->d;
-  HIPCHK(hipEventRecord(e->ev0, e->stream));
-  HIPCHK(hipMemcpyAsync(e->sb_in, h, sizeof(double) * nin, hipMemcpyHostToDevice, e->stream));
   const int big = (int)(n > M ? n : M);
-  hipLaunchKernelGGL(k_sb_children, dim3((big + 255) / 256, B), dim3(256), 0, e->stream, d, e->sb_in,
-                     (const int *)(e->sb_in + 3 * M + n), K);
+  hipLaunchKernelGGL(k_sb_children, dim3((big + 255) / 256, B), dim3(256), 0, e->stream, d, e->der_in,
+                     (const int *)(e->der_in + 3 * M + n), K);
   if (int rc = slice_run(e, B, max_iter)) return rc;
-  hipLaunchKernelGGL(k_sb_score, dim3(1), dim3(64), 0, e->stream, d, e->sb_rec, K, parent_lower, eps);
-  HIPCHK(hipMemcpyAsync(e->hsb_rec, e->sb_rec, sizeof(SbRec), hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipEventRecord(e->ev1, e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
-  const SbRec &r = *e->hsb_rec;
+  hipLaunchKernelGGL(k_sb_score, dim3(1), dim3(64), 0, e->stream, d, (SbRec *)e->der_rec, K, parent_lower, eps);
+  if (int rc = derived_end(e, (sizeof(SbRec) + 7) / 8, &info->device_time)) return rc;
+  const SbRec &r = *(const SbRec *)e->h_der;
   int64_t iters = 0;
   for (int b = 0; b < B; b++) {
     lower_out[b] = r.lower[b];
@@ -1242,12 +1208,9 @@ int miosqp_qp_strong_branch(miosqp_qp_engine *e, const double *l, const double *
     iters += r.iter[b];
   }
   for (int k = 0; k < K; k++) score_out[k] = r.score[k];
-  float ms = 0;
-  HIPCHK(hipEventElapsedTime(&ms, e->ev0, e->ev1));
   info->chosen = r.chosen;
   info->children = B;
   info->iters = (int32_t)iters;
-  info->device_time = 1e-3 * ms;
   info->run_time = wall() - t0;
   return 0;
 }
@@ -1271,44 +1234,19 @@ int miosqp_qp_round_and_fix(miosqp_qp_engine *e, const double *l, const double *
     return MIOSQP_EARG;
   }
   const size_t n = e->n, M = e->M;
-  for (size_t j = 0; j < M; j++)
-    if (l[j] > u[j]) return MIOSQP_EBOUNDS;
-  if (e->Bcap == 0) {
-    int cap = e->st.max_batch > 1 ? e->st.max_batch : 64;
-    if (cap > 1024) cap = 1024;
-    int rc = alloc_batch(e, cap);
-    if (rc) return rc;
-  }
-  const size_t nin = 3 * M + n, nrec = RF_REC_DOUBLES + n;
-  if (!e->rf_in) {
-    int rc = dalloc(e, &e->rf_in, nin);
-    if (!rc) rc = dalloc(e, &e->rf_rec, nrec);
-    if (rc) return rc;
-    HIPCHK(hipHostMalloc((void **)&e->hrf_rec, sizeof(double) * (nin > nrec ? nin : nrec), hipHostMallocDefault));
-  }
-  const double t0 = wall();
   const int B = K;
-  if (int rc = slice_begin(e, B)) return rc;
-  // the pinned block carries the parent in and, once the stream has drained, the record and the winner's x out
-  double *h = e->hrf_rec;
-  memcpy(h, l, sizeof(double) * M);
-  memcpy(h + M, u, sizeof(double) * M);
-  memcpy(h + 2 * M, x, sizeof(double) * n);
-  memcpy(h + 2 * M + n, y, sizeof(double) * M);
+  double t0;
+  if (int rc = derived_begin(e, B, l, u, x, y, nullptr, 0, &t0)) return rc;
   const Dev &d = e->d;
-  HIPCHK(hipEventRecord(e->ev0, e->stream));
-  HIPCHK(hipMemcpyAsync(e->rf_in, h, sizeof(double) * nin, hipMemcpyHostToDevice, e->stream));
   const int big = (int)(n > M ? n : M);
-  hipLaunchKernelGGL(k_rf_candidates, dim3((big + 255) / 256, B), dim3(256), 0, e->stream, d, e->rf_in, K);
+  hipLaunchKernelGGL(k_rf_candidates, dim3((big + 255) / 256, B), dim3(256), 0, e->stream, d, e->der_in, K);
   if (int rc = slice_run(e, B, max_iter)) return rc;
-  RfRec *drec = (RfRec *)e->rf_rec;
+  RfRec *drec = (RfRec *)e->der_rec;
   hipLaunchKernelGGL(k_rf_pick, dim3(1), dim3(64), 0, e->stream, d, drec, K, upper);
   hipLaunchKernelGGL(k_rf_gather, dim3(((int)n + 255) / 256), dim3(256), 0, e->stream, d, drec,
-                     e->rf_rec + RF_REC_DOUBLES);
-  HIPCHK(hipMemcpyAsync(h, e->rf_rec, sizeof(double) * nrec, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipEventRecord(e->ev1, e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
-  const RfRec &r = *(const RfRec *)h;
+                     e->der_rec + RF_REC_DOUBLES);
+  if (int rc = derived_end(e, RF_REC_DOUBLES + n, &info->device_time)) return rc;
+  const RfRec &r = *(const RfRec *)e->h_der;
   int64_t iters = 0;
   for (int k = 0; k < K; k++) {
     status_out[k] = r.status[k];
@@ -1317,14 +1255,11 @@ int miosqp_qp_round_and_fix(miosqp_qp_engine *e, const double *l, const double *
     viol_out[k] = r.viol[k];
     iters += r.iter[k];
   }
-  if (r.chosen >= 0) memcpy(x_out, h + RF_REC_DOUBLES, sizeof(double) * n);
-  float ms = 0;
-  HIPCHK(hipEventElapsedTime(&ms, e->ev0, e->ev1));
+  if (r.chosen >= 0) memcpy(x_out, e->h_der + RF_REC_DOUBLES, sizeof(double) * n);
   info->chosen = r.chosen;
   info->feasible = r.feasible;
   info->candidates = K;
   info->iters = (int32_t)iters;
-  info->device_time = 1e-3 * ms;
   info->run_time = wall() - t0;
   return 0;
 }

@@ -172,13 +172,10 @@ struct miosqp_qp_engine {
   double *hb_in = nullptr, *hb_out = nullptr;
   int *hb_int = nullptr;       // status | iter
   double *hb_dbl = nullptr;    // pri | dua | obj | lower
-  // strong branching: the parent (l | u | x | y, 3M + n doubles) and 32 candidate positions (int32, 16 doubles' room)
-  // staged in, the score record out; device / pinned host
-  double *sb_in = nullptr, *hsb_in = nullptr;
-  SbRec *sb_rec = nullptr, *hsb_rec = nullptr;
-  // round and fix: the parent (l | u | x | y) on the device, the record with the winner's x behind it (doubles); one
-  // pinned host block serves both directions
-  double *rf_in = nullptr, *rf_rec = nullptr, *hrf_rec = nullptr;
+  // derived batches (strong branching, round and fix; derived_begin / derived_end): the parent (l | u | x | y, 3M + n
+  // doubles) and strong branching's 32 candidate positions (int32, 16 doubles' room) staged in, the feature's record
+  // out (round and fix: the winner's x behind it); device in / device record / ONE pinned block for both directions
+  double *der_in = nullptr, *der_rec = nullptr, *h_der = nullptr;
   hipGraphExec_t xb_full[16] = {}, xb_tail[16] = {};
   hipGraph_t gb_full[16] = {}, gb_tail[16] = {};
   bool compact = true;   // compaction of converged columns in solve_batch (MIOSQP_COMPACT=0 disables)
@@ -1467,6 +1464,16 @@ int alloc_batch(miosqp_qp_engine *e, int cap) {
   return 0;
 }
 
+// batched mode on first use: settings.max_batch columns, 64 without the setting, 1024 at the most
+int ensure_batch(miosqp_qp_engine *e) {
+  if (e->Bcap == 0) {
+    int cap = e->st.max_batch > 1 ? e->st.max_batch : 64;
+    if (cap > 1024) cap = 1024;
+    return alloc_batch(e, cap);
+  }
+  return 0;
+}
+
 // Before a slice of B columns is queued: the checks and the chunk graphs of its width (captured on an idle stream)
 int slice_begin(miosqp_qp_engine *e, int B) {
   const int ntiles = (B + 63) / 64;
@@ -1588,6 +1595,48 @@ int slice_run(miosqp_qp_engine *e, int B, int max_iter) {
   if (d.digest) hipLaunchKernelGGL(kb_heur_rows, dim3((d.M + 3) / 4, ntiles), dim3(256), 0, e->stream, d);
   hipLaunchKernelGGL(kb_obj_rows, dim3((d.n + 3) / 4, ntiles), dim3(256), 0, e->stream, d);
   hipLaunchKernelGGL(kb_obj_sum, dim3(ntiles), dim3(1024), 0, e->stream, d);
+  return 0;
+}
+
+// A derived batch (kernels_derived.inc), up to the point where the caller's builder kernel turns the uploaded parent
+// into B nodes in d.b_raw: bounds check, batched mode and the staging blocks on first use, slice_begin, then
+// l | u | x | y | extra (strong branching's candidate positions) through the pinned block into der_in.  *t0: when the
+// call's wall time starts (after the one-time allocations).
+int derived_begin(miosqp_qp_engine *e, int B, const double *l, const double *u, const double *x, const double *y,
+                  const void *extra, size_t extra_bytes, double *t0) {
+  const size_t n = e->n, M = e->M;
+  for (size_t j = 0; j < M; j++)
+    if (l[j] > u[j]) return MIOSQP_EBOUNDS;
+  if (int rc = ensure_batch(e)) return rc;
+  if (!e->h_der) {  // (the last of the three to be allocated)
+    const size_t nin = 3 * M + n + SB_MAX_K / 2, nrec = std::max((sizeof(SbRec) + 7) / 8, RF_REC_DOUBLES + n);
+    int rc = dalloc(e, &e->der_in, nin);
+    if (!rc) rc = dalloc(e, &e->der_rec, nrec);
+    if (rc) return rc;
+    HIPCHK(hipHostMalloc((void **)&e->h_der, sizeof(double) * std::max(nin, nrec), hipHostMallocDefault));
+  }
+  *t0 = wall();
+  if (int rc = slice_begin(e, B)) return rc;
+  double *h = e->h_der;
+  memcpy(h, l, sizeof(double) * M);
+  memcpy(h + M, u, sizeof(double) * M);
+  memcpy(h + 2 * M, x, sizeof(double) * n);
+  memcpy(h + 2 * M + n, y, sizeof(double) * M);
+  if (extra_bytes) memcpy(h + 3 * M + n, extra, extra_bytes);
+  HIPCHK(hipEventRecord(e->ev0, e->stream));
+  HIPCHK(hipMemcpyAsync(e->der_in, h, sizeof(double) * (3 * M + n) + extra_bytes, hipMemcpyHostToDevice, e->stream));
+  return 0;
+}
+
+// ... and once the caller's judge kernels are queued: the first rec_doubles of der_rec into the pinned block, the
+// stream drained, the device time from the upload to here
+int derived_end(miosqp_qp_engine *e, size_t rec_doubles, double *device_seconds) {
+  HIPCHK(hipMemcpyAsync(e->h_der, e->der_rec, sizeof(double) * rec_doubles, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipEventRecord(e->ev1, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  float ms = 0;
+  HIPCHK(hipEventElapsedTime(&ms, e->ev0, e->ev1));
+  *device_seconds = 1e-3 * ms;
   return 0;
 }
 

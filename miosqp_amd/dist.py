@@ -18,6 +18,8 @@ import os
 
 import numpy as np
 
+from miosqp_amd import bnb
+
 
 class LocalComm(object):
     """world_size 1: no collective."""
@@ -213,8 +215,7 @@ class ShardedSearch(object):
     once (on rank 0) in `nodes` / `iters`."""
 
     def __init__(self, model, comm=None):
-        if model.work.settings.get('primal_heuristic', 0) != 0:
-            raise ValueError("sharded search: primal_heuristic 0 only (round and fix runs in MIOSQP.solve)")
+        bnb.require_plain_search(model.work.settings, "sharded search", rule=False)
         self.model = model
         self.work = model.work
         self.comm = comm if comm is not None else LocalComm()
@@ -571,10 +572,7 @@ class ShardedStream(object):
         interface, e.g. search.HostedSearch (node-at-a-time relaxations, loop in the C++ library); step_kwargs: what
         its step() is called with (HostedSearch: nodes=, budget=)."""
         from miosqp_amd import stream
-        if model.work.settings.get('branching_rule', 0) != 0:
-            raise ValueError("sharded stream: branching_rule 0 only (strong / reliability branching run in MIOSQP.solve)")
-        if model.work.settings.get('primal_heuristic', 0) != 0:
-            raise ValueError("sharded stream: primal_heuristic 0 only (round and fix runs in MIOSQP.solve)")
+        bnb.require_plain_search(model.work.settings, "sharded stream")
         self.model, self.work = model, model.work
         self.comm = comm if comm is not None else LocalComm()
         self.seq = ShardedSearch(model, self.comm)  # replicated ramp-up (its _visit / _agree / counters)

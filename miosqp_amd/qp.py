@@ -98,6 +98,14 @@ def leaf_record_views(tensor, n_int, n, m):
     return tuple(DevicePtr(base + 8 * o, c) for o, c in zip(offs, cnts))
 
 
+def _digest(info):
+    """The node digest of a miosqp_qp_info (None from an engine without root bounds: miosqp_qp_set_root)."""
+    if info.int_inf < 0:
+        return None
+    return types.SimpleNamespace(int_inf=info.int_inf, nextvar=info.nextvar, heur_feasible=info.heur_viol <= 0.0,
+                                 heur_obj=info.heur_obj, info_viol=info.heur_viol)
+
+
 def _vec(a, size, name):
     """ctypes pointer of a leaf vector given as an array (host) or a DevicePtr"""
     if isinstance(a, DevicePtr):
@@ -190,13 +198,8 @@ class OSQP(object):
         if rc == 1:
             raise ValueError("Lower bound must be lower than or equal to upper bound")
         lower = None if np.isnan(info.lower) else info.lower
-        digest = None
-        if info.int_inf >= 0:
-            digest = types.SimpleNamespace(int_inf=info.int_inf, nextvar=info.nextvar,
-                                           heur_feasible=info.heur_viol <= 0.0, heur_obj=info.heur_obj,
-                                           info_viol=info.heur_viol)
         return types.SimpleNamespace(x=x, y=y, status_val=info.status_val, iter=info.iter,
-                                     run_time=info.run_time, lower=lower, info=info, digest=digest)
+                                     run_time=info.run_time, lower=lower, info=info, digest=_digest(info))
 
     def solve_batch(self, l, u, x0, y0):
         """B independent nodes sharing the factor; arrays are [B, .]."""
@@ -212,14 +215,8 @@ class OSQP(object):
                                                     _lib.as_d(y), infos), "solve_batch")
         if rc == 1:
             raise ValueError("Lower bound must be lower than or equal to upper bound")
-        digests = [None] * B
-        for k, i in enumerate(infos):
-            if i.int_inf >= 0:
-                digests[k] = types.SimpleNamespace(int_inf=i.int_inf, nextvar=i.nextvar,
-                                                   heur_feasible=i.heur_viol <= 0.0, heur_obj=i.heur_obj,
-                                                   info_viol=i.heur_viol)
         return types.SimpleNamespace(
-            digest=digests,
+            digest=[_digest(i) for i in infos],
             x=x, y=y, status_val=np.array([i.status_val for i in infos]),
             iter=np.array([i.iter for i in infos]), lower=np.array([i.lower for i in infos]),
             run_time=np.array([i.run_time for i in infos]), infos=infos)

@@ -141,10 +141,7 @@ class StreamSearch(object):
         self.eng = w.solver
         if not hasattr(self.eng, "pool_create"):
             raise TypeError("the streaming search needs the HIP engine (miosqp_amd.qp)")
-        if w.settings.get('branching_rule', 0) != 0:
-            raise ValueError("streaming search: branching_rule 0 only (strong / reliability branching run in MIOSQP.solve)")
-        if w.settings.get('primal_heuristic', 0) != 0:
-            raise ValueError("streaming search: primal_heuristic 0 only (round and fix runs in MIOSQP.solve)")
+        bnb.require_plain_search(w.settings, "streaming search")
         self.columns = int(columns)
         self.p = w.data.n_int
         # every column dives on its own, and until the first incumbent nothing can be pruned: on config 2 the first
@@ -419,10 +416,7 @@ class NativeStreamSearch(object):
         self.eng = w.solver
         if not hasattr(self.eng, "stream_create"):
             raise TypeError("the native streaming search needs the HIP engine (miosqp_amd.qp)")
-        if w.settings.get('branching_rule', 0) != 0:
-            raise ValueError("streaming search: branching_rule 0 only (strong / reliability branching run in MIOSQP.solve)")
-        if w.settings.get('primal_heuristic', 0) != 0:
-            raise ValueError("streaming search: primal_heuristic 0 only (round and fix runs in MIOSQP.solve)")
+        bnb.require_plain_search(w.settings, "streaming search")
         if w.settings['tree_explor_rule'] not in (0, 1):
             raise ValueError('Tree exploring strategy not recognized')
         self.columns, self.p, self.rounds = int(columns), w.data.n_int, int(rounds)

@@ -1,6 +1,6 @@
-"""Round and fix on the device (miosqp_qp_round_and_fix, csrc/kernels_rf.inc) against its CPU restatement (Workspace
-with the oracle backend: the reference's four calls per candidate on a second solver with max_iter = rf_max_iter, the
-acceptance rule in numpy), and settings["primal_heuristic"] = 1 over whole trees.
+"""Round and fix on the device (miosqp_qp_round_and_fix, csrc/kernels_derived.inc) against its CPU restatement
+(Workspace with the oracle backend: the reference's four calls per candidate on a second solver with
+max_iter = rf_max_iter, the acceptance rule in numpy), and settings["primal_heuristic"] = 1 over whole trees.
 
 Feasibility flags can only be compared where no candidate sits on the threshold.  In the restatement the smallest
 |viol| over the candidates of the roots used below is 6.2e-5 -- entries of -0.001 = -eps_abs are rows exactly on a
@@ -244,6 +244,66 @@ def test_round_and_fix_leaves_no_state_behind(oracle_mod):
     for key in ("status", "iter", "obj", "viol", "x"):
         np.testing.assert_array_equal(getattr(rf, key), getattr(rf2, key))
     assert (rf.chosen, rf.feasible, rf.iters) == (rf2.chosen, rf2.feasible, rf2.iters)
+
+
+def _fresh_engine(pr):
+    from miosqp_amd import qp
+    A, l, u = problems.extended(pr)
+    eng = qp.OSQP()
+    eng.setup(pr["P"], pr["q"], A, l, u, **problems.QP_SETTINGS)
+    eng.set_integer_rows(pr["i_idx"], pr["A"].shape[0])
+    eng.set_root(l, u, problems.BNB_SETTINGS["eps_int_feas"], problems.QP_SETTINGS["eps_abs"])
+    return eng
+
+
+# The second has M = 270: two blocks in x of the builder grid; the third n > M: n sizes that grid.  On the CPU oracle
+# all three have a SOLVED, fractional root and two such nodes at depth 2 (fractional integers 5, 1, 2 / 6, 8, 4 /
+# 3, 1, 1); the third at seed 2 because seeds 0 and 1 of its shape leave one and two nodes.
+SHARED_STAGING = [dict(problems.CONFIGS["cfg1"], seed=0), dict(n=40, m=250, p=20, seed=0),
+                  dict(n=300, m=20, p=8, seed=2)]
+
+
+@pytest.mark.parametrize("kw", SHARED_STAGING)
+def test_both_features_share_one_staging_block(oracle_mod, kw):
+    """Round and fix and strong branching stage through the same device and pinned blocks: interleaved on ONE engine,
+    each call returns bit for bit what it returns as the first call of a fresh engine, and so does the solve_batch
+    that follows them."""
+    from miosqp_amd import bnb
+    pr = problems.random_miqp(**kw)
+    o = bnb.MIOSQP(backend=oracle_mod)
+    o.setup(pr["P"], pr["q"], pr["A"], pr["l"], pr["u"], pr["i_idx"], pr["i_l"], pr["i_u"], dict(problems.BNB_SETTINGS),
+            dict(problems.QP_SETTINGS))
+    nodes = _nodes(o.work, 3)
+    assert len(nodes) == 3 and nodes[0].depth == 0 and all(lf.depth == 2 for lf in nodes[1:])
+    cap = 2 * 25  # two termination checks
+
+    def rf(K):
+        return lambda eng, lf: eng.round_and_fix(lf.l, lf.u, lf.x, lf.y, np.inf, K, cap)
+
+    def sb(largest):
+        def call(eng, lf):
+            cand = sorted(lf.frac_idx)[:32 if largest else 1]
+            return eng.strong_branch(lf.l, lf.u, lf.x, lf.y, lf.lower, cand, cap, 1e-6)
+        return call
+
+    def batch(eng, _):
+        return eng.solve_batch(*(np.stack([getattr(lf, key) for lf in nodes]) for key in ("l", "u", "x", "y")))
+
+    keys = {"rf": ("status", "iter", "obj", "viol", "x", "chosen", "feasible", "iters"),
+            "sb": ("lower", "status", "iter", "score", "chosen", "iters"),
+            "batch": ("x", "y", "status_val", "iter", "lower")}
+    sequence = (("rf", rf(32)), ("sb", sb(False)), ("rf", rf(1)), ("sb", sb(True)))
+    calls = [(kind, fn, lf) for lf in nodes for kind, fn in sequence]
+    calls.append(("batch", batch, None))
+    shared = _fresh_engine(pr)
+    for kind, fn, lf in calls:
+        got, want = fn(shared, lf), fn(_fresh_engine(pr), lf)
+        for key in keys[kind]:
+            a, b = getattr(got, key), getattr(want, key)
+            if b is None:
+                assert a is None, (kind, key)
+            else:
+                assert np.array_equal(a, b, equal_nan=True), (kind, key, a, b)
 
 
 def test_round_and_fix_argument_checks(oracle_mod):

@@ -1,6 +1,6 @@
-"""Strong branching on the device (miosqp_qp_strong_branch, csrc/kernels_sb.inc) against its CPU restatement (Workspace
-with the oracle backend: the reference's four calls per child on a second solver with max_iter = sb_max_iter, scores in
-numpy), and branching rules 1 and 2 over whole trees."""
+"""Strong branching on the device (miosqp_qp_strong_branch, csrc/kernels_derived.inc) against its CPU restatement
+(Workspace with the oracle backend: the reference's four calls per child on a second solver with max_iter = sb_max_iter,
+scores in numpy), and branching rules 1 and 2 over whole trees."""
 import numpy as np
 import pytest
 
