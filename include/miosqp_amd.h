@@ -361,6 +361,16 @@ const char *miosqp_qp_last_error(void);
  * termination test disabled (iterate-level parity against the oracle). x: n, z,y: M. */
 int miosqp_qp_debug_iterate(miosqp_qp_engine *e, int32_t k, double *x, double *z, double *y);
 
+/* debug: one device-resident product of the set-up copied to the host exactly as it lies in device memory, row-major,
+ * padding included (the tests of the set-up kernels compare it with a high-precision reference).  which:
+ *   0 d2inv (n x 1)        1 Linv (n x ld, strict lower)      2 LinvT (n x ld)
+ *   3 W, the explicit KKT inverse (N x ldw, N = M + n, constraints first)      4 Kc = [0 Abar; Abar^T Pbar] (N x ldw)
+ *   5 the persistent solver's tail inverse S^-1 (n x its own leading dimension)
+ * *rows and *ld are always reported; with out == NULL nothing else happens, otherwise capacity (in doubles) must be at
+ * least rows * ld.  A product this engine did not build is an error (MIOSQP_EUNSUPPORTED with a last_error text), never zeros.
+ * Waits for the engine's stream first; changes no state. */
+int miosqp_qp_debug_factor(miosqp_qp_engine *e, int32_t which, double *out, int64_t capacity, int32_t *rows, int32_t *ld);
+
 /* D (n), E (M), c of the Ruiz equilibration */
 int miosqp_qp_get_scaling(miosqp_qp_engine *e, double *D, double *E, double *c);
 

@@ -113,6 +113,7 @@ SYMBOLS = {
     "miosqp_qp_cleanup": (C.c_int, [C.c_void_p]),
     "miosqp_qp_last_error": (C.c_char_p, []),
     "miosqp_qp_debug_iterate": (C.c_int, [C.c_void_p, C.c_int32, dp, dp, dp]),
+    "miosqp_qp_debug_factor": (C.c_int, [C.c_void_p, C.c_int32, dp, C.c_int64, ip, ip]),
     "miosqp_qp_get_scaling": (C.c_int, [C.c_void_p, dp, dp, dp]),
     "miosqp_qp_get_factor_stats": (C.c_int, [C.c_void_p, i64p]),
     "miosqp_qp_get_inverse_guard": (C.c_int, [C.c_void_p, dp]),

@@ -1663,6 +1663,46 @@ int miosqp_qp_debug_iterate(miosqp_qp_engine *e, int32_t k, double *x, double *z
   return 0;
 }
 
+// debug: one device-resident product of the set-up copied to the host as it lies in device memory (row-major, padding
+// included).  Reads only: nothing the solvers use is touched.
+int miosqp_qp_debug_factor(miosqp_qp_engine *e, int32_t which, double *out, int64_t capacity, int32_t *rows, int32_t *ld) {
+  if (!e || !rows || !ld || which < 0 || which > 5) {
+    g_err = "debug_factor: bad argument";
+    return MIOSQP_EARG;
+  }
+  ENTER(e);
+  const Dev &d = e->d;
+  const int n = e->n, N = e->n + e->M;
+  const double *src = nullptr;
+  int r = 0, l = 0;
+  const char *name = "";
+  switch (which) {
+    case 0: src = d.d2inv; r = n; l = 1; name = "d2inv"; break;  // (a vector: n rows of one value)
+    case 1: src = d.Linv; r = n; l = d.ld; name = "Linv"; break;
+    case 2: src = d.LinvT; r = n; l = d.ld; name = "LinvT"; break;
+    case 3: src = d.W; r = N; l = d.ldw; name = "the explicit KKT inverse W"; break;
+    case 4: src = d.Kc; r = N; l = d.ldw; name = "Kc"; break;
+    default:
+      if (e->pers_capable) src = e->pp.sinv;
+      r = n; l = e->pp.sinv_ld; name = "the persistent solver's tail inverse";
+      break;
+  }
+  if (!src || l <= 0) {
+    g_err = std::string("debug_factor: this engine did not build ") + name;
+    return MIOSQP_EUNSUPPORTED;
+  }
+  *rows = r;
+  *ld = l;
+  if (!out) return 0;
+  if (capacity < (int64_t)r * l) {
+    g_err = "debug_factor: the output holds fewer than rows * ld values";
+    return MIOSQP_EARG;
+  }
+  HIPCHK(hipStreamSynchronize(e->stream));
+  HIPCHK(hipMemcpy(out, src, sizeof(double) * (size_t)r * l, hipMemcpyDeviceToHost));
+  return 0;
+}
+
 int miosqp_qp_get_scaling(miosqp_qp_engine *e, double *D, double *E, double *c) {
   if (!e) return MIOSQP_EARG;
   if (D) memcpy(D, e->sc.D.data(), sizeof(double) * e->n);

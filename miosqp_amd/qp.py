@@ -463,6 +463,20 @@ class OSQP(object):
                "debug_iterate")
         return x, z, y
 
+    def debug_factor(self, which):
+        """One device-resident product of the set-up read back (miosqp_qp_debug_factor): 0 d2inv, 1 Linv, 2 LinvT, 3 W,
+        4 Kc, 5 the persistent solver's tail inverse.  Returns (the logical part, the raw padded array): d2inv as a
+        vector of n, Linv / LinvT / the tail inverse n x n, W / Kc N x N; raw is rows x ld as it lies in device memory.
+        RuntimeError when this engine did not build the product."""
+        rows, ld = C.c_int32(), C.c_int32()
+        _check(self._lib.miosqp_qp_debug_factor(self._h, int(which), None, 0, C.byref(rows), C.byref(ld)), "debug_factor")
+        raw = np.empty((rows.value, ld.value))
+        _check(self._lib.miosqp_qp_debug_factor(self._h, int(which), _lib.as_d(raw), raw.size, C.byref(rows), C.byref(ld)),
+               "debug_factor")
+        if which == 0:
+            return raw[:, 0].copy(), raw
+        return raw[:, :rows.value].copy(), raw
+
     def scaling(self):
         D, E, c = np.empty(self.n), np.empty(self.m), C.c_double()
         _check(self._lib.miosqp_qp_get_scaling(self._h, _lib.as_d(D), _lib.as_d(E), C.byref(c)),
