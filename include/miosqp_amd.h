@@ -223,6 +223,44 @@ int miosqp_qp_round_and_fix(miosqp_qp_engine *e, const double *l, const double *
                             double upper, int32_t K, int32_t max_iter, double *x_out, int32_t *status_out,
                             int32_t *iter_out, double *obj_out, double *viol_out, miosqp_rf_info *info);
 
+/* ---- polishing: the exact optimum on the active set a first-order solution points to --------------------------
+ * OSQP's solution polishing (osqp_polish / polish.c of OSQP 0.6.x, which the reference's users reach by passing
+ * `polish` through qp_settings to osqp.OSQP.setup, /root/reference/miosqp/workspace.py:67-68; OSQP paper sec. 4),
+ * as a call of its own on one node: l, u its bounds (M), x, y an approximate solution of it (n, M), all unscaled.
+ *   1. z = A x.  Row j is lower-active when l_j == u_j or z_j - l_j < -y_j, otherwise upper-active when
+ *      u_j - z_j < y_j (OSQP's rule, plus: an equality row is always active); a bound at or beyond +-1e30 is infinite
+ *      and never active.  A_act: the active rows, b: their active bounds.
+ *   2. S = P + delta I + A_act^T A_act / delta (dense, factorised on the device by the set-up's blocked LDL^T);
+ *      ksolve(r1, r2): dx = S^-1 (r1 + A_act^T r2 / delta), dy = (A_act dx - r2) / delta -- block elimination of the
+ *      regularised KKT matrix [[P + delta I, A_act^T], [A_act, -delta I]].
+ *   3. (xh, yh) = ksolve(-q, b), then refine_iter times += ksolve(-q - P xh - A_act^T yh, b - A_act xh): the residuals
+ *      of the UNregularised system.  yh is zero on inactive rows.
+ *   4. pri = max_j max(l_j - (A xh)_j, (A xh)_j - u_j, 0), dua = |P xh + q + A^T yh|_inf over ALL rows, and the same two
+ *      numbers for (x, y).  Accepted when no pivot of S was <= 0, pri_after <= max(pri_before, 1e-10) and
+ *      dua_after <= max(dua_before, 1e-10) -- decided on the device.
+ * The arithmetic is done on the unscaled matrices.  x_out / y_out: the polished point when accepted, otherwise the input
+ * bit for bit.  Reads nothing and writes nothing the node solvers use: solve_node answers the same before and after.
+ * MIOSQP_EBOUNDS: some l > u; MIOSQP_EARG: delta <= 0, refine_iter outside 0..10, or a NaN in l, u, x or y (a primal
+ * infeasible node has no x to polish); MIOSQP_EUNSUPPORTED: n beyond 19 000 (one row of S per workgroup in LDS). */
+typedef struct miosqp_polish_info {
+  int32_t accepted;     /* 1: x_out / y_out hold the polished point */
+  int32_t reason;       /* 0 ok, 1 factorisation (a pivot <= 0), 2 primal residual grew, 3 dual residual grew */
+  int32_t n_lower;      /* rows active at their lower bound (equality rows included) */
+  int32_t n_upper;
+  double pri_before, dua_before;  /* of the input */
+  double pri_after, dua_after;    /* of the polished point, accepted or not (NaN after reason 1) */
+  double obj;           /* .5 xh' P xh + q' xh of the polished point, accepted or not (NaN after reason 1) */
+  double device_time;   /* seconds between the events around the call */
+  double run_time;      /* wall seconds of the call (the one-time allocation of the first call excluded) */
+} miosqp_polish_info;
+
+int miosqp_qp_polish(miosqp_qp_engine *e, const double *l, const double *u, const double *x, const double *y,
+                     double delta, int32_t refine_iter, double *x_out, double *y_out, miosqp_polish_info *info);
+
+/* device seconds of the last miosqp_qp_polish call by stage: classification, rows of S, factorisation and inverse,
+ * solves + refinement + acceptance (zeros before the first call).  No counterpart in OSQP, which reports one polish_time. */
+int miosqp_qp_get_polish_stages(miosqp_qp_engine *e, double *seconds);
+
 /* ---- a whole tree search in one launch (small problems) ------------------------------------------------
  * the MPC re-solve path (/root/reference/miosqp/solver.py:65-172 per MIQP,
  * examples/power_converter/power_converter.py:421-508 per sampling step).  For problems the LDS-resident solver

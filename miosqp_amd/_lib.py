@@ -58,6 +58,12 @@ class RfInfo(C.Structure):
                 ("device_time", C.c_double), ("run_time", C.c_double)]
 
 
+class PolishInfo(C.Structure):
+    _fields_ = [("accepted", C.c_int32), ("reason", C.c_int32), ("n_lower", C.c_int32), ("n_upper", C.c_int32),
+                ("pri_before", C.c_double), ("dua_before", C.c_double), ("pri_after", C.c_double),
+                ("dua_after", C.c_double), ("obj", C.c_double), ("device_time", C.c_double), ("run_time", C.c_double)]
+
+
 class PoolDigest(C.Structure):
     _fields_ = [("slot", C.c_int32), ("status_val", C.c_int32), ("iter", C.c_int32), ("int_inf", C.c_int32),
                 ("nextvar", C.c_int32), ("reserved", C.c_int32), ("lower", C.c_double), ("heur_viol", C.c_double),
@@ -81,6 +87,8 @@ SYMBOLS = {
                                           dp, ip, ip, dp, C.POINTER(SbInfo)]),
     "miosqp_qp_round_and_fix": (C.c_int, [C.c_void_p, dp, dp, dp, dp, C.c_double, C.c_int32, C.c_int32, dp, ip, ip, dp, dp,
                                           C.POINTER(RfInfo)]),
+    "miosqp_qp_polish": (C.c_int, [C.c_void_p, dp, dp, dp, dp, C.c_double, C.c_int32, dp, dp, C.POINTER(PolishInfo)]),
+    "miosqp_qp_get_polish_stages": (C.c_int, [C.c_void_p, dp]),
     "miosqp_qp_solve_trees": (C.c_int, [C.c_void_p, C.c_int32, dp, dp, dp, dp, dp, dp, dp, C.c_int32, C.c_int32, dp,
                                         C.POINTER(TreeInfo)]),
     "miosqp_qp_search_create": (C.c_int, [C.c_void_p, C.c_int32]),

@@ -94,9 +94,29 @@ def heuristic_settings(settings, qp_settings):
     return dict(on=int(on), K=int(K), max_iter=int(cap), every=int(every))
 
 
-def require_plain_search(settings, who, rule=True, heuristic=True):
-    """The searches beside MIOSQP.solve branch on the most fractional variable and run no primal heuristic: `who`
-    (the search's name in the message) refuses the settings that ask for more."""
+def polish_settings(settings):
+    """Polishing of the incumbent and its parameters, checked (MIOSQP.setup calls this before anything is built).
+    polish_incumbent 0: the incumbent as the search found it; 1: re-solved with its integers fixed and polished
+    (Workspace.polish_incumbent)."""
+    on = settings.get('polish_incumbent', 0)
+    if on not in (0, 1):
+        raise ValueError('polish_incumbent must be 0 or 1')
+    delta = settings.get('polish_delta', 1e-6)
+    if isinstance(delta, bool) or not isinstance(delta, (int, float, np.integer, np.floating)) \
+            or not (delta > 0 and np.isfinite(delta)):
+        raise ValueError('polish_delta must be a positive number')
+    it = settings.get('polish_refine_iter', 3)
+    if isinstance(it, bool) or not isinstance(it, (int, float, np.integer, np.floating)) or int(it) != it \
+            or not 0 <= it <= 10:
+        raise ValueError('polish_refine_iter must be an integer in 0..10')
+    return dict(on=int(on), delta=float(delta), refine_iter=int(it))
+
+
+def require_plain_search(settings, who, rule=True, heuristic=True, polish=True):
+    """The searches beside MIOSQP.solve branch on the most fractional variable, run no primal heuristic and do not
+    polish their incumbent: `who` (the search's name in the message) refuses the settings that ask for more."""
+    if polish and settings.get('polish_incumbent', 0) != 0:
+        raise ValueError("%s: polish_incumbent 0 only (the incumbent is polished by MIOSQP.solve)" % who)
     if rule and settings.get('branching_rule', 0) != 0:
         raise ValueError("%s: branching_rule 0 only (strong / reliability branching run in MIOSQP.solve)" % who)
     if heuristic and settings.get('primal_heuristic', 0) != 0:
@@ -127,6 +147,86 @@ def sb_scores(lower, status, parent_lower, eps, ok):
         gd, gu = gain[k], gain[K + k]
         score[k] = (gd if gd > eps else eps) * (gu if gu > eps else eps)
     return gain, score, int(np.argmax(score))
+
+
+POLISH_INFTY = 1e30  # a bound at or beyond it is infinite (the engine's constant)
+
+
+def polish_restatement(P, q, A, l, u, x, y, delta=1e-6, refine_iter=3):
+    """Polishing of one node's solution in dense numpy: what `OSQP.polish` of the HIP engine computes on the device
+    (include/miosqp_amd.h: miosqp_qp_polish), used where the backend has none.  A, l, u: all M rows; everything unscaled.
+
+    1. z = A x; row j is lower-active when l_j == u_j or z_j - l_j < -y_j, otherwise upper-active when u_j - z_j < y_j;
+       an infinite bound is never active.
+    2. S = P + delta I + A_act' A_act / delta (Cholesky); ksolve(r1, r2): dx = S^-1 (r1 + A_act' r2 / delta),
+       dy = (A_act dx - r2) / delta.
+    3. (xh, yh) = ksolve(-q, b), then refine_iter times += ksolve of the unregularised system's residuals.
+    4. accepted when S was positive definite, pri_after <= max(pri_before, 1e-10), dua_after <= max(dua_before, 1e-10)
+       (pri, dua over all rows); otherwise x, y are the input and reason says why (1 factorisation, 2 primal, 3 dual).
+
+    Besides the record: active (per row -1 lower, 1 upper, 0 inactive), margin (per row the smallest distance from
+    equality of the comparisons that classified it; inf for equality rows and rows without a finite bound: an input
+    with a tiny margin sits on a tie and another summation order may classify it differently), xh, yh (the polished
+    point whether accepted or not; None after reason 1)."""
+    P = np.asarray(P.todense()) if spa.issparse(P) else np.asarray(P, dtype=float)
+    A = np.asarray(A.todense()) if spa.issparse(A) else np.asarray(A, dtype=float)
+    q, l, u = np.asarray(q, dtype=float), np.asarray(l, dtype=float), np.asarray(u, dtype=float)
+    x, y = np.asarray(x, dtype=float), np.asarray(y, dtype=float)
+    M, n = A.shape
+    z = A.dot(x)
+    active, margin, b = np.zeros(M, dtype=np.int64), np.full(M, np.inf), np.zeros(M)
+    for j in range(M):
+        lo_fin, up_fin, eq = l[j] > -POLISH_INFTY, u[j] < POLISH_INFTY, l[j] == u[j]
+        if lo_fin and eq:
+            active[j], b[j] = -1, l[j]
+            continue
+        if lo_fin:
+            margin[j] = abs((z[j] - l[j]) + y[j])
+            if z[j] - l[j] < -y[j]:
+                active[j], b[j] = -1, l[j]
+                continue
+        if up_fin:
+            margin[j] = min(margin[j], abs((u[j] - z[j]) - y[j]))
+            if u[j] - z[j] < y[j]:
+                active[j], b[j] = 1, u[j]
+
+    def residuals(xv, yv):
+        zv = A.dot(xv)
+        pri = max(np.max(l - zv), np.max(zv - u), 0.0) if M else 0.0
+        return float(pri), float(np.max(np.abs(P.dot(xv) + q + A.T.dot(yv)))) if n else 0.0
+
+    pri0, dua0 = residuals(x, y)
+    rows = np.where(active != 0)[0]
+    Aa, ba = A[rows], b[rows]
+    out = types.SimpleNamespace(accepted=False, reason=1, n_lower=int(np.sum(active < 0)), n_upper=int(np.sum(active > 0)),
+                                pri_before=pri0, dua_before=dua0, pri_after=np.nan, dua_after=np.nan, obj=np.nan,
+                                x=x.copy(), y=y.copy(), active=active, margin=margin, xh=None, yh=None)
+    S = P + delta * np.eye(n) + Aa.T.dot(Aa) / delta
+    try:
+        L = np.linalg.cholesky(S)
+    except np.linalg.LinAlgError:
+        return out
+
+    def ksolve(r1, r2):
+        dx = np.linalg.solve(L.T, np.linalg.solve(L, r1 + Aa.T.dot(r2) / delta))
+        return dx, (Aa.dot(dx) - r2) / delta
+
+    xh, ya = ksolve(-q, ba)
+    for _ in range(refine_iter):
+        dx, dy = ksolve(-q - P.dot(xh) - Aa.T.dot(ya), ba - Aa.dot(xh))
+        xh, ya = xh + dx, ya + dy
+    yh = np.zeros(M)
+    yh[rows] = ya
+    pri1, dua1 = residuals(xh, yh)
+    out.xh, out.yh, out.pri_after, out.dua_after = xh, yh, pri1, dua1
+    out.obj = float(.5 * np.dot(xh, P.dot(xh)) + np.dot(q, xh))
+    if not pri1 <= max(pri0, 1e-10):
+        out.reason = 2
+    elif not dua1 <= max(dua0, 1e-10):
+        out.reason = 3
+    else:
+        out.reason, out.accepted, out.x, out.y = 0, True, xh.copy(), yh.copy()
+    return out
 
 
 def add_bounds(i_idx, l_new, u_new, A, l, u):
@@ -240,6 +340,7 @@ class Workspace(object):
         self.settings = settings
         self.sb = branching_settings(settings, qp_settings)
         self.rf = heuristic_settings(settings, qp_settings)
+        self.pol = polish_settings(settings)
         self._second = {}  # second relaxation solvers of the host-side restatements, by iteration cap
         self.backend = backend if backend is not None else _default_backend()
         self.constant = self.backend.constant
@@ -289,6 +390,8 @@ class Workspace(object):
         # rf_every-th of them, the first included)
         self.rf_stats = dict(calls=0, candidates=0, feasible=0, improved=0, osqp_iter=0, solve_time=0.)
         self.rf_nodes = 0
+        # polishing of the incumbent (after the search): n_active, pri_after, dua_after are the last call's
+        self.polish_stats = dict(calls=0, accepted=0, n_active=0, pri_after=np.nan, dua_after=np.nan, time=0.)
 
     def _make_root(self):
         return Node(self.data, self.data.l, self.data.u, self.solver, constant=self.constant)
@@ -695,6 +798,41 @@ class Workspace(object):
             ii = self.data.i_idx
             self.x[ii] = np.round(self.x[ii])
 
+    # -- polishing of the incumbent ---------------------------------------------------------------------------
+    def polish_incumbent(self):
+        """After the search (settings['polish_incumbent'] = 1, an incumbent exists): the root with every integer row
+        fixed to the incumbent's rounded value is solved once through the normal node path, warm-started from the
+        incumbent with y = 0, and that solution is polished -- one device call on an engine with `polish`, otherwise
+        polish_restatement.  On acceptance the polished x (its integer entries set to the exact integers) becomes the
+        returned x and upper_glob its objective; status, node count and the search's statistics are not touched."""
+        t0 = time()
+        data, st = self.data, self.polish_stats
+        ii, m = data.i_idx, data.m
+        xi = np.round(self.x[ii])
+        l, u = np.copy(data.l), np.copy(data.u)
+        l[m:] = xi
+        u[m:] = xi
+        x0 = np.array(self.x, dtype=float)
+        x0[ii] = xi
+        node = Node(data, l, u, self.solver, x0=x0, y0=np.zeros(m + data.n_int), constant=self.constant)
+        node.solve()
+        if node.status in self.ok:
+            pol = self.pol
+            if hasattr(self.solver, 'polish'):
+                r = self.solver.polish(l, u, node.x, node.y, pol['delta'], pol['refine_iter'])
+            else:
+                r = polish_restatement(data.P, data.q, data.A, l, u, node.x, node.y, pol['delta'], pol['refine_iter'])
+            st['calls'] += 1
+            st['n_active'] = int(r.n_lower + r.n_upper)
+            st['pri_after'], st['dua_after'] = float(r.pri_after), float(r.dua_after)
+            if r.accepted:
+                x = np.array(r.x, dtype=float)
+                x[ii] = xi
+                self.x = x
+                self.upper_glob = data.compute_obj_val(x)
+                st['accepted'] += 1
+        st['time'] += time() - t0
+
     # -- progress table (workspace.py:386-433) --------------------------------------------
     def print_headline(self):
         print("     Nodes      |           Current Node        |"
@@ -763,6 +901,8 @@ class MIOSQP(object):
         work.osqp_iter_avg = work.osqp_iter / work.iter_num
         work.get_return_status()
         work.get_return_solution()
+        if work.pol['on'] and work.status in (MI_SOLVED, MI_MAX_ITER_FEASIBLE):
+            work.polish_incumbent()
         if verbose:
             work.print_footer()
         work.solve_time = time() - t0
@@ -847,6 +987,7 @@ class MIOSQP(object):
         an unfinished device-hosted search are placeholders and not resumable either way).
         Returns a list of dicts: x, upper_glob, status, nodes, osqp_iter, run_time."""
         work, data, st = self.work, self.work.data, self.work.settings
+        require_plain_search(st, "solve_many", rule=False, heuristic=False)
         B = len(instances)
         if B == 0:
             return []

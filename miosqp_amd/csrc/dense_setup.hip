@@ -325,6 +325,32 @@ done:
   return rc;
 }
 
+// The same blocked LDL^T, inverse and transpose for a matrix that already lies in device memory (the polishing step's
+// reduced system, engine.hip: miosqp_qp_polish).  S: n x ld (+64 doubles), lower triangle valid; on return it holds the
+// strict lower part of L^-1, LinvT (n x ld + 64) its transpose and d the pivots; X (n x ld) and W (n x 64) are scratch.
+// Everything is queued on `stream` and nothing is waited for: a pivot <= 0 sets *flag (device memory, cleared here) and
+// leaves the products undefined -- the caller's own kernels read the flag.
+int miosqp_device_ldl_inverse_resident(int n, int ld, double *S, double *X, double *LinvT, double *W, double *d,
+                                       int *flag, hipStream_t stream) {
+  const size_t mat = (size_t)n * ld * sizeof(double);
+  const int nt = (n + NB - 1) / NB;
+  if (hipMemsetAsync(X, 0, mat, stream) != hipSuccess || hipMemsetAsync(LinvT, 0, mat, stream) != hipSuccess ||
+      hipMemsetAsync(d, 0, (size_t)n * sizeof(double), stream) != hipSuccess ||
+      hipMemsetAsync(flag, 0, sizeof(int), stream) != hipSuccess)
+    return -2;
+  for (int jb = 0; jb < n; jb += NB) {
+    const int w = n - jb < NB ? n - jb : NB, je = jb + w;
+    hipLaunchKernelGGL(ks_diag, dim3(1), dim3(256), 0, stream, S, ld, jb, w, d, flag);
+    if (je >= n) break;
+    const int rt = (n - je + NB - 1) / NB;
+    hipLaunchKernelGGL(ks_panel, dim3(rt), dim3(64), 0, stream, S, ld, n, jb, w, d, W);
+    hipLaunchKernelGGL(ks_update, dim3(rt, rt), dim3(256), 0, stream, S, ld, n, jb, w, W);
+  }
+  for (int I = 0; I < nt; I++) hipLaunchKernelGGL(ks_inv, dim3(I + 1), dim3(256), 0, stream, S, X, ld, n, I);
+  hipLaunchKernelGGL(ks_out, dim3(nt, nt), dim3(256), 0, stream, X, S, LinvT, ld, n);
+  return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
 // ------------------------------------------------------------------------------------------
 // Equilibration on the device (miosqp::RuizOps, factor.hpp): column / row maxima and element-wise products over
 // device-resident copies of P (upper triangle, CSC) and A (CSC).  Maxima of non-negative doubles are taken on their

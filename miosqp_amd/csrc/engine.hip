@@ -49,6 +49,9 @@ void miosqp_device_ruiz_free(void *storage);
 // dense_setup.hip: explicit KKT inverse W = F^T D22^-1 F from the product-form rows (device pointers)
 int miosqp_device_kkt_inverse(const double *F, int ldf, const double *dinv, int n, int M, double *W, int ldw,
                               hipStream_t stream);
+// dense_setup.hip: the same LDL^T + triangular inverse on a matrix that lies in device memory, queued on `stream`
+int miosqp_device_ldl_inverse_resident(int n, int ld, double *S, double *X, double *LinvT, double *W, double *d,
+                                       int *flag, hipStream_t stream);
 
 namespace {
 
@@ -231,6 +234,7 @@ struct CoopNode {
 #include "kernels_pool.inc"  // device-resident leaf pool, streaming batch (refill / harvest between chunks)
 #include "kernels_bstream.inc"  // the streaming batch as ONE persistent launch: iterations, test, harvest and refill per column group (kbs)
 #include "kernels_derived.inc"  // nodes derived from one parent on the device, judged after the batch solve: strong branching, round and fix
+#include "kernels_polish.inc"  // polishing of a node's solution: active set, weighted Schur rows, solves and refinement, acceptance
 #include "host.inc"  // host side: engine object, allocation, launches, graph capture, solve loops
 #include "host_pool.inc"  // host side of the leaf pool (C ABI miosqp_qp_pool_*)
 #include "host_search.inc"  // node-at-a-time branch and bound driven from the host in C++ (C ABI miosqp_qp_search_*)
@@ -250,6 +254,110 @@ hipError_t lds_limit_once(const void *fn, int which) {
   if (dev >= 0 && dev < 64 && done[which][dev]) return hipSuccess;
   rc = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   if (rc == hipSuccess && dev >= 0 && dev < 64) done[which][dev] = true;
+  return rc;
+}
+
+// ---- polishing (miosqp_qp_polish): scratch of one engine, built on the first call ----
+void polish_free(miosqp_qp_engine *e) {
+  PolishScratch *s = e->pol;
+  if (!s) return;
+  for (hipEvent_t ev : s->ev)
+    if (ev) hipEventDestroy(ev);
+  if (s->h) hipHostFree(s->h);
+  if (s->din) hipFree(s->din);
+  if (s->p.S) hipFree(s->p.S);
+  if (s->X) hipFree(s->X);
+  if (s->p.LinvT) hipFree(s->p.LinvT);
+  delete s;
+  e->pol = nullptr;
+}
+
+// The values of A as given at set-up in the layout of the scaled rows the device already holds: the same patterns
+// (pc_* by constraint, pv_* by variable), pads zero.  Both packings keep a column's / a row's entries in ascending order
+// (factor.cpp: pack_rows), which a cursor per row reproduces; every position is checked against the packed index.
+bool polish_raw_rows(const miosqp_qp_engine *e, std::vector<double> &by_con, std::vector<double> &by_var) {
+  const miosqp::PCsr &C = e->fa.panel_by_con, &V = e->fa.panel_by_var;
+  const std::vector<int> &Ap = e->sc.Ap, &Ai = e->sc.Ai;
+  const int n = e->n, M = e->M;
+  if ((int64_t)e->A_raw.size() != (int64_t)Ai.size() || (int)Ap.size() != n + 1) return false;
+  by_con.assign(C.idx.size(), 0.0);
+  by_var.assign(V.idx.size(), 0.0);
+  std::vector<int> cur(M, 0);
+  std::vector<std::pair<int, double>> col;
+  for (int i = 0; i < n; i++) {
+    col.clear();
+    for (int p = Ap[i]; p < Ap[i + 1]; p++) col.push_back({Ai[p], e->A_raw[p]});
+    std::sort(col.begin(), col.end(), [](const std::pair<int, double> &a, const std::pair<int, double> &b) { return a.first < b.first; });
+    if (V.ptr[i] + (int)col.size() > V.ptr[i + 1]) return false;
+    for (size_t k = 0; k < col.size(); k++) {
+      const int r = col[k].first, pv = V.ptr[i] + (int)k;
+      if (r < 0 || r >= M || V.idx[pv] != r) return false;
+      by_var[pv] = col[k].second;
+      const int pc = C.ptr[r] + cur[r]++;
+      if (pc >= C.ptr[r + 1] || C.idx[pc] != i) return false;
+      by_con[pc] = col[k].second;
+    }
+  }
+  return true;
+}
+
+int polish_build(miosqp_qp_engine *e) {
+  const size_t n = e->n, M = e->M, ld = e->d.ld;
+  if (ld * sizeof(double) > 150 * 1024) {
+    g_err = "polish: a row of the reduced system does not fit one workgroup's LDS";
+    return MIOSQP_EUNSUPPORTED;
+  }
+  std::vector<double> by_con, by_var;
+  if (!polish_raw_rows(e, by_con, by_var)) {
+    g_err = "polish: the rows of A on the device do not follow the order of the matrix given at set-up";
+    return MIOSQP_EUNSUPPORTED;
+  }
+  PolishScratch *s = new PolishScratch();
+  e->pol = s;  // (freed by polish_ensure after a failure below, otherwise with the engine)
+  auto al = [](size_t doubles) { return (doubles + 31) & ~(size_t)31; };
+  const size_t nA = al(by_con.size() + 64), nAt = al(by_var.size() + 64), nn = al(n + 64), nM = al(M + 64);
+  const size_t nin = al(3 * M + n), nout = al(POL_REC_DOUBLES + n + M);
+  // one block: A | At | in (l u x y) | w b r2 yh prow0 prow1 (M each) | dd xh r1 t v dx dcol0 dcol1 ocol (n each) |
+  //            W (n x 64) | counters | record + x + y
+  const size_t total = nA + nAt + nin + 6 * nM + 9 * nn + al(n * 64) + 32 + nout;
+  HIPCHK(hipMalloc((void **)&s->din, total * sizeof(double)));
+  HIPCHK(hipMemsetAsync(s->din, 0, total * sizeof(double), e->stream));
+  const size_t mat = n * ld + 64;
+  HIPCHK(hipMalloc((void **)&s->p.S, mat * sizeof(double)));
+  HIPCHK(hipMalloc((void **)&s->X, mat * sizeof(double)));
+  HIPCHK(hipMalloc((void **)&s->p.LinvT, mat * sizeof(double)));
+  HIPCHK(hipMemsetAsync(s->p.S, 0, mat * sizeof(double), e->stream));
+  HIPCHK(hipMemsetAsync(s->X, 0, mat * sizeof(double), e->stream));
+  HIPCHK(hipMemsetAsync(s->p.LinvT, 0, mat * sizeof(double), e->stream));
+  HIPCHK(hipHostMalloc((void **)&s->h, std::max(nin, nout) * sizeof(double), hipHostMallocDefault));
+  for (hipEvent_t &ev : s->ev) HIPCHK(hipEventCreate(&ev));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  Pol &p = s->p;
+  const Dev &d = e->d;
+  double *c = s->din;
+  auto take = [&](size_t doubles) { double *r = c; c += doubles; return r; };
+  double *A = take(nA), *At = take(nAt), *in = take(nin);
+  if (!by_con.empty()) HIPCHK(hipMemcpy(A, by_con.data(), by_con.size() * sizeof(double), hipMemcpyHostToDevice));
+  if (!by_var.empty()) HIPCHK(hipMemcpy(At, by_var.data(), by_var.size() * sizeof(double), hipMemcpyHostToDevice));
+  p.n = (int)n; p.M = (int)M; p.ld = (int)ld;
+  p.pc_ptr = d.pc_ptr; p.pc_idx = d.pc_idx; p.pv_ptr = d.pv_ptr; p.pv_idx = d.pv_idx; p.pr_ptr = d.pr_ptr; p.pr_idx = d.pr_idx;
+  p.A = A; p.At = At; p.pr_val = d.pr_val; p.q = d.qraw;
+  p.l = in; p.u = in + M; p.x = in + 2 * M; p.y = in + 2 * M + n;
+  p.w = take(nM); p.b = take(nM); p.r2 = take(nM); p.yh = take(nM); p.prow0 = take(nM); p.prow1 = take(nM);
+  p.dd = take(nn); p.xh = take(nn); p.r1 = take(nn); p.t = take(nn); p.v = take(nn); p.dx = take(nn);
+  p.dcol0 = take(nn); p.dcol1 = take(nn); p.ocol = take(nn);
+  s->W = take(al(n * 64));
+  p.cnt = (int *)take(32);
+  p.rec = (PolRec *)take(nout);
+  HIPCHK(hipFuncSetAttribute((const void *)k_pol_schur_row, hipFuncAttributeMaxDynamicSharedMemorySize,
+                             (int)(ld * sizeof(double))));
+  return 0;
+}
+
+int polish_ensure(miosqp_qp_engine *e) {
+  if (e->pol) return 0;
+  const int rc = polish_build(e);
+  if (rc) polish_free(e);  // (a half-built scratch is not kept: the next call starts over)
   return rc;
 }
 }  // namespace
@@ -354,6 +462,7 @@ int miosqp_qp_cleanup(miosqp_qp_engine *e) {
   if (e->hb_int) hipHostFree(e->hb_int);
   if (e->hb_dbl) hipHostFree(e->hb_dbl);
   if (e->h_der) hipHostFree(e->h_der);
+  polish_free(e);
   for (int k = 0; k < 16; k++) {
     if (e->xb_full[k]) hipGraphExecDestroy(e->xb_full[k]);
     if (e->xb_tail[k]) hipGraphExecDestroy(e->xb_tail[k]);
@@ -548,6 +657,7 @@ int miosqp_qp_setup(miosqp_qp_engine **out, int32_t n, int32_t M, const int32_t 
   if (actx.dLinvT) e->allocs.push_back(actx.dLinvT);
   tick("host: scaling + factor (total)");
   e->nnzA = Ap[n];
+  e->A_raw.assign(Ax, Ax + Ap[n]);  // polishing works on the unscaled A
   e->nnzPtriu = (int64_t)e->sc.Pi.size();
   const miosqp::Factor &f = e->fa;
   Dev &d = e->d;
@@ -1261,6 +1371,106 @@ int miosqp_qp_round_and_fix(miosqp_qp_engine *e, const double *l, const double *
   info->candidates = K;
   info->iters = (int32_t)iters;
   info->run_time = wall() - t0;
+  return 0;
+}
+
+int miosqp_qp_polish(miosqp_qp_engine *e, const double *l, const double *u, const double *x, const double *y,
+                     double delta, int32_t refine_iter, double *x_out, double *y_out, miosqp_polish_info *info) {
+  if (!e || !l || !u || !x || !y || !x_out || !y_out || !info) return MIOSQP_EARG;
+  ENTER(e);
+  if (!(delta > 0.0) || !(delta < QP_INFTY)) {
+    g_err = "polish: delta must be positive";
+    return MIOSQP_EARG;
+  }
+  if (refine_iter < 0 || refine_iter > 10) {
+    g_err = "polish: refine_iter must be in 0..10";
+    return MIOSQP_EARG;
+  }
+  const size_t n = e->n, M = e->M;
+  for (size_t j = 0; j < M; j++) {
+    if (l[j] > u[j]) return MIOSQP_EBOUNDS;
+    if (l[j] != l[j] || u[j] != u[j] || y[j] != y[j]) {
+      g_err = "polish: NaN in l, u or y (a node without a solution cannot be polished)";
+      return MIOSQP_EARG;
+    }
+  }
+  for (size_t i = 0; i < n; i++)
+    if (x[i] != x[i]) {
+      g_err = "polish: NaN in x (a node without a solution cannot be polished)";
+      return MIOSQP_EARG;
+    }
+  if (int rc = polish_ensure(e)) return rc;
+  const double t0 = wall();
+  PolishScratch *s = e->pol;
+  Pol &p = s->p;
+  p.delta = delta;
+  p.inv_delta = 1.0 / delta;
+  double *h = s->h;
+  memcpy(h, l, sizeof(double) * M);
+  memcpy(h + M, u, sizeof(double) * M);
+  memcpy(h + 2 * M, x, sizeof(double) * n);
+  memcpy(h + 2 * M + n, y, sizeof(double) * M);
+  hipStream_t st = e->stream;
+  const dim3 gM((unsigned)((M + 3) / 4)), gn((unsigned)((n + 3) / 4)), b256(256);
+  HIPCHK(hipEventRecord(s->ev[0], st));
+  HIPCHK(hipMemcpyAsync((void *)p.l, h, sizeof(double) * (3 * M + n), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemsetAsync(p.cnt, 0, 4 * sizeof(int), st));
+  HIPCHK(hipMemsetAsync(p.xh, 0, sizeof(double) * n, st));
+  if (M) {
+    HIPCHK(hipMemsetAsync(p.yh, 0, sizeof(double) * M, st));
+    hipLaunchKernelGGL(k_pol_classify, gM, b256, 0, st, p);
+  }
+  HIPCHK(hipEventRecord(s->ev[1], st));
+  hipLaunchKernelGGL(k_pol_schur_row, dim3((unsigned)n), b256, p.ld * sizeof(double), st, p);
+  HIPCHK(hipEventRecord(s->ev[2], st));
+  if (miosqp_device_ldl_inverse_resident((int)n, p.ld, p.S, s->X, p.LinvT, s->W, p.dd, p.cnt + 2, st)) {
+    g_err = "polish: the factorisation of the reduced system could not be queued";
+    return MIOSQP_EHIP;
+  }
+  HIPCHK(hipEventRecord(s->ev[3], st));
+  // (xh, yh) = ksolve(-q, b), then refine_iter corrections by the residuals of the unregularised system: with
+  // xh = yh = 0 the first pass's residuals are exactly (-q, b)
+  for (int it = 0; it <= refine_iter; it++) {
+    if (M) hipLaunchKernelGGL(k_pol_r2, gM, b256, 0, st, p);
+    hipLaunchKernelGGL(k_pol_rhs, gn, b256, 0, st, p);
+    hipLaunchKernelGGL(k_pol_lower, gn, b256, 0, st, p);
+    hipLaunchKernelGGL(k_pol_upper, gn, b256, 0, st, p);
+    if (M) hipLaunchKernelGGL(k_pol_dy, gM, b256, 0, st, p);
+  }
+  if (M) hipLaunchKernelGGL(k_pol_rows_after, gM, b256, 0, st, p);
+  hipLaunchKernelGGL(k_pol_cols, gn, b256, 0, st, p);
+  hipLaunchKernelGGL(k_pol_decide, dim3(1), b256, 0, st, p);
+  HIPCHK(hipEventRecord(s->ev[4], st));
+  HIPCHK(hipMemcpyAsync(h, p.rec, sizeof(double) * (POL_REC_DOUBLES + n + M), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipEventRecord(s->ev[5], st));
+  HIPCHK(hipStreamSynchronize(st));
+  HIPCHK(hipGetLastError());
+  float ms = 0;
+  for (int k = 0; k < 4; k++) {
+    HIPCHK(hipEventElapsedTime(&ms, s->ev[k], s->ev[k + 1]));
+    s->stage_s[k] = 1e-3 * ms;
+  }
+  HIPCHK(hipEventElapsedTime(&ms, s->ev[0], s->ev[5]));
+  const PolRec &r = *(const PolRec *)h;
+  info->accepted = r.accepted;
+  info->reason = r.reason;
+  info->n_lower = r.n_lower;
+  info->n_upper = r.n_upper;
+  info->pri_before = r.pri_before;
+  info->dua_before = r.dua_before;
+  info->pri_after = r.pri_after;
+  info->dua_after = r.dua_after;
+  info->obj = r.obj;
+  memcpy(x_out, h + POL_REC_DOUBLES, sizeof(double) * n);
+  memcpy(y_out, h + POL_REC_DOUBLES + n, sizeof(double) * M);
+  info->device_time = 1e-3 * ms;
+  info->run_time = wall() - t0;
+  return 0;
+}
+
+int miosqp_qp_get_polish_stages(miosqp_qp_engine *e, double *seconds) {
+  if (!e || !seconds) return MIOSQP_EARG;
+  for (int k = 0; k < 4; k++) seconds[k] = e->pol ? e->pol->stage_s[k] : 0.0;
   return 0;
 }
 

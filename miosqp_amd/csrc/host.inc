@@ -176,6 +176,10 @@ struct miosqp_qp_engine {
   // doubles) and strong branching's 32 candidate positions (int32, 16 doubles' room) staged in, the feature's record
   // out (round and fix: the winner's x behind it); device in / device record / ONE pinned block for both directions
   double *der_in = nullptr, *der_rec = nullptr, *h_der = nullptr;
+  // polishing (miosqp_qp_polish): the values of A as they were given at set-up (the device holds the scaled copy), and
+  // the scratch of the reduced system, built on the first call and freed with the engine
+  std::vector<double> A_raw;
+  PolishScratch *pol = nullptr;
   hipGraphExec_t xb_full[16] = {}, xb_tail[16] = {};
   hipGraph_t gb_full[16] = {}, gb_tail[16] = {};
   bool compact = true;   // compaction of converged columns in solve_batch (MIOSQP_COMPACT=0 disables)

@@ -265,6 +265,32 @@ class OSQP(object):
                                      iter=iters[:K], obj=obj[:K], viol=viol[:K], feasible=info.feasible,
                                      iters=info.iters, device_time=info.device_time, run_time=info.run_time)
 
+    def polish(self, l, u, x, y, delta=1e-6, refine_iter=3):
+        """Polishing of one node's solution (bounds l, u; approximate x, y) on the device (miosqp_qp_polish): the active
+        set guessed from (x, y), the regularised KKT system on it solved through a dense factorisation of the reduced
+        matrix and refined `refine_iter` times.  Returns the record (accepted, reason 0 ok / 1 factorisation / 2 primal
+        / 3 dual, n_lower, n_upper, pri / dua before and after, obj of the polished point, device_time, run_time) plus
+        x, y: the polished point when accepted, the input otherwise.  The QP setting `polish` stays ignored: this is a
+        call of its own."""
+        l, u = _f64(l, self.m, "l"), _f64(u, self.m, "u")
+        x, y = _f64(x, self.n, "x"), _f64(y, self.m, "y")
+        xo, yo, info = np.empty(self.n), np.empty(self.m), _lib.PolishInfo()
+        rc = _check(self._lib.miosqp_qp_polish(self._h, _lib.as_d(l), _lib.as_d(u), _lib.as_d(x), _lib.as_d(y),
+                                               float(delta), int(refine_iter), _lib.as_d(xo), _lib.as_d(yo),
+                                               C.byref(info)), "polish")
+        if rc == 1:
+            raise ValueError("Lower bound must be lower than or equal to upper bound")
+        return types.SimpleNamespace(x=xo, y=yo, accepted=bool(info.accepted), reason=info.reason, n_lower=info.n_lower,
+                                     n_upper=info.n_upper, pri_before=info.pri_before, dua_before=info.dua_before,
+                                     pri_after=info.pri_after, dua_after=info.dua_after, obj=info.obj,
+                                     device_time=info.device_time, run_time=info.run_time)
+
+    def polish_stages(self):
+        """Device seconds of the last polish call: classification, rows of the reduced matrix, factorisation, solves."""
+        out = np.zeros(4)
+        _check(self._lib.miosqp_qp_get_polish_stages(self._h, _lib.as_d(out)), "get_polish_stages")
+        return tuple(float(v) for v in out)
+
     def solve_tree(self, l, u, x0, y0, upper0, x_inc0, tree_explor_rule, max_iter_bb):
         """A whole tree search in one launch (small problems); None when the engine does not cover this size."""
         l, u = _f64(l, self.m, "l"), _f64(u, self.m, "u")

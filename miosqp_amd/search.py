@@ -33,7 +33,7 @@ class HostedSearch(object):
             raise RuntimeError("the engine has no hosted search (miosqp_qp_search_*)")
         if w.settings['branching_rule'] != 0 or w.settings['tree_explor_rule'] not in (0, 1):
             raise ValueError("hosted search: branching_rule 0 and tree_explor_rule 0 / 1 only")
-        bnb.require_plain_search(w.settings, "hosted search", rule=False)
+        bnb.require_plain_search(w.settings, "hosted search", rule=False, polish=not owned)  # (MIOSQP.solve polishes after its own)
         self.p = w.data.n_int
         if capacity is None:
             slot = 8 * (w.data.n + w.data.m + 3 * self.p)
