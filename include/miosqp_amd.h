@@ -261,6 +261,43 @@ int miosqp_qp_polish(miosqp_qp_engine *e, const double *l, const double *u, cons
  * solves + refinement + acceptance (zeros before the first call).  No counterpart in OSQP, which reports one polish_time. */
 int miosqp_qp_get_polish_stages(miosqp_qp_engine *e, double *seconds);
 
+/* ---- polishing with a repair loop around the active set ---------------------------------------------------------
+ * OSQP's polish (polish.c of OSQP 0.6.x) guesses the active set once and gives the point up when the guess was wrong.
+ * This entry extends it: OSQP has NO such loop.  Round 0 is miosqp_qp_polish unchanged (steps 1-3 above).  After the
+ * solves of round k, with (xh, yh) the point just computed, z = A xh and tol = 1e-10 (the floor of the acceptance
+ * test), every row is revised:
+ *   - an equality row (l == u) stays active;
+ *   - a lower-active row with yh > tol becomes inactive; an upper-active row with yh < -tol becomes inactive;
+ *   - an inactive row with finite l and l - z > tol becomes lower-active, otherwise an inactive row with finite u and
+ *     z - u > tol becomes upper-active; bounds at or beyond +-1e30 are never active;
+ *   - a row dropped in a revision is not added again in the same revision.
+ * changed = added + dropped.  changed == 0: stop 0, the set is a fixed point and the point is the node's KKT point up
+ * to tol.  changed > 0 and k == repair_iter: stop 1.  Otherwise round k + 1 runs on the revised set: S rebuilt from
+ * scratch, the LDL^T again, xh = yh = 0, 1 + refine_iter solves -- identical sets give identical bits whatever path led
+ * to them.  A pivot <= 0 in a round k + 1 >= 1: stop 2, and the point and the set of round k are the ones judged.
+ * Step 4 runs once more on the point the loop ended with: accepted when round 0 had no bad pivot,
+ * pri_after <= max(pri_before, 1e-10) and dua_after <= max(dua_before, 1e-10); reasons 0-3 as above.  The host decides
+ * once per round, on four counters of the revision.  With repair_iter 0 the answer is miosqp_qp_polish's bit for bit,
+ * plus `stop` from one revision.  After reason 1 in round 0 nothing is revised (rounds 0, stop 0).
+ * Errors: those of miosqp_qp_polish; MIOSQP_EARG also for repair_iter outside 0..20. */
+typedef struct miosqp_polish_repair_info {
+  miosqp_polish_info polish;   /* of the point the loop ended with; n_lower / n_upper of the final set */
+  int32_t rounds;              /* repair rounds run (0 .. repair_iter), one that stopped on a bad pivot included */
+  int32_t stop;                /* 0 fixed point, 1 round limit, 2 bad pivot in a repair round */
+  int32_t n_added, n_dropped;  /* summed over the revisions */
+  int32_t accepted0, reason0;  /* what round 0 alone would have answered */
+} miosqp_polish_repair_info;
+
+int miosqp_qp_polish_repair(miosqp_qp_engine *e, const double *l, const double *u, const double *x, const double *y,
+                            double delta, int32_t refine_iter, int32_t repair_iter, double *x_out, double *y_out,
+                            miosqp_polish_repair_info *info);
+
+/* of the last miosqp_qp_polish_repair call: cls (M) the class of every row in the final set (-1 lower-active, 1
+ * upper-active, 0 inactive); round_seconds (21) the device seconds of round 0, 1, .. up to the revision's counters;
+ * wait_seconds (21) the host's wait for them.  Entries of rounds not run are zero; any pointer may be NULL.
+ * (miosqp_qp_get_polish_stages reports round 0's stages after such a call.) */
+int miosqp_qp_get_polish_repair_trace(miosqp_qp_engine *e, int8_t *cls, double *round_seconds, double *wait_seconds);
+
 /* ---- a whole tree search in one launch (small problems) ------------------------------------------------
  * the MPC re-solve path (/root/reference/miosqp/solver.py:65-172 per MIQP,
  * examples/power_converter/power_converter.py:421-508 per sampling step).  For problems the LDS-resident solver

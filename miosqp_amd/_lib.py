@@ -64,6 +64,11 @@ class PolishInfo(C.Structure):
                 ("dua_after", C.c_double), ("obj", C.c_double), ("device_time", C.c_double), ("run_time", C.c_double)]
 
 
+class PolishRepairInfo(C.Structure):
+    _fields_ = [("polish", PolishInfo), ("rounds", C.c_int32), ("stop", C.c_int32), ("n_added", C.c_int32),
+                ("n_dropped", C.c_int32), ("accepted0", C.c_int32), ("reason0", C.c_int32)]
+
+
 class PoolDigest(C.Structure):
     _fields_ = [("slot", C.c_int32), ("status_val", C.c_int32), ("iter", C.c_int32), ("int_inf", C.c_int32),
                 ("nextvar", C.c_int32), ("reserved", C.c_int32), ("lower", C.c_double), ("heur_viol", C.c_double),
@@ -89,6 +94,9 @@ SYMBOLS = {
                                           C.POINTER(RfInfo)]),
     "miosqp_qp_polish": (C.c_int, [C.c_void_p, dp, dp, dp, dp, C.c_double, C.c_int32, dp, dp, C.POINTER(PolishInfo)]),
     "miosqp_qp_get_polish_stages": (C.c_int, [C.c_void_p, dp]),
+    "miosqp_qp_polish_repair": (C.c_int, [C.c_void_p, dp, dp, dp, dp, C.c_double, C.c_int32, C.c_int32, dp, dp,
+                                          C.POINTER(PolishRepairInfo)]),
+    "miosqp_qp_get_polish_repair_trace": (C.c_int, [C.c_void_p, C.POINTER(C.c_int8), dp, dp]),
     "miosqp_qp_solve_trees": (C.c_int, [C.c_void_p, C.c_int32, dp, dp, dp, dp, dp, dp, dp, C.c_int32, C.c_int32, dp,
                                         C.POINTER(TreeInfo)]),
     "miosqp_qp_search_create": (C.c_int, [C.c_void_p, C.c_int32]),

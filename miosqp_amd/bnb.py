@@ -97,7 +97,9 @@ def heuristic_settings(settings, qp_settings):
 def polish_settings(settings):
     """Polishing of the incumbent and its parameters, checked (MIOSQP.setup calls this before anything is built).
     polish_incumbent 0: the incumbent as the search found it; 1: re-solved with its integers fixed and polished
-    (Workspace.polish_incumbent)."""
+    (Workspace.polish_incumbent).  polish_repair_iter is checked here with its neighbours and read by
+    polish_repair_setting: this record keeps its three keys."""
+    polish_repair_setting(settings)
     on = settings.get('polish_incumbent', 0)
     if on not in (0, 1):
         raise ValueError('polish_incumbent must be 0 or 1')
@@ -110,6 +112,16 @@ def polish_settings(settings):
             or not 0 <= it <= 10:
         raise ValueError('polish_refine_iter must be an integer in 0..10')
     return dict(on=int(on), delta=float(delta), refine_iter=int(it))
+
+
+def polish_repair_setting(settings):
+    """polish_repair_iter, checked: the most repair rounds of the polish's active set (0, the default: the set guessed
+    once, as OSQP polishes; up to 20)."""
+    it = settings.get('polish_repair_iter', 0)
+    if isinstance(it, bool) or not isinstance(it, (int, float, np.integer, np.floating)) or not 0 <= it <= 20 \
+            or int(it) != it:
+        raise ValueError('polish_repair_iter must be an integer in 0..20')
+    return int(it)
 
 
 def require_plain_search(settings, who, rule=True, heuristic=True, polish=True):
@@ -152,9 +164,10 @@ def sb_scores(lower, status, parent_lower, eps, ok):
 POLISH_INFTY = 1e30  # a bound at or beyond it is infinite (the engine's constant)
 
 
-def polish_restatement(P, q, A, l, u, x, y, delta=1e-6, refine_iter=3):
+def polish_restatement(P, q, A, l, u, x, y, delta=1e-6, refine_iter=3, repair_iter=None):
     """Polishing of one node's solution in dense numpy: what `OSQP.polish` of the HIP engine computes on the device
-    (include/miosqp_amd.h: miosqp_qp_polish), used where the backend has none.  A, l, u: all M rows; everything unscaled.
+    (include/miosqp_amd.h: miosqp_qp_polish, miosqp_qp_polish_repair), used where the backend has none.  A, l, u: all M
+    rows; everything unscaled.
 
     1. z = A x; row j is lower-active when l_j == u_j or z_j - l_j < -y_j, otherwise upper-active when u_j - z_j < y_j;
        an infinite bound is never active.
@@ -164,15 +177,28 @@ def polish_restatement(P, q, A, l, u, x, y, delta=1e-6, refine_iter=3):
     4. accepted when S was positive definite, pri_after <= max(pri_before, 1e-10), dua_after <= max(dua_before, 1e-10)
        (pri, dua over all rows); otherwise x, y are the input and reason says why (1 factorisation, 2 primal, 3 dual).
 
+    repair_iter None: exactly the above.  An integer 0..20 adds the repair loop (OSQP has none): steps 1-3 are round 0;
+    after the solves of round k every row is revised from (xh, yh), z = A xh, tol = 1e-10 -- an equality row stays; a
+    lower-active row with yh > tol and an upper-active row with yh < -tol become inactive; an inactive row with finite
+    l and l - z > tol becomes lower-active, otherwise with finite u and z - u > tol upper-active.  No change: stop 0 (a
+    fixed point).  A change at k == repair_iter: stop 1.  Otherwise round k + 1 repeats steps 2-3 on the revised set
+    from xh = yh = 0; a factorisation that fails there ends the loop with stop 2 and round k's point and set.  Step 4
+    judges the point the loop ended with (reason 1 only for round 0's factorisation).  The record gains rounds (repair
+    rounds run), stop, n_added, n_dropped (summed over the revisions), accepted0, reason0 (step 4 on round 0's point);
+    n_lower, n_upper, active, xh, yh are those of the final set and point.
+
     Besides the record: active (per row -1 lower, 1 upper, 0 inactive), margin (per row the smallest distance from
-    equality of the comparisons that classified it; inf for equality rows and rows without a finite bound: an input
-    with a tiny margin sits on a tie and another summation order may classify it differently), xh, yh (the polished
-    point whether accepted or not; None after reason 1)."""
+    equality of the comparisons that classified it, the revisions' |quantity - tol| included; inf for equality rows
+    and rows without a finite bound: an input with a tiny margin sits on a tie and another summation order may
+    classify it differently), xh, yh (the polished point whether accepted or not; None after reason 1)."""
     P = np.asarray(P.todense()) if spa.issparse(P) else np.asarray(P, dtype=float)
     A = np.asarray(A.todense()) if spa.issparse(A) else np.asarray(A, dtype=float)
     q, l, u = np.asarray(q, dtype=float), np.asarray(l, dtype=float), np.asarray(u, dtype=float)
     x, y = np.asarray(x, dtype=float), np.asarray(y, dtype=float)
     M, n = A.shape
+    if repair_iter is not None and (isinstance(repair_iter, bool) or int(repair_iter) != repair_iter
+                                    or not 0 <= repair_iter <= 20):
+        raise ValueError('repair_iter must be an integer in 0..20')
     z = A.dot(x)
     active, margin, b = np.zeros(M, dtype=np.int64), np.full(M, np.inf), np.zeros(M)
     for j in range(M):
@@ -195,37 +221,100 @@ def polish_restatement(P, q, A, l, u, x, y, delta=1e-6, refine_iter=3):
         pri = max(np.max(l - zv), np.max(zv - u), 0.0) if M else 0.0
         return float(pri), float(np.max(np.abs(P.dot(xv) + q + A.T.dot(yv)))) if n else 0.0
 
+    def solve_on(active, b):
+        """steps 2 and 3 on one set: (xh, yh), or None when S is not positive definite"""
+        rows = np.where(active != 0)[0]
+        Aa, ba = A[rows], b[rows]
+        S = P + delta * np.eye(n) + Aa.T.dot(Aa) / delta
+        try:
+            L = np.linalg.cholesky(S)
+        except np.linalg.LinAlgError:
+            return None
+
+        def ksolve(r1, r2):
+            dx = np.linalg.solve(L.T, np.linalg.solve(L, r1 + Aa.T.dot(r2) / delta))
+            return dx, (Aa.dot(dx) - r2) / delta
+
+        xh, ya = ksolve(-q, ba)
+        for _ in range(refine_iter):
+            dx, dy = ksolve(-q - P.dot(xh) - Aa.T.dot(ya), ba - Aa.dot(xh))
+            xh, ya = xh + dx, ya + dy
+        yh = np.zeros(M)
+        yh[rows] = ya
+        return xh, yh
+
+    def revise(active, b, xh, yh):
+        """the revised set from (xh, yh): (active, b, added, dropped); margin takes the comparisons made"""
+        tol = 1e-10
+        zh = A.dot(xh)
+        act, bb, added, dropped = active.copy(), b.copy(), 0, 0
+        for j in range(M):
+            if l[j] == u[j]:
+                continue
+            if active[j] < 0:
+                margin[j] = min(margin[j], abs(yh[j] - tol))
+                if yh[j] > tol:
+                    act[j], bb[j], dropped = 0, 0.0, dropped + 1
+            elif active[j] > 0:
+                margin[j] = min(margin[j], abs(-yh[j] - tol))
+                if yh[j] < -tol:
+                    act[j], bb[j], dropped = 0, 0.0, dropped + 1
+            else:
+                if l[j] > -POLISH_INFTY:
+                    margin[j] = min(margin[j], abs((l[j] - zh[j]) - tol))
+                    if l[j] - zh[j] > tol:
+                        act[j], bb[j], added = -1, l[j], added + 1
+                        continue
+                if u[j] < POLISH_INFTY:
+                    margin[j] = min(margin[j], abs((zh[j] - u[j]) - tol))
+                    if zh[j] - u[j] > tol:
+                        act[j], bb[j], added = 1, u[j], added + 1
+        return act, bb, added, dropped
+
+    def judge(xh, yh):
+        pri1, dua1 = residuals(xh, yh)
+        if not pri1 <= max(pri0, 1e-10):
+            return 2, pri1, dua1
+        if not dua1 <= max(dua0, 1e-10):
+            return 3, pri1, dua1
+        return 0, pri1, dua1
+
     pri0, dua0 = residuals(x, y)
-    rows = np.where(active != 0)[0]
-    Aa, ba = A[rows], b[rows]
     out = types.SimpleNamespace(accepted=False, reason=1, n_lower=int(np.sum(active < 0)), n_upper=int(np.sum(active > 0)),
                                 pri_before=pri0, dua_before=dua0, pri_after=np.nan, dua_after=np.nan, obj=np.nan,
                                 x=x.copy(), y=y.copy(), active=active, margin=margin, xh=None, yh=None)
-    S = P + delta * np.eye(n) + Aa.T.dot(Aa) / delta
-    try:
-        L = np.linalg.cholesky(S)
-    except np.linalg.LinAlgError:
+    if repair_iter is not None:
+        out.rounds, out.stop, out.n_added, out.n_dropped, out.accepted0, out.reason0 = 0, 0, 0, 0, False, 1
+    point = solve_on(active, b)
+    if point is None:
         return out
-
-    def ksolve(r1, r2):
-        dx = np.linalg.solve(L.T, np.linalg.solve(L, r1 + Aa.T.dot(r2) / delta))
-        return dx, (Aa.dot(dx) - r2) / delta
-
-    xh, ya = ksolve(-q, ba)
-    for _ in range(refine_iter):
-        dx, dy = ksolve(-q - P.dot(xh) - Aa.T.dot(ya), ba - Aa.dot(xh))
-        xh, ya = xh + dx, ya + dy
-    yh = np.zeros(M)
-    yh[rows] = ya
-    pri1, dua1 = residuals(xh, yh)
-    out.xh, out.yh, out.pri_after, out.dua_after = xh, yh, pri1, dua1
+    xh, yh = point
+    if repair_iter is not None:
+        out.reason0 = judge(xh, yh)[0]
+        out.accepted0 = out.reason0 == 0
+        k = 0
+        while True:
+            act, bb, added, dropped = revise(active, b, xh, yh)
+            out.n_added, out.n_dropped = out.n_added + added, out.n_dropped + dropped
+            if added + dropped == 0:
+                out.stop = 0
+                break
+            if k == repair_iter:
+                out.stop = 1
+                break
+            k += 1
+            out.rounds = k
+            point = solve_on(act, bb)
+            if point is None:
+                out.stop = 2
+                break
+            (xh, yh), active, b = point, act, bb
+        out.active, out.n_lower, out.n_upper = active, int(np.sum(active < 0)), int(np.sum(active > 0))
+    out.reason, out.pri_after, out.dua_after = judge(xh, yh)
+    out.xh, out.yh = xh, yh
     out.obj = float(.5 * np.dot(xh, P.dot(xh)) + np.dot(q, xh))
-    if not pri1 <= max(pri0, 1e-10):
-        out.reason = 2
-    elif not dua1 <= max(dua0, 1e-10):
-        out.reason = 3
-    else:
-        out.reason, out.accepted, out.x, out.y = 0, True, xh.copy(), yh.copy()
+    if out.reason == 0:
+        out.accepted, out.x, out.y = True, xh.copy(), yh.copy()
     return out
 
 
@@ -341,6 +430,7 @@ class Workspace(object):
         self.sb = branching_settings(settings, qp_settings)
         self.rf = heuristic_settings(settings, qp_settings)
         self.pol = polish_settings(settings)
+        self.pol_repair_iter = polish_repair_setting(settings)
         self._second = {}  # second relaxation solvers of the host-side restatements, by iteration cap
         self.backend = backend if backend is not None else _default_backend()
         self.constant = self.backend.constant
@@ -392,6 +482,8 @@ class Workspace(object):
         self.rf_nodes = 0
         # polishing of the incumbent (after the search): n_active, pri_after, dua_after are the last call's
         self.polish_stats = dict(calls=0, accepted=0, n_active=0, pri_after=np.nan, dua_after=np.nan, time=0.)
+        # the repair loop of the polish (polish_repair_iter > 0): sums over the calls; fixed_points counts stop 0
+        self.polish_repair_stats = dict(calls=0, rounds=0, added=0, dropped=0, fixed_points=0)
 
     def _make_root(self):
         return Node(self.data, self.data.l, self.data.u, self.solver, constant=self.constant)
@@ -803,8 +895,10 @@ class Workspace(object):
         """After the search (settings['polish_incumbent'] = 1, an incumbent exists): the root with every integer row
         fixed to the incumbent's rounded value is solved once through the normal node path, warm-started from the
         incumbent with y = 0, and that solution is polished -- one device call on an engine with `polish`, otherwise
-        polish_restatement.  On acceptance the polished x (its integer entries set to the exact integers) becomes the
-        returned x and upper_glob its objective; status, node count and the search's statistics are not touched."""
+        polish_restatement; with polish_repair_iter > 0 both run the repair loop of the active set and
+        polish_repair_stats counts its rounds.  On acceptance the polished x (its integer entries set to the exact
+        integers) becomes the returned x and upper_glob its objective; status, node count and the search's statistics
+        are not touched."""
         t0 = time()
         data, st = self.data, self.polish_stats
         ii, m = data.i_idx, data.m
@@ -818,10 +912,19 @@ class Workspace(object):
         node.solve()
         if node.status in self.ok:
             pol = self.pol
+            rep = dict(repair_iter=self.pol_repair_iter) if self.pol_repair_iter > 0 else {}
             if hasattr(self.solver, 'polish'):
-                r = self.solver.polish(l, u, node.x, node.y, pol['delta'], pol['refine_iter'])
+                r = self.solver.polish(l, u, node.x, node.y, pol['delta'], pol['refine_iter'], **rep)
             else:
-                r = polish_restatement(data.P, data.q, data.A, l, u, node.x, node.y, pol['delta'], pol['refine_iter'])
+                r = polish_restatement(data.P, data.q, data.A, l, u, node.x, node.y, pol['delta'], pol['refine_iter'],
+                                       **rep)
+            if rep:
+                rs = self.polish_repair_stats
+                rs['calls'] += 1
+                rs['rounds'] += int(r.rounds)
+                rs['added'] += int(r.n_added)
+                rs['dropped'] += int(r.n_dropped)
+                rs['fixed_points'] += int(r.stop == 0)
             st['calls'] += 1
             st['n_active'] = int(r.n_lower + r.n_upper)
             st['pri_after'], st['dua_after'] = float(r.pri_after), float(r.dua_after)

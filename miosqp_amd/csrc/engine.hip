@@ -263,6 +263,8 @@ void polish_free(miosqp_qp_engine *e) {
   if (!s) return;
   for (hipEvent_t ev : s->ev)
     if (ev) hipEventDestroy(ev);
+  for (hipEvent_t ev : s->evr)
+    if (ev) hipEventDestroy(ev);
   if (s->h) hipHostFree(s->h);
   if (s->din) hipFree(s->din);
   if (s->p.S) hipFree(s->p.S);
@@ -317,9 +319,11 @@ int polish_build(miosqp_qp_engine *e) {
   auto al = [](size_t doubles) { return (doubles + 31) & ~(size_t)31; };
   const size_t nA = al(by_con.size() + 64), nAt = al(by_var.size() + 64), nn = al(n + 64), nM = al(M + 64);
   const size_t nin = al(3 * M + n), nout = al(POL_REC_DOUBLES + n + M);
+  const size_t ncls = al(M / 8 + 8);  // a class array: one byte per row
   // one block: A | At | in (l u x y) | w b r2 yh prow0 prow1 (M each) | dd xh r1 t v dx dcol0 dcol1 ocol (n each) |
-  //            W (n x 64) | counters | record + x + y
-  const size_t total = nA + nAt + nin + 6 * nM + 9 * nn + al(n * 64) + 32 + nout;
+  //            W (n x 64) | counters | record + x + y | the repair loop's: kept x (n), kept y (M), two class arrays,
+  //            second record + x + y
+  const size_t total = nA + nAt + nin + 6 * nM + 9 * nn + al(n * 64) + 32 + nout + nn + nM + 2 * ncls + nout;
   HIPCHK(hipMalloc((void **)&s->din, total * sizeof(double)));
   HIPCHK(hipMemsetAsync(s->din, 0, total * sizeof(double), e->stream));
   const size_t mat = n * ld + 64;
@@ -329,8 +333,14 @@ int polish_build(miosqp_qp_engine *e) {
   HIPCHK(hipMemsetAsync(s->p.S, 0, mat * sizeof(double), e->stream));
   HIPCHK(hipMemsetAsync(s->X, 0, mat * sizeof(double), e->stream));
   HIPCHK(hipMemsetAsync(s->p.LinvT, 0, mat * sizeof(double), e->stream));
-  HIPCHK(hipHostMalloc((void **)&s->h, std::max(nin, nout) * sizeof(double), hipHostMallocDefault));
+  // pinned: in (l u x y) on the way down, on the way up the final record + x + y and round 0's record; behind both the
+  // final classes (they outlive the next call's inputs) and the counters of a round
+  const size_t nh = std::max(nin, nout + al(POL_REC_DOUBLES));
+  HIPCHK(hipHostMalloc((void **)&s->h, (nh + ncls + 8) * sizeof(double), hipHostMallocDefault));
+  s->hcls = (signed char *)(s->h + nh);
+  s->hcnt = (int *)(s->h + nh + ncls);
   for (hipEvent_t &ev : s->ev) HIPCHK(hipEventCreate(&ev));
+  for (hipEvent_t &ev : s->evr) HIPCHK(hipEventCreate(&ev));
   HIPCHK(hipStreamSynchronize(e->stream));
   Pol &p = s->p;
   const Dev &d = e->d;
@@ -349,6 +359,13 @@ int polish_build(miosqp_qp_engine *e) {
   s->W = take(al(n * 64));
   p.cnt = (int *)take(32);
   p.rec = (PolRec *)take(nout);
+  s->xk = take(nn);
+  s->yk = take(nM);
+  s->cls_buf[0] = (signed char *)take(ncls);
+  s->cls_buf[1] = (signed char *)take(ncls);
+  p.cls = s->cls_buf[0];
+  p.cls_next = s->cls_buf[1];
+  s->rec2 = (PolRec *)take(nout);
   HIPCHK(hipFuncSetAttribute((const void *)k_pol_schur_row, hipFuncAttributeMaxDynamicSharedMemorySize,
                              (int)(ld * sizeof(double))));
   return 0;
@@ -359,6 +376,121 @@ int polish_ensure(miosqp_qp_engine *e) {
   const int rc = polish_build(e);
   if (rc) polish_free(e);  // (a half-built scratch is not kept: the next call starts over)
   return rc;
+}
+
+// What both polish entries do first: the argument checks, the scratch, the inputs into the pinned block.  *t0: the wall
+// clock once the scratch exists (run_time leaves the one-time allocation out).
+int polish_begin(miosqp_qp_engine *e, const double *l, const double *u, const double *x, const double *y, double delta,
+                 int32_t refine_iter, int32_t repair_iter, double *t0) {
+  ENTER(e);
+  if (!(delta > 0.0) || !(delta < QP_INFTY)) {
+    g_err = "polish: delta must be positive";
+    return MIOSQP_EARG;
+  }
+  if (refine_iter < 0 || refine_iter > 10) {
+    g_err = "polish: refine_iter must be in 0..10";
+    return MIOSQP_EARG;
+  }
+  if (repair_iter < 0 || repair_iter >= POL_MAX_ROUNDS) {
+    g_err = "polish: repair_iter must be in 0..20";
+    return MIOSQP_EARG;
+  }
+  const size_t n = e->n, M = e->M;
+  for (size_t j = 0; j < M; j++) {
+    if (l[j] > u[j]) return MIOSQP_EBOUNDS;
+    if (l[j] != l[j] || u[j] != u[j] || y[j] != y[j]) {
+      g_err = "polish: NaN in l, u or y (a node without a solution cannot be polished)";
+      return MIOSQP_EARG;
+    }
+  }
+  for (size_t i = 0; i < n; i++)
+    if (x[i] != x[i]) {
+      g_err = "polish: NaN in x (a node without a solution cannot be polished)";
+      return MIOSQP_EARG;
+    }
+  if (int rc = polish_ensure(e)) return rc;
+  *t0 = wall();
+  PolishScratch *s = e->pol;
+  Pol &p = s->p;
+  p.delta = delta;
+  p.inv_delta = 1.0 / delta;
+  p.cls = s->cls_buf[0];
+  p.cls_next = s->cls_buf[1];
+  double *h = s->h;
+  memcpy(h, l, sizeof(double) * M);
+  memcpy(h + M, u, sizeof(double) * M);
+  memcpy(h + 2 * M, x, sizeof(double) * n);
+  memcpy(h + 2 * M + n, y, sizeof(double) * M);
+  return 0;
+}
+
+// S of the set in p.w, its LDL^T, then (xh, yh) = ksolve(-q, b) and refine_iter corrections by the residuals of the
+// unregularised system: with xh = yh = 0 the first pass's residuals are exactly (-q, b).  ev2 / ev3, when given, are
+// recorded behind the rows of S and behind the factorisation.
+int polish_queue_solve(miosqp_qp_engine *e, const Pol &p, int refine_iter, hipEvent_t ev2, hipEvent_t ev3) {
+  PolishScratch *s = e->pol;
+  hipStream_t st = e->stream;
+  const size_t n = e->n, M = e->M;
+  const dim3 gM((unsigned)((M + 3) / 4)), gn((unsigned)((n + 3) / 4)), b256(256);
+  hipLaunchKernelGGL(k_pol_schur_row, dim3((unsigned)n), b256, p.ld * sizeof(double), st, p);
+  if (ev2) HIPCHK(hipEventRecord(ev2, st));
+  if (miosqp_device_ldl_inverse_resident((int)n, p.ld, p.S, s->X, p.LinvT, s->W, p.dd, p.cnt + 2, st)) {
+    g_err = "polish: the factorisation of the reduced system could not be queued";
+    return MIOSQP_EHIP;
+  }
+  if (ev3) HIPCHK(hipEventRecord(ev3, st));
+  for (int it = 0; it <= refine_iter; it++) {
+    if (M) hipLaunchKernelGGL(k_pol_r2, gM, b256, 0, st, p);
+    hipLaunchKernelGGL(k_pol_rhs, gn, b256, 0, st, p);
+    hipLaunchKernelGGL(k_pol_lower, gn, b256, 0, st, p);
+    hipLaunchKernelGGL(k_pol_upper, gn, b256, 0, st, p);
+    if (M) hipLaunchKernelGGL(k_pol_dy, gM, b256, 0, st, p);
+  }
+  return 0;
+}
+
+// the residuals of (xh, yh), the acceptance test and the record p.rec with the point behind it
+void polish_queue_decide(miosqp_qp_engine *e, const Pol &p) {
+  hipStream_t st = e->stream;
+  const size_t n = e->n, M = e->M;
+  const dim3 gM((unsigned)((M + 3) / 4)), gn((unsigned)((n + 3) / 4)), b256(256);
+  if (M) hipLaunchKernelGGL(k_pol_rows_after, gM, b256, 0, st, p);
+  hipLaunchKernelGGL(k_pol_cols, gn, b256, 0, st, p);
+  hipLaunchKernelGGL(k_pol_decide, dim3(1), b256, 0, st, p);
+}
+
+// The polish proper, queued (events 0..4 around its stages): inputs down, the set guessed from (x, y), the solves, the
+// decision.  It is all of miosqp_qp_polish up to the copy back, and round 0 of miosqp_qp_polish_repair.
+int polish_queue_round0(miosqp_qp_engine *e, int refine_iter) {
+  PolishScratch *s = e->pol;
+  const Pol &p = s->p;
+  hipStream_t st = e->stream;
+  const size_t n = e->n, M = e->M;
+  HIPCHK(hipEventRecord(s->ev[0], st));
+  HIPCHK(hipMemcpyAsync((void *)p.l, s->h, sizeof(double) * (3 * M + n), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemsetAsync(p.cnt, 0, 8 * sizeof(int), st));
+  HIPCHK(hipMemsetAsync(p.xh, 0, sizeof(double) * n, st));
+  if (M) {
+    HIPCHK(hipMemsetAsync(p.yh, 0, sizeof(double) * M, st));
+    hipLaunchKernelGGL(k_pol_classify, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, p);
+  }
+  HIPCHK(hipEventRecord(s->ev[1], st));
+  if (int rc = polish_queue_solve(e, p, refine_iter, s->ev[2], s->ev[3])) return rc;
+  polish_queue_decide(e, p);
+  HIPCHK(hipEventRecord(s->ev[4], st));
+  return 0;
+}
+
+void polish_fill_info(const PolRec &r, miosqp_polish_info *info) {
+  info->accepted = r.accepted;
+  info->reason = r.reason;
+  info->n_lower = r.n_lower;
+  info->n_upper = r.n_upper;
+  info->pri_before = r.pri_before;
+  info->dua_before = r.dua_before;
+  info->pri_after = r.pri_after;
+  info->dua_after = r.dua_after;
+  info->obj = r.obj;
 }
 }  // namespace
 
@@ -1377,71 +1509,14 @@ int miosqp_qp_round_and_fix(miosqp_qp_engine *e, const double *l, const double *
 int miosqp_qp_polish(miosqp_qp_engine *e, const double *l, const double *u, const double *x, const double *y,
                      double delta, int32_t refine_iter, double *x_out, double *y_out, miosqp_polish_info *info) {
   if (!e || !l || !u || !x || !y || !x_out || !y_out || !info) return MIOSQP_EARG;
-  ENTER(e);
-  if (!(delta > 0.0) || !(delta < QP_INFTY)) {
-    g_err = "polish: delta must be positive";
-    return MIOSQP_EARG;
-  }
-  if (refine_iter < 0 || refine_iter > 10) {
-    g_err = "polish: refine_iter must be in 0..10";
-    return MIOSQP_EARG;
-  }
+  double t0 = 0.0;
+  if (int rc = polish_begin(e, l, u, x, y, delta, refine_iter, 0, &t0)) return rc;
   const size_t n = e->n, M = e->M;
-  for (size_t j = 0; j < M; j++) {
-    if (l[j] > u[j]) return MIOSQP_EBOUNDS;
-    if (l[j] != l[j] || u[j] != u[j] || y[j] != y[j]) {
-      g_err = "polish: NaN in l, u or y (a node without a solution cannot be polished)";
-      return MIOSQP_EARG;
-    }
-  }
-  for (size_t i = 0; i < n; i++)
-    if (x[i] != x[i]) {
-      g_err = "polish: NaN in x (a node without a solution cannot be polished)";
-      return MIOSQP_EARG;
-    }
-  if (int rc = polish_ensure(e)) return rc;
-  const double t0 = wall();
   PolishScratch *s = e->pol;
-  Pol &p = s->p;
-  p.delta = delta;
-  p.inv_delta = 1.0 / delta;
   double *h = s->h;
-  memcpy(h, l, sizeof(double) * M);
-  memcpy(h + M, u, sizeof(double) * M);
-  memcpy(h + 2 * M, x, sizeof(double) * n);
-  memcpy(h + 2 * M + n, y, sizeof(double) * M);
   hipStream_t st = e->stream;
-  const dim3 gM((unsigned)((M + 3) / 4)), gn((unsigned)((n + 3) / 4)), b256(256);
-  HIPCHK(hipEventRecord(s->ev[0], st));
-  HIPCHK(hipMemcpyAsync((void *)p.l, h, sizeof(double) * (3 * M + n), hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemsetAsync(p.cnt, 0, 4 * sizeof(int), st));
-  HIPCHK(hipMemsetAsync(p.xh, 0, sizeof(double) * n, st));
-  if (M) {
-    HIPCHK(hipMemsetAsync(p.yh, 0, sizeof(double) * M, st));
-    hipLaunchKernelGGL(k_pol_classify, gM, b256, 0, st, p);
-  }
-  HIPCHK(hipEventRecord(s->ev[1], st));
-  hipLaunchKernelGGL(k_pol_schur_row, dim3((unsigned)n), b256, p.ld * sizeof(double), st, p);
-  HIPCHK(hipEventRecord(s->ev[2], st));
-  if (miosqp_device_ldl_inverse_resident((int)n, p.ld, p.S, s->X, p.LinvT, s->W, p.dd, p.cnt + 2, st)) {
-    g_err = "polish: the factorisation of the reduced system could not be queued";
-    return MIOSQP_EHIP;
-  }
-  HIPCHK(hipEventRecord(s->ev[3], st));
-  // (xh, yh) = ksolve(-q, b), then refine_iter corrections by the residuals of the unregularised system: with
-  // xh = yh = 0 the first pass's residuals are exactly (-q, b)
-  for (int it = 0; it <= refine_iter; it++) {
-    if (M) hipLaunchKernelGGL(k_pol_r2, gM, b256, 0, st, p);
-    hipLaunchKernelGGL(k_pol_rhs, gn, b256, 0, st, p);
-    hipLaunchKernelGGL(k_pol_lower, gn, b256, 0, st, p);
-    hipLaunchKernelGGL(k_pol_upper, gn, b256, 0, st, p);
-    if (M) hipLaunchKernelGGL(k_pol_dy, gM, b256, 0, st, p);
-  }
-  if (M) hipLaunchKernelGGL(k_pol_rows_after, gM, b256, 0, st, p);
-  hipLaunchKernelGGL(k_pol_cols, gn, b256, 0, st, p);
-  hipLaunchKernelGGL(k_pol_decide, dim3(1), b256, 0, st, p);
-  HIPCHK(hipEventRecord(s->ev[4], st));
-  HIPCHK(hipMemcpyAsync(h, p.rec, sizeof(double) * (POL_REC_DOUBLES + n + M), hipMemcpyDeviceToHost, st));
+  if (int rc = polish_queue_round0(e, refine_iter)) return rc;
+  HIPCHK(hipMemcpyAsync(h, s->p.rec, sizeof(double) * (POL_REC_DOUBLES + n + M), hipMemcpyDeviceToHost, st));
   HIPCHK(hipEventRecord(s->ev[5], st));
   HIPCHK(hipStreamSynchronize(st));
   HIPCHK(hipGetLastError());
@@ -1451,20 +1526,124 @@ int miosqp_qp_polish(miosqp_qp_engine *e, const double *l, const double *u, cons
     s->stage_s[k] = 1e-3 * ms;
   }
   HIPCHK(hipEventElapsedTime(&ms, s->ev[0], s->ev[5]));
-  const PolRec &r = *(const PolRec *)h;
-  info->accepted = r.accepted;
-  info->reason = r.reason;
-  info->n_lower = r.n_lower;
-  info->n_upper = r.n_upper;
-  info->pri_before = r.pri_before;
-  info->dua_before = r.dua_before;
-  info->pri_after = r.pri_after;
-  info->dua_after = r.dua_after;
-  info->obj = r.obj;
+  polish_fill_info(*(const PolRec *)h, info);
   memcpy(x_out, h + POL_REC_DOUBLES, sizeof(double) * n);
   memcpy(y_out, h + POL_REC_DOUBLES + n, sizeof(double) * M);
   info->device_time = 1e-3 * ms;
   info->run_time = wall() - t0;
+  return 0;
+}
+
+int miosqp_qp_polish_repair(miosqp_qp_engine *e, const double *l, const double *u, const double *x, const double *y,
+                            double delta, int32_t refine_iter, int32_t repair_iter, double *x_out, double *y_out,
+                            miosqp_polish_repair_info *info) {
+  if (!e || !l || !u || !x || !y || !x_out || !y_out || !info) return MIOSQP_EARG;
+  double t0 = 0.0;
+  if (int rc = polish_begin(e, l, u, x, y, delta, refine_iter, repair_iter, &t0)) return rc;
+  const size_t n = e->n, M = e->M;
+  PolishScratch *s = e->pol;
+  Pol p = s->p;
+  double *h = s->h;
+  hipStream_t st = e->stream;
+  const dim3 gM((unsigned)((M + 3) / 4)), b256(256);
+  const size_t nrec = POL_REC_DOUBLES + n + M;
+  if (int rc = polish_queue_round0(e, refine_iter)) return rc;
+  // set k: the set round k solved on (0: guessed from (x, y)); one host decision per round, on the revision's counters
+  int nl[POL_MAX_ROUNDS + 1] = {0}, nu[POL_MAX_ROUNDS + 1] = {0};
+  int k = 0, judged = 0, stop = 0, added = 0, dropped = 0;
+  for (;;) {
+    p.cls = s->cls_buf[k & 1];
+    p.cls_next = s->cls_buf[(k + 1) & 1];
+    HIPCHK(hipMemsetAsync(p.cnt + 4, 0, 4 * sizeof(int), st));
+    if (M) hipLaunchKernelGGL(k_pol_revise, gM, b256, 0, st, p);
+    HIPCHK(hipMemcpyAsync(s->hcnt, p.cnt, 8 * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipEventRecord(s->evr[k], st));
+    const double tw = wall();
+    HIPCHK(hipEventSynchronize(s->evr[k]));
+    s->wait_s[k] = wall() - tw;
+    const int *c = s->hcnt;
+    if (k == 0) {
+      nl[0] = c[0];
+      nu[0] = c[1];
+      if (c[2]) break;  // round 0's own factorisation broke: reason 1, nothing to repair
+    } else if (c[2]) {
+      stop = 2;  // the point and the set of the round before are judged
+      break;
+    }
+    judged = k;
+    added += c[4];
+    dropped += c[5];
+    nl[k + 1] = c[6];
+    nu[k + 1] = c[7];
+    if (c[4] + c[5] == 0) break;
+    if (k == repair_iter) {
+      stop = 1;
+      break;
+    }
+    // round k + 1 on the revised set (k_pol_revise left it in w, b): this round's point is kept, then the same solves
+    // from xh = yh = 0 (the factorisation clears its own flag)
+    HIPCHK(hipMemcpyAsync(s->xk, p.xh, sizeof(double) * n, hipMemcpyDeviceToDevice, st));
+    if (M) HIPCHK(hipMemcpyAsync(s->yk, p.yh, sizeof(double) * M, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemsetAsync(p.xh, 0, sizeof(double) * n, st));
+    if (M) HIPCHK(hipMemsetAsync(p.yh, 0, sizeof(double) * M, st));
+    if (int rc = polish_queue_solve(e, p, refine_iter, nullptr, nullptr)) return rc;
+    k++;
+  }
+  const int rounds = k;
+  if (rounds > 0) {
+    // the final point gets a record of its own behind round 0's
+    if (stop == 2) {
+      HIPCHK(hipMemcpyAsync(p.xh, s->xk, sizeof(double) * n, hipMemcpyDeviceToDevice, st));
+      if (M) HIPCHK(hipMemcpyAsync(p.yh, s->yk, sizeof(double) * M, hipMemcpyDeviceToDevice, st));
+      HIPCHK(hipMemsetAsync(p.cnt + 2, 0, sizeof(int), st));
+    }
+    p.rec = s->rec2;
+    polish_queue_decide(e, p);
+    HIPCHK(hipMemcpyAsync(h + nrec, s->p.rec, sizeof(PolRec), hipMemcpyDeviceToHost, st));
+  }
+  HIPCHK(hipMemcpyAsync(h, p.rec, sizeof(double) * nrec, hipMemcpyDeviceToHost, st));
+  if (M) HIPCHK(hipMemcpyAsync(s->hcls, s->cls_buf[judged & 1], M, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipEventRecord(s->ev[5], st));
+  HIPCHK(hipStreamSynchronize(st));
+  HIPCHK(hipGetLastError());
+  float ms = 0;
+  for (int j = 0; j < 4; j++) {
+    HIPCHK(hipEventElapsedTime(&ms, s->ev[j], s->ev[j + 1]));
+    s->stage_s[j] = 1e-3 * ms;
+  }
+  for (int j = 0; j <= rounds; j++) {
+    HIPCHK(hipEventElapsedTime(&ms, j ? s->evr[j - 1] : s->ev[0], s->evr[j]));
+    s->round_s[j] = 1e-3 * ms;
+  }
+  s->rounds_run = rounds + 1;
+  HIPCHK(hipEventElapsedTime(&ms, s->ev[0], s->ev[5]));
+  const PolRec &r = *(const PolRec *)h, &r0 = rounds > 0 ? *(const PolRec *)(h + nrec) : r;
+  polish_fill_info(r, &info->polish);
+  info->polish.n_lower = nl[judged];
+  info->polish.n_upper = nu[judged];
+  memcpy(x_out, h + POL_REC_DOUBLES, sizeof(double) * n);
+  memcpy(y_out, h + POL_REC_DOUBLES + n, sizeof(double) * M);
+  info->polish.device_time = 1e-3 * ms;
+  info->rounds = rounds;
+  info->stop = stop;
+  info->n_added = added;
+  info->n_dropped = dropped;
+  info->accepted0 = r0.accepted;
+  info->reason0 = r0.reason;
+  info->polish.run_time = wall() - t0;
+  return 0;
+}
+
+int miosqp_qp_get_polish_repair_trace(miosqp_qp_engine *e, int8_t *cls, double *round_seconds, double *wait_seconds) {
+  if (!e) return MIOSQP_EARG;
+  const PolishScratch *s = e->pol;
+  const int run = s ? s->rounds_run : 0;
+  if (cls)
+    for (int j = 0; j < e->M; j++) cls[j] = run ? s->hcls[j] : 0;
+  for (int k = 0; k < POL_MAX_ROUNDS; k++) {
+    if (round_seconds) round_seconds[k] = k < run ? s->round_s[k] : 0.0;
+    if (wait_seconds) wait_seconds[k] = k < run ? s->wait_s[k] : 0.0;
+  }
   return 0;
 }
 

@@ -5,6 +5,12 @@
 // were given at set-up, laid out like the scaled rows (pc_* by constraint, pv_* by variable; pads are zeros).  Plain
 // fp64; every sum has a fixed order (lanes stride a row, partial sums meet in an xor butterfly), the two counters are
 // integer atomics: two identical calls give identical bits.
+//
+// The repair loop (miosqp_qp_polish_repair) goes round steps 2-3: after a round's solves k_pol_revise classifies every
+// row again from the polished point (rows it violates join the set, rows whose multiplier has the wrong sign leave it),
+// the host reads the four counters and either queues the next round on the revised set or goes on to the acceptance.
+constexpr double POL_TOL = 1e-10;  // the revision's tolerance: the floor of the acceptance test
+constexpr int POL_MAX_ROUNDS = 21;  // round 0 and at most 20 repair rounds
 struct PolRec {
   int accepted, reason;  // reason: 0 ok, 1 factorisation, 2 primal, 3 dual
   int n_lower, n_upper;
@@ -22,8 +28,10 @@ struct Pol {
   double *S, *LinvT, *dd;             // S, later strict_lower(L^-1) in place; its transpose; the pivots
   double *xh, *yh, *r1, *r2, *t, *v, *dx;
   double *prow0, *prow1, *dcol0, *dcol1, *ocol;  // per row / per variable terms of the two norms before and after, of the objective
-  int *cnt;                           // [0] lower-active rows, [1] upper-active rows, [2] the factorisation's flag
+  int *cnt;                           // [0] lower-active rows, [1] upper-active rows, [2] the factorisation's flag;
+                                      // the revision's: [4] rows added, [5] dropped, [6] / [7] lower / upper of the new set
   PolRec *rec;                        // followed by the returned x (n) and y (M)
+  signed char *cls, *cls_next;        // per row -1 lower-active, 1 upper-active, 0 inactive: of this round's set, of the revised one
 };
 
 __device__ __forceinline__ double pol_wave_sum(double v) {
@@ -51,18 +59,49 @@ __global__ __launch_bounds__(256) void k_pol_classify(Pol p) {
   if (lane) return;
   const double l = p.l[row], u = p.u[row], y = p.y[row];
   double w = 0.0, b = 0.0;
+  signed char c = 0;
   if (l > -QP_INFTY && (l == u || z - l < -y)) {
     w = p.inv_delta;
     b = l;
+    c = -1;
     atomicAdd(p.cnt, 1);
   } else if (u < QP_INFTY && u - z < y) {
     w = p.inv_delta;
     b = u;
+    c = 1;
     atomicAdd(p.cnt + 1, 1);
   }
   p.w[row] = w;
   p.b[row] = b;
+  p.cls[row] = c;
   p.prow0[row] = pol_max(pol_max(0.0, l - z), z - u);
+}
+
+// The revision after a round's solves, one wavefront per row: z = A xh and the row's class in the revised set.  An
+// equality row stays; a lower-active row whose multiplier is above POL_TOL and an upper-active one whose multiplier is
+// below -POL_TOL leave; an inactive row violated by more than POL_TOL joins on that side (a row that just left is not
+// looked at again).  Weight, bound and class of the revised set, and the four counters.  After a round whose
+// factorisation broke there is no point to revise from: nothing is written and the counters stay zero.
+__global__ __launch_bounds__(256) void k_pol_revise(Pol p) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= p.M) return;
+  if (p.cnt[2] != 0) return;
+  const double z = pol_row_dot(p.pc_idx, p.A, p.pc_ptr[row], p.pc_ptr[row + 1], lane, p.xh);
+  if (lane) return;
+  const double l = p.l[row], u = p.u[row], y = p.yh[row];
+  const signed char c = p.cls[row];
+  signed char cn = c;
+  if (l != u) {
+    if (c < 0) cn = y > POL_TOL ? 0 : c;
+    else if (c > 0) cn = y < -POL_TOL ? 0 : c;
+    else if (l > -QP_INFTY && l - z > POL_TOL) cn = -1;
+    else if (u < QP_INFTY && z - u > POL_TOL) cn = 1;
+  }
+  if (cn != c) atomicAdd(p.cnt + (c == 0 ? 4 : 5), 1);
+  if (cn != 0) atomicAdd(p.cnt + (cn < 0 ? 6 : 7), 1);
+  p.w[row] = cn != 0 ? p.inv_delta : 0.0;
+  p.b[row] = cn < 0 ? l : cn > 0 ? u : 0.0;
+  p.cls_next[row] = cn;
 }
 
 // Row i1 of S = P + delta I + sum over active rows r of (1 / delta) A[r][i1] A[r][:] (lower triangle; the rest of the
@@ -261,4 +300,14 @@ struct PolishScratch {
   double *h = nullptr;
   hipEvent_t ev[6] = {};
   double stage_s[4] = {0, 0, 0, 0};  // classification, Schur rows, factorisation, solves + acceptance of the last call
+  // the repair loop: the kept point of the round before (n + M), the second class array, the second record (+ x + y), the
+  // counters' pinned copy, an event per round (the host waits for it), and the last call's trace
+  double *xk = nullptr, *yk = nullptr;
+  signed char *cls_buf[2] = {nullptr, nullptr};  // the set of round k is in cls_buf[k & 1]
+  PolRec *rec2 = nullptr;
+  int *hcnt = nullptr;
+  signed char *hcls = nullptr;
+  hipEvent_t evr[POL_MAX_ROUNDS] = {};
+  int rounds_run = 0;                 // rounds of the last repair call, round 0 included (0: none yet)
+  double round_s[POL_MAX_ROUNDS] = {}, wait_s[POL_MAX_ROUNDS] = {};  // device seconds of a round up to its counters, host wait for them
 };

@@ -265,25 +265,52 @@ class OSQP(object):
                                      iter=iters[:K], obj=obj[:K], viol=viol[:K], feasible=info.feasible,
                                      iters=info.iters, device_time=info.device_time, run_time=info.run_time)
 
-    def polish(self, l, u, x, y, delta=1e-6, refine_iter=3):
+    def polish(self, l, u, x, y, delta=1e-6, refine_iter=3, repair_iter=None):
         """Polishing of one node's solution (bounds l, u; approximate x, y) on the device (miosqp_qp_polish): the active
         set guessed from (x, y), the regularised KKT system on it solved through a dense factorisation of the reduced
         matrix and refined `refine_iter` times.  Returns the record (accepted, reason 0 ok / 1 factorisation / 2 primal
         / 3 dual, n_lower, n_upper, pri / dua before and after, obj of the polished point, device_time, run_time) plus
         x, y: the polished point when accepted, the input otherwise.  The QP setting `polish` stays ignored: this is a
-        call of its own."""
+        call of its own.
+
+        repair_iter None: as above.  An integer 0..20 calls miosqp_qp_polish_repair: up to that many rounds that revise
+        the set from the polished point and solve again; the record is that of the point the loop ended with and gains
+        rounds, stop (0 fixed point, 1 round limit, 2 bad pivot in a repair round), n_added, n_dropped, accepted0,
+        reason0 (round 0's answer) and active (per row -1 lower, 1 upper, 0 inactive in the final set)."""
         l, u = _f64(l, self.m, "l"), _f64(u, self.m, "u")
         x, y = _f64(x, self.n, "x"), _f64(y, self.m, "y")
-        xo, yo, info = np.empty(self.n), np.empty(self.m), _lib.PolishInfo()
-        rc = _check(self._lib.miosqp_qp_polish(self._h, _lib.as_d(l), _lib.as_d(u), _lib.as_d(x), _lib.as_d(y),
-                                               float(delta), int(refine_iter), _lib.as_d(xo), _lib.as_d(yo),
-                                               C.byref(info)), "polish")
+        xo, yo = np.empty(self.n), np.empty(self.m)
+        args = (self._h, _lib.as_d(l), _lib.as_d(u), _lib.as_d(x), _lib.as_d(y), float(delta), int(refine_iter))
+        if repair_iter is None:
+            rep, info = None, _lib.PolishInfo()
+            rc = _check(self._lib.miosqp_qp_polish(*args, _lib.as_d(xo), _lib.as_d(yo), C.byref(info)), "polish")
+        else:
+            rep = _lib.PolishRepairInfo()
+            rc = _check(self._lib.miosqp_qp_polish_repair(*args, int(repair_iter), _lib.as_d(xo), _lib.as_d(yo),
+                                                          C.byref(rep)), "polish_repair")
+            info = rep.polish
         if rc == 1:
             raise ValueError("Lower bound must be lower than or equal to upper bound")
-        return types.SimpleNamespace(x=xo, y=yo, accepted=bool(info.accepted), reason=info.reason, n_lower=info.n_lower,
-                                     n_upper=info.n_upper, pri_before=info.pri_before, dua_before=info.dua_before,
-                                     pri_after=info.pri_after, dua_after=info.dua_after, obj=info.obj,
-                                     device_time=info.device_time, run_time=info.run_time)
+        out = types.SimpleNamespace(x=xo, y=yo, accepted=bool(info.accepted), reason=info.reason, n_lower=info.n_lower,
+                                    n_upper=info.n_upper, pri_before=info.pri_before, dua_before=info.dua_before,
+                                    pri_after=info.pri_after, dua_after=info.dua_after, obj=info.obj,
+                                    device_time=info.device_time, run_time=info.run_time)
+        if rep is not None:
+            out.rounds, out.stop, out.n_added, out.n_dropped = rep.rounds, rep.stop, rep.n_added, rep.n_dropped
+            out.accepted0, out.reason0 = bool(rep.accepted0), rep.reason0
+            cls = np.zeros(self.m, dtype=np.int8)
+            _check(self._lib.miosqp_qp_get_polish_repair_trace(self._h, cls.ctypes.data_as(C.POINTER(C.c_int8)), None,
+                                                               None), "get_polish_repair_trace")
+            out.active = cls.astype(np.int64)
+        return out
+
+    def polish_rounds(self):
+        """Of the last polish call with repair_iter: per round (round 0 first, 21 entries, zeros for rounds not run) the
+        device seconds up to the revision's counters, and the host's wait for them."""
+        dev, wait = np.zeros(21), np.zeros(21)
+        _check(self._lib.miosqp_qp_get_polish_repair_trace(self._h, None, _lib.as_d(dev), _lib.as_d(wait)),
+               "get_polish_repair_trace")
+        return dev, wait
 
     def polish_stages(self):
         """Device seconds of the last polish call: classification, rows of the reduced matrix, factorisation, solves."""

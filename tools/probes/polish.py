@@ -6,8 +6,11 @@ Config 1 and config 2 of problems.random_miqp (seed 0), rho 0.1 and "auto":
     reduced matrix, factorisation + inverse, solves + refinement + acceptance;
   * whether the two rho modes end on the same integer assignment, and how far their upper_glob are apart before and
     after polishing.
+With --repair-iter K > 0, for the config-2 root (both rho) and for config-1 incumbents with their integers fixed (seed 0
+at rho 0.1, seed 1 at rho "auto"): the device time of a plain polish, of a repair call as a whole and round by round
+(a round's time runs up to the revision's counters), and the host's wait for each round's counters.
 
-    python tools/probes/polish.py [--out profiles/polish.txt] [--reps 5]
+    python tools/probes/polish.py [--out profiles/polish.txt] [--reps 5] [--repair-iter 5] [--no-trees]
 """
 import argparse
 import os
@@ -30,17 +33,66 @@ def tree(pr, rho, on):
     return m, r, time.time() - t0
 
 
+def repair_calls(out, reps, repair_iter):
+    """plain polish against the repair call on four inputs, each solved by the engine that then polishes it"""
+    out("# repair loop, repair_iter %d: device times in us, medians of %d; a round's time runs from the round before's "
+        "counters (round 0: from the call's first event) to its own, `wait` is the host's wait for them" % (repair_iter, reps))
+    for label, cfg, seed, rho, incumbent in (("cfg2 root", "cfg2", 0, 0.1, False), ("cfg2 root", "cfg2", 0, "auto", False),
+                                             ("cfg1 incumbent", "cfg1", 0, 0.1, True),
+                                             ("cfg1 incumbent", "cfg1", 1, "auto", True)):
+        c = problems.CONFIGS[cfg]
+        pr = problems.random_miqp(c["n"], c["m"], c["p"], density=c["density"], seed=seed)
+        m = bnb.MIOSQP()
+        m.setup(pr["P"], pr["q"], pr["A"], np.copy(pr["l"]), np.copy(pr["u"]), pr["i_idx"], pr["i_l"], pr["i_u"],
+                dict(problems.BNB_SETTINGS), dict(problems.QP_SETTINGS, rho=rho))
+        w, d = m.work, m.work.data
+        l, u = d.l.copy(), d.u.copy()
+        if incumbent:
+            r = m.solve()
+            xi = np.round(r.x[d.i_idx])
+            l[d.m:] = xi
+            u[d.m:] = xi
+            node = w.solver.solve_node(l, u, np.array(r.x), np.zeros(d.m + d.n_int))
+        else:
+            node = w.solver.solve_node(l, u, np.zeros(d.n), np.zeros(d.m + d.n_int))
+        plain, whole, rounds, waits = [], [], [], []
+        for _ in range(reps):
+            p0 = w.solver.polish(l, u, node.x, node.y)
+            plain.append(p0.device_time)
+            p = w.solver.polish(l, u, node.x, node.y, repair_iter=repair_iter)
+            whole.append(p.device_time)
+            dev, wait = w.solver.polish_rounds()
+            rounds.append(dev[:p.rounds + 1])
+            waits.append(wait[:p.rounds + 1])
+        rs, ws = 1e6 * np.median(np.array(rounds), axis=0), 1e6 * np.median(np.array(waits), axis=0)
+        out("%s seed %d rho %-5r plain: accepted %d reason %d, %d rows, %.1f us | repair: accepted %d, rounds %d stop %d "
+            "+%d -%d, %d rows, pri %.1e dua %.1e, %.1f us; rounds %s; wait %s"
+            % (label, seed, rho, p0.accepted, p0.reason, p0.n_lower + p0.n_upper, 1e6 * np.median(plain), p.accepted,
+               p.rounds, p.stop, p.n_added, p.n_dropped, p.n_lower + p.n_upper, p.pri_after, p.dua_after,
+               1e6 * np.median(whole), " ".join("%.1f" % v for v in rs), " ".join("%.1f" % v for v in ws)))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--repair-iter", type=int, default=0, help="also time the repair loop with this many rounds at most")
+    ap.add_argument("--no-trees", action="store_true", help="skip the whole trees: the single calls only")
     a = ap.parse_args()
-    lines = []
+    f = open(a.out, "w") if a.out else None
 
     def out(s=""):
         print(s, flush=True)
-        lines.append(s)
+        if f:
+            f.write(s + "\n")
+            f.flush()
 
+    if a.repair_iter > 0:
+        repair_calls(out, a.reps, a.repair_iter)
+    if a.no_trees:
+        if f:
+            f.close()
+        return
     out("# polishing of the incumbent (one MI355X), random_miqp seed 0; times are measured, medians of %d" % a.reps)
     for cfg in ("cfg1", "cfg2"):
         c = problems.CONFIGS[cfg]
@@ -82,9 +134,8 @@ def main():
         same = bool(np.array_equal(ints[0.1][0], ints["auto"][0]))
         out("%s rho 0.1 vs auto: integer parts %s; |upper_glob difference| search %.2e, polished %.2e"
             % (cfg, "agree" if same else "DIFFER", abs(ints[0.1][1] - ints["auto"][1]), abs(ints[0.1][2] - ints["auto"][2])))
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
+    if f:
+        f.close()
 
 
 if __name__ == "__main__":
