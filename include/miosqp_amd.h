@@ -298,6 +298,35 @@ int miosqp_qp_polish_repair(miosqp_qp_engine *e, const double *l, const double *
  * (miosqp_qp_get_polish_stages reports round 0's stages after such a call.) */
 int miosqp_qp_get_polish_repair_trace(miosqp_qp_engine *e, int8_t *cls, double *round_seconds, double *wait_seconds);
 
+/* ---- polishing of many small instances in one launch -----------------------------------------------------------
+ * The polish of the MPC re-solve pattern (/root/reference/miosqp/solver.py:174-212 per MIQP,
+ * examples/power_converter/power_converter.py:467-476 per sampling step; `polish` reaches OSQP through qp_settings,
+ * /root/reference/miosqp/workspace.py:67-68): B instances on this engine's P and A, each with its own linear cost and
+ * bounds, polished side by side.  OSQP has NO batched polish (osqp_polish of OSQP 0.6.x works on one workspace), and no
+ * repair loop either.
+ * All arrays are instance-major: q, x, x_out B x n; l, u, y, y_out B x M; info B records.  q == NULL: the engine's
+ * current linear cost for every instance.  Per instance b the answer is what miosqp_qp_polish_repair gives after
+ * miosqp_qp_update_lin_cost(q_b): the same classification rule, the same S built in the same order, 1 + refine_iter
+ * solves against the unregularised system, the same revision (tol 1e-10), stops 0 / 1 / 2, the kept point after a bad
+ * pivot in a repair round, the same acceptance test and reasons 0-3, accepted0 / reason0, and the input bit for bit on
+ * rejection.  Only the order of the sums differs (one workgroup owns an instance from start to finish: S is factorised
+ * by a textbook LDL^T in LDS and solved by substitution, and the rounds run inside the launch with no host decision):
+ * integer fields are equal wherever no comparison sits on a tie.  repair_iter 0 is the plain polish plus one revision.
+ * An instance's answer has the same bits whatever B is and wherever it sits in the batch.  device_time / run_time in
+ * every record are the call's totals.
+ * The engine's q, bounds, iterates and the single polish's scratch are not touched.
+ * MIOSQP_EARG: B < 1, delta <= 0, refine_iter outside 0..10, repair_iter outside 0..20, a NaN anywhere in q, l, u, x, y;
+ * MIOSQP_EBOUNDS: l > u in any instance (nothing is computed); MIOSQP_EUNSUPPORTED: the reduced system and the rows of
+ * A do not fit one workgroup's 160 KB of LDS -- every n + M <= 192 fits, which is everything miosqp_qp_solve_tree(s)
+ * takes. */
+int miosqp_qp_polish_many(miosqp_qp_engine *e, int32_t B, const double *q, const double *l, const double *u,
+                          const double *x, const double *y, double delta, int32_t refine_iter, int32_t repair_iter,
+                          double *x_out, double *y_out, miosqp_polish_repair_info *info);
+
+/* of the last miosqp_qp_polish_many call: cls (M) the class of every row of instance b in its final set (-1
+ * lower-active, 1 upper-active, 0 inactive).  MIOSQP_EARG when that call had no instance b. */
+int miosqp_qp_get_polish_many_classes(miosqp_qp_engine *e, int32_t b, int8_t *cls);
+
 /* ---- a whole tree search in one launch (small problems) ------------------------------------------------
  * the MPC re-solve path (/root/reference/miosqp/solver.py:65-172 per MIQP,
  * examples/power_converter/power_converter.py:421-508 per sampling step).  For problems the LDS-resident solver

@@ -318,6 +318,18 @@ def polish_restatement(P, q, A, l, u, x, y, delta=1e-6, refine_iter=3, repair_it
     return out
 
 
+def primal_guess_multipliers(l, u, z, tau):
+    """A multiplier guess from the primal side alone, for polishing a point that comes without a y (a tree's incumbent):
+    y_j = 0 where l_j == u_j (an equality row is active whatever y says) or both bounds are infinite (never active);
+    otherwise y_j = -tau when z_j - l_j < u_j - z_j (the lower bound is the nearer one), else +tau.  Under OSQP's rule
+    (polish_restatement step 1) a row is then lower-active iff z - l < tau, otherwise upper-active iff u - z < tau: the
+    rows within tau of a bound.  The repair loop corrects what this guesses wrongly."""
+    l, u, z = np.asarray(l, dtype=float), np.asarray(u, dtype=float), np.asarray(z, dtype=float)
+    y = np.where(z - l < u - z, -float(tau), float(tau))
+    y[(l == u) | ((l <= -POLISH_INFTY) & (u >= POLISH_INFTY))] = 0.0
+    return y
+
+
 def add_bounds(i_idx, l_new, u_new, A, l, u):
     """Append l_new <= x[i_idx] <= u_new as identity rows of A (data.py:5-33)."""
     n = A.shape[1]
@@ -1077,7 +1089,74 @@ class MIOSQP(object):
             alive = hs.step(st['max_iter_bb'] - work.iter_num)
         work.leaves = [root] * int(alive)  # the leaves live on the device; what matters is whether any is left
 
-    def solve_many(self, instances):
+    def _instance_vectors(self, instances):
+        """(Q, L, U) of solve_many's instances, instance-major: the model's current vector where a key is missing"""
+        data = self.work.data
+        B, n, m, M = len(instances), data.n, data.m, data.m + data.n_int
+        Q = np.empty((B, n)); L = np.empty((B, M)); U = np.empty((B, M))
+        for k, inst in enumerate(instances):
+            Q[k] = data.q if inst.get('q') is None else inst['q']
+            L[k] = data.l; U[k] = data.u
+            if inst.get('l') is not None:
+                L[k, :m] = inst['l']
+            if inst.get('u') is not None:
+                U[k, :m] = inst['u']
+        return Q, L, U
+
+    def polish_many(self, instances, results, tau=None, repair_iter=20):
+        """Polishes the answers of `solve_many(instances)` in place, all in ONE device call.  For every result with status
+        MI_SOLVED / MI_MAX_ITER_FEASIBLE: its x with the integers rounded, the instance's l, u with the integer rows fixed
+        to them, and -- a tree returns no y -- the multipliers of `primal_guess_multipliers(l, u, A x, tau)`
+        (tau None: 10 x qp_settings['eps_abs']); the repair loop of the polish (up to `repair_iter` rounds) corrects the
+        guess.  delta and refine_iter are the settings polish_delta / polish_refine_iter.  On an engine with
+        `polish_many` the call is `OSQP.polish_many` (one launch, one workgroup per instance); a backend without it, or a
+        problem it does not hold, goes through polish_restatement per instance with that instance's q.  An instance's
+        point is adopted when `accepted and stop == 0`: the guessed y makes dua_before meaningless, so the fixed point of
+        the revision is the certificate.  On adoption x is the polished point with its integers set exactly and
+        upper_glob its objective with the instance's q.  Every result gains polished (bool), polish_rounds, pri_after,
+        dua_after (NaN where nothing was polished).  The model is not touched.  Returns `results`."""
+        work, data = self.work, self.work.data
+        if len(instances) != len(results):
+            raise ValueError('polish_many: one result per instance')
+        pol = work.pol
+        if tau is None:
+            tau = 10. * work.qp_settings.get('eps_abs', 1e-3)
+        if not tau > 0:
+            raise ValueError('polish_many: tau must be positive')
+        for r in results:
+            r.update(polished=False, polish_rounds=0, pri_after=np.nan, dua_after=np.nan)
+        todo = [k for k, r in enumerate(results) if r['status'] in (MI_SOLVED, MI_MAX_ITER_FEASIBLE)]
+        if not todo:
+            return results
+        Q, L, U = self._instance_vectors([instances[k] for k in todo])
+        ii, m = data.i_idx, data.m
+        X = np.array([results[k]['x'] for k in todo], dtype=float)
+        XI = np.round(X[:, ii])
+        X[:, ii] = XI
+        L[:, m:] = XI
+        U[:, m:] = XI
+        Y = np.array([primal_guess_multipliers(L[b], U[b], data.A.dot(X[b]), tau) for b in range(len(todo))])
+        recs = None
+        if hasattr(work.solver, 'polish_many') and not getattr(work, '_no_polish_many', False):
+            recs = work.solver.polish_many(Q, L, U, X, Y, pol['delta'], pol['refine_iter'], repair_iter)
+            if recs is None:
+                work._no_polish_many = True  # this problem is beyond one workgroup: do not ask again
+        if recs is None:
+            recs = [polish_restatement(data.P, Q[b], data.A, L[b], U[b], X[b], Y[b], pol['delta'], pol['refine_iter'],
+                                       repair_iter=repair_iter) for b in range(len(todo))]
+        for b, k in enumerate(todo):
+            r, res = recs[b], results[k]
+            res['polish_rounds'] = int(r.rounds)
+            res['pri_after'], res['dua_after'] = float(r.pri_after), float(r.dua_after)
+            if r.accepted and r.stop == 0:
+                x = np.array(r.x, dtype=float)
+                x[ii] = XI[b]
+                res['x'] = x
+                res['upper_glob'] = .5 * np.dot(x, data.P.dot(x)) + np.dot(Q[b], x)
+                res['polished'] = True
+        return results
+
+    def solve_many(self, instances, polish=False):
         """B MIQPs on this model's factorisation, solved TOGETHER: instance k is what
         `update_vectors(q=, l=, u=)` [+ `set_x0(x0)`] + `solve()` would solve (the reference's MPC pattern,
         /root/reference/miosqp/solver.py:174-212, examples/power_converter/power_converter.py:467-476), for a list of
@@ -1088,7 +1167,11 @@ class MIOSQP(object):
         sequential calls.  The model itself is left as it was: the one-launch path touches nothing of it, the sequential
         fallback puts q, l, u, the leaf list and the statistics back when it is done or when an instance raises (leaves of
         an unfinished device-hosted search are placeholders and not resumable either way).
-        Returns a list of dicts: x, upper_glob, status, nodes, osqp_iter, run_time."""
+        Returns a list of dicts: x, upper_glob, status, nodes, osqp_iter, run_time.
+
+        polish=True: the incumbents are then polished together by `polish_many` (one more launch on the HIP engine) and
+        every dict gains polished, polish_rounds, pri_after, dua_after.  Polishing many instances is asked for per call:
+        the setting polish_incumbent, which polishes the incumbent of `solve`, stays refused here."""
         work, data, st = self.work, self.work.data, self.work.settings
         require_plain_search(st, "solve_many", rule=False, heuristic=False)
         B = len(instances)
@@ -1099,15 +1182,9 @@ class MIOSQP(object):
             and not work.rf['on'] \
             and st['tree_explor_rule'] in (0, 1) and data.n_int > 0 and 'eps_abs' in work.qp_settings \
             and st.get('device_digest', True) and not getattr(work, '_no_trees', False)
-        Q = np.empty((B, n)); L = np.empty((B, M)); U = np.empty((B, M))
+        Q, L, U = self._instance_vectors(instances)
         up = np.full(B, np.inf); XI = np.zeros((B, n)); any_inc = False
         for k, inst in enumerate(instances):
-            Q[k] = data.q if inst.get('q') is None else inst['q']
-            L[k] = data.l; U[k] = data.u
-            if inst.get('l') is not None:
-                L[k, :m] = inst['l']
-            if inst.get('u') is not None:
-                U[k, :m] = inst['u']
             x0 = inst.get('x0')
             if x0 is not None:
                 # Workspace.set_x0 (workspace.py:94-111) on this instance's data
@@ -1174,6 +1251,8 @@ class MIOSQP(object):
                 self.update_vectors(q=q_keep, l=l_keep, u=u_keep)
                 for a, v in keep.items():
                     setattr(work, a, v)
+        if polish:
+            self.polish_many(instances, out)
         return out
 
     def update_vectors(self, q=None, l=None, u=None):

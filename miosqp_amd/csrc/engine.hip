@@ -37,6 +37,7 @@
 
 #include "../../include/miosqp_amd.h"
 #include "factor.hpp"
+#include "polish_many.hpp"  // polishing of many small instances in one launch (polish_many.hip)
 
 #define QP_INFTY 1e30
 #define QP_MIN_SCALING 1e-4
@@ -481,6 +482,50 @@ int polish_queue_round0(miosqp_qp_engine *e, int refine_iter) {
   return 0;
 }
 
+// ---- polishing of many instances (miosqp_qp_polish_many): the pinned blocks and their device copies, grown with B ----
+void polish_many_free(miosqp_qp_engine *e) {
+  miosqp::PolManyScratch *s = e->polm;
+  if (!s) return;
+  for (void *ev : s->ev)
+    if (ev) hipEventDestroy((hipEvent_t)ev);
+  if (s->h_in) hipHostFree(s->h_in);
+  if (s->h_out) hipHostFree(s->h_out);
+  if (s->d_in) hipFree(s->d_in);
+  if (s->d_out) hipFree(s->d_out);
+  delete s;
+  e->polm = nullptr;
+}
+
+int polish_many_ensure(miosqp_qp_engine *e, size_t n_in, size_t n_out) {
+  if (!e->polm) {
+    e->polm = new miosqp::PolManyScratch();
+    for (void *&ev : e->polm->ev) HIPCHK(hipEventCreate((hipEvent_t *)&ev));
+  }
+  miosqp::PolManyScratch *s = e->polm;
+  if (n_in > s->cap_in) {
+    HIPCHK(hipStreamSynchronize(e->stream));
+    if (s->h_in) hipHostFree(s->h_in);
+    if (s->d_in) hipFree(s->d_in);
+    s->h_in = s->d_in = nullptr;
+    s->cap_in = 0;
+    HIPCHK(hipHostMalloc((void **)&s->h_in, n_in * sizeof(double), hipHostMallocDefault));
+    HIPCHK(hipMalloc((void **)&s->d_in, n_in * sizeof(double)));
+    s->cap_in = n_in;
+  }
+  if (n_out > s->cap_out) {
+    HIPCHK(hipStreamSynchronize(e->stream));
+    if (s->h_out) hipHostFree(s->h_out);
+    if (s->d_out) hipFree(s->d_out);
+    s->h_out = s->d_out = nullptr;
+    s->cap_out = 0;
+    s->last_B = 0;
+    HIPCHK(hipHostMalloc((void **)&s->h_out, n_out * sizeof(double), hipHostMallocDefault));
+    HIPCHK(hipMalloc((void **)&s->d_out, n_out * sizeof(double)));
+    s->cap_out = n_out;
+  }
+  return 0;
+}
+
 void polish_fill_info(const PolRec &r, miosqp_polish_info *info) {
   info->accepted = r.accepted;
   info->reason = r.reason;
@@ -595,6 +640,7 @@ int miosqp_qp_cleanup(miosqp_qp_engine *e) {
   if (e->hb_dbl) hipHostFree(e->hb_dbl);
   if (e->h_der) hipHostFree(e->h_der);
   polish_free(e);
+  polish_many_free(e);
   for (int k = 0; k < 16; k++) {
     if (e->xb_full[k]) hipGraphExecDestroy(e->xb_full[k]);
     if (e->xb_tail[k]) hipGraphExecDestroy(e->xb_tail[k]);
@@ -1644,6 +1690,124 @@ int miosqp_qp_get_polish_repair_trace(miosqp_qp_engine *e, int8_t *cls, double *
     if (round_seconds) round_seconds[k] = k < run ? s->round_s[k] : 0.0;
     if (wait_seconds) wait_seconds[k] = k < run ? s->wait_s[k] : 0.0;
   }
+  return 0;
+}
+
+int miosqp_qp_polish_many(miosqp_qp_engine *e, int32_t B, const double *q, const double *l, const double *u,
+                          const double *x, const double *y, double delta, int32_t refine_iter, int32_t repair_iter,
+                          double *x_out, double *y_out, miosqp_polish_repair_info *info) {
+  if (!e || !l || !u || !x || !y || !x_out || !y_out || !info) return MIOSQP_EARG;
+  ENTER(e);
+  if (B < 1) {
+    g_err = "polish_many: B must be at least 1";
+    return MIOSQP_EARG;
+  }
+  if (!(delta > 0.0) || !(delta < QP_INFTY)) {
+    g_err = "polish_many: delta must be positive";
+    return MIOSQP_EARG;
+  }
+  if (refine_iter < 0 || refine_iter > 10) {
+    g_err = "polish_many: refine_iter must be in 0..10";
+    return MIOSQP_EARG;
+  }
+  if (repair_iter < 0 || repair_iter >= POL_MAX_ROUNDS) {
+    g_err = "polish_many: repair_iter must be in 0..20";
+    return MIOSQP_EARG;
+  }
+  const size_t n = e->n, M = e->M, nB = (size_t)B;
+  for (size_t j = 0; j < nB * M; j++) {
+    if (l[j] > u[j]) return MIOSQP_EBOUNDS;
+    if (l[j] != l[j] || u[j] != u[j] || y[j] != y[j]) {
+      g_err = "polish_many: NaN in l, u or y (a node without a solution cannot be polished)";
+      return MIOSQP_EARG;
+    }
+  }
+  for (size_t i = 0; i < nB * n; i++)
+    if (x[i] != x[i] || (q && q[i] != q[i])) {
+      g_err = "polish_many: NaN in x or q";
+      return MIOSQP_EARG;
+    }
+  if (miosqp::polish_many_lds_bytes((int)n, (int)M) > 160 * 1024) {
+    g_err = "polish_many: only for problems whose reduced system and rows of A fit one workgroup's 160 KB of LDS";
+    return MIOSQP_EUNSUPPORTED;
+  }
+  if (int rc = polish_ensure(e)) return rc;  // (places the unscaled rows of A on the device; nothing of it is written here)
+  const size_t so = miosqp::polm_out_stride((int)n, (int)M);
+  const size_t n_in = nB * ((q ? 2 : 1) * n + 3 * M), n_out = nB * so;
+  if (int rc = polish_many_ensure(e, n_in, n_out)) return rc;
+  const double t0 = wall();
+  miosqp::PolManyScratch *s = e->polm;
+  s->last_B = 0;
+  // one block down: [q] | l | u | x | y, each instance-major
+  double *h = s->h_in;
+  const size_t oq = 0, ol = q ? nB * n : 0, ou = ol + nB * M, ox = ou + nB * M, oy = ox + nB * n;
+  if (q) memcpy(h + oq, q, sizeof(double) * nB * n);
+  memcpy(h + ol, l, sizeof(double) * nB * M);
+  memcpy(h + ou, u, sizeof(double) * nB * M);
+  memcpy(h + ox, x, sizeof(double) * nB * n);
+  memcpy(h + oy, y, sizeof(double) * nB * M);
+  const Pol &p = e->pol->p;
+  miosqp::PolManyArgs a{};
+  a.n = (int)n; a.M = (int)M; a.B = B; a.refine_iter = refine_iter; a.repair_iter = repair_iter;
+  a.delta = delta; a.inv_delta = 1.0 / delta;
+  a.pc_ptr = p.pc_ptr; a.pc_idx = p.pc_idx; a.pr_ptr = p.pr_ptr; a.pr_idx = p.pr_idx;
+  a.A = p.A; a.pr_val = p.pr_val;
+  a.q = q ? s->d_in + oq : nullptr;
+  a.q_engine = e->d.qraw;
+  a.l = s->d_in + ol; a.u = s->d_in + ou; a.x = s->d_in + ox; a.y = s->d_in + oy;
+  a.out = s->d_out;
+  hipStream_t st = e->stream;
+  HIPCHK(hipEventRecord((hipEvent_t)s->ev[0], st));
+  HIPCHK(hipMemcpyAsync(s->d_in, h, sizeof(double) * n_in, hipMemcpyHostToDevice, st));
+  if (int rc = miosqp::polish_many_launch(a, (void *)st)) {
+    set_err("polish_many: launch", (hipError_t)rc, __FILE__, __LINE__);
+    return MIOSQP_EHIP;
+  }
+  HIPCHK(hipMemcpyAsync(s->h_out, s->d_out, sizeof(double) * n_out, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipEventRecord((hipEvent_t)s->ev[1], st));
+  HIPCHK(hipStreamSynchronize(st));
+  HIPCHK(hipGetLastError());
+  float ms = 0;
+  HIPCHK(hipEventElapsedTime(&ms, (hipEvent_t)s->ev[0], (hipEvent_t)s->ev[1]));
+  for (size_t b = 0; b < nB; b++) {
+    const double *o = s->h_out + b * so;
+    const miosqp::PolManyRec &r = *(const miosqp::PolManyRec *)o;
+    miosqp_polish_repair_info &f = info[b];
+    f.polish.accepted = r.accepted;
+    f.polish.reason = r.reason;
+    f.polish.n_lower = r.n_lower;
+    f.polish.n_upper = r.n_upper;
+    f.polish.pri_before = r.pri_before;
+    f.polish.dua_before = r.dua_before;
+    f.polish.pri_after = r.pri_after;
+    f.polish.dua_after = r.dua_after;
+    f.polish.obj = r.obj;
+    f.polish.device_time = 1e-3 * ms;
+    f.rounds = r.rounds;
+    f.stop = r.stop;
+    f.n_added = r.n_added;
+    f.n_dropped = r.n_dropped;
+    f.accepted0 = r.accepted0;
+    f.reason0 = r.reason0;
+    memcpy(x_out + b * n, o + miosqp::POLM_REC_DOUBLES, sizeof(double) * n);
+    memcpy(y_out + b * M, o + miosqp::POLM_REC_DOUBLES + n, sizeof(double) * M);
+  }
+  s->last_B = B;
+  const double rt = wall() - t0;
+  for (size_t b = 0; b < nB; b++) info[b].polish.run_time = rt;
+  return 0;
+}
+
+int miosqp_qp_get_polish_many_classes(miosqp_qp_engine *e, int32_t b, int8_t *cls) {
+  if (!e || !cls) return MIOSQP_EARG;
+  const miosqp::PolManyScratch *s = e->polm;
+  if (!s || b < 0 || b >= s->last_B) {
+    g_err = "get_polish_many_classes: no such instance in the last polish_many call";
+    return MIOSQP_EARG;
+  }
+  const size_t n = e->n, M = e->M;
+  const double *o = s->h_out + (size_t)b * miosqp::polm_out_stride((int)n, (int)M);
+  memcpy(cls, o + miosqp::POLM_REC_DOUBLES + n + M, M);
   return 0;
 }
 

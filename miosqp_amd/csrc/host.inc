@@ -180,6 +180,7 @@ struct miosqp_qp_engine {
   // the scratch of the reduced system, built on the first call and freed with the engine
   std::vector<double> A_raw;
   PolishScratch *pol = nullptr;
+  miosqp::PolManyScratch *polm = nullptr;  // polishing of many instances in one launch (miosqp_qp_polish_many)
   hipGraphExec_t xb_full[16] = {}, xb_tail[16] = {};
   hipGraph_t gb_full[16] = {}, gb_tail[16] = {};
   bool compact = true;   // compaction of converged columns in solve_batch (MIOSQP_COMPACT=0 disables)

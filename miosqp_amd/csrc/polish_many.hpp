@@ -1,0 +1,47 @@
+// Polishing of many small instances in one launch (polish_many.hip; C entry miosqp_qp_polish_many in engine.hip):
+// what the two translation units share -- the kernel's argument block, the record an instance writes, the host's scratch.
+#pragma once
+
+#include <cstddef>
+#include <cstdint>
+
+namespace miosqp {
+
+// one instance's answer on the device and in the pinned block: this record, then x (n), y (M), then the class of every
+// row in the final set (M bytes, padded to doubles)
+struct PolManyRec {
+  int accepted, reason, n_lower, n_upper;
+  int rounds, stop, n_added, n_dropped, accepted0, reason0, pad[2];
+  double pri_before, dua_before, pri_after, dua_after, obj;
+};
+constexpr size_t POLM_REC_DOUBLES = (sizeof(PolManyRec) + 7) / 8;
+constexpr size_t polm_out_stride(int n, int M) { return POLM_REC_DOUBLES + (size_t)n + (size_t)M + ((size_t)M + 7) / 8; }
+
+// raw device pointers and sizes: the unscaled problem as the single polish keeps it (rows of A by constraint with the
+// engine's padded pattern, rows of the full symmetric P), the call's inputs (instance-major) and where the answers go
+struct PolManyArgs {
+  int n, M, B, refine_iter, repair_iter;
+  double delta, inv_delta;
+  const int *pc_ptr, *pc_idx, *pr_ptr, *pr_idx;
+  const double *A, *pr_val;
+  const double *q;         // B x n, or nullptr: q_engine (n) for every instance
+  const double *q_engine;
+  const double *l, *u, *x, *y;  // B x M, B x M, B x n, B x M
+  double *out;             // B x polm_out_stride(n, M)
+};
+
+// host scratch of one engine: the pinned blocks of both directions and their device copies (grown with B on demand),
+// the events around a call; the last call's answers stay in h_out for the class getter
+struct PolManyScratch {
+  double *h_in = nullptr, *h_out = nullptr, *d_in = nullptr, *d_out = nullptr;
+  size_t cap_in = 0, cap_out = 0;  // doubles
+  void *ev[2] = {nullptr, nullptr};
+  int last_B = 0;
+};
+
+// bytes of LDS one instance's workgroup needs (the caller compares with the chip's 160 KB)
+size_t polish_many_lds_bytes(int n, int M);
+// queues the one launch on `stream` (a hipStream_t); returns the hipError_t of the launch as an int (0: queued)
+int polish_many_launch(const PolManyArgs &a, void *stream);
+
+}  // namespace miosqp

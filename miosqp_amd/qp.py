@@ -304,6 +304,47 @@ class OSQP(object):
             out.active = cls.astype(np.int64)
         return out
 
+    def polish_many(self, q, l, u, x, y, delta=1e-6, refine_iter=3, repair_iter=0):
+        """B polishes in ONE launch, one workgroup per instance (miosqp_qp_polish_many): q, x B x n (q None: the engine's
+        current linear cost for every instance), l, u, y B x M.  Instance b is answered as
+        `update(q=q[b])` + `polish(l[b], u[b], x[b], y[b], delta, refine_iter, repair_iter=repair_iter)` would, up to the
+        order of the sums, without touching the engine's q.  Returns a list of B records shaped like
+        `polish(..., repair_iter=)`'s, `active` included (device_time / run_time are the call's totals), or None when the
+        problem is beyond what one workgroup holds."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if x.ndim != 2:
+            raise ValueError("polish_many: instance-major arrays (B x n, B x M)")
+        B = x.shape[0]
+        l, u = np.ascontiguousarray(l, dtype=np.float64), np.ascontiguousarray(u, dtype=np.float64)
+        y = np.ascontiguousarray(y, dtype=np.float64)
+        q = None if q is None else np.ascontiguousarray(q, dtype=np.float64)
+        if x.shape != (B, self.n) or l.shape != (B, self.m) or u.shape != (B, self.m) or y.shape != (B, self.m) or \
+                (q is not None and q.shape != (B, self.n)):
+            raise ValueError("polish_many: instance-major arrays (B x n, B x M)")
+        xo, yo = np.empty((B, self.n)), np.empty((B, self.m))
+        infos = (_lib.PolishRepairInfo * max(B, 1))()
+        rc = self._lib.miosqp_qp_polish_many(self._h, B, None if q is None else _lib.as_d(q), _lib.as_d(l), _lib.as_d(u),
+                                             _lib.as_d(x), _lib.as_d(y), float(delta), int(refine_iter), int(repair_iter),
+                                             _lib.as_d(xo), _lib.as_d(yo), infos)
+        if rc == -5:
+            return None
+        _check(rc, "polish_many")
+        if rc == 1:
+            raise ValueError("Lower bound must be lower than or equal to upper bound")
+        out = []
+        for b in range(B):
+            rep, info = infos[b], infos[b].polish
+            cls = np.zeros(self.m, dtype=np.int8)
+            _check(self._lib.miosqp_qp_get_polish_many_classes(self._h, b, cls.ctypes.data_as(C.POINTER(C.c_int8))),
+                   "get_polish_many_classes")
+            out.append(types.SimpleNamespace(
+                x=xo[b].copy(), y=yo[b].copy(), accepted=bool(info.accepted), reason=info.reason, n_lower=info.n_lower,
+                n_upper=info.n_upper, pri_before=info.pri_before, dua_before=info.dua_before, pri_after=info.pri_after,
+                dua_after=info.dua_after, obj=info.obj, device_time=info.device_time, run_time=info.run_time,
+                rounds=rep.rounds, stop=rep.stop, n_added=rep.n_added, n_dropped=rep.n_dropped,
+                accepted0=bool(rep.accepted0), reason0=rep.reason0, active=cls.astype(np.int64)))
+        return out
+
     def polish_rounds(self):
         """Of the last polish call with repair_iter: per round (round 0 first, 21 entries, zeros for rounds not run) the
         device seconds up to the revision's counters, and the host's wait for them."""
