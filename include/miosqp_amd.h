@@ -345,7 +345,14 @@ typedef struct miosqp_tree_info {
 } miosqp_tree_info;
 
 /* l, u, x0, y0: the root node (M, M, n, M doubles); upper0 / x_inc0: incumbent from MIOSQP.set_x0 (x_inc0 NULL or
- * upper0 >= 1.7e308: none); tree_explor_rule, max_iter_bb: the B&B settings; branching_rule 0 is implied. */
+ * upper0 >= 1.7e308: none); tree_explor_rule, max_iter_bb: the B&B settings; branching_rule 0 is implied.
+ * tree_explor_rule: 0 depth first (the first deepest leaf); 1 the reference's default (depth first until an incumbent
+ * exists, then the leaf with the LARGEST inherited bound); 2 best bound: the open leaf with the SMALLEST inherited bound
+ * (the root's is -inf); 3 depth first until an incumbent exists -- x_inc0 counts from the first node --, then best bound.
+ * Ties go to the first leaf in list order under every rule (two siblings share their parent's bound, so under best bound
+ * ties are the normal case and this rule decides the tree); the rest of the list keeps its order.  Any other value:
+ * MIOSQP_EARG.  Under rule 2 many more leaves are alive at once than under depth first: info->overflow (more than 1024)
+ * is to be expected more often, and means what it always meant -- redo on the host. */
 int miosqp_qp_solve_tree(miosqp_qp_engine *e, const double *l, const double *u, const double *x0, const double *y0,
                          double upper0, const double *x_inc0, int32_t tree_explor_rule, int32_t max_iter_bb,
                          double *x_out, miosqp_tree_info *info);
@@ -355,7 +362,9 @@ int miosqp_qp_solve_tree(miosqp_qp_engine *e, const double *l, const double *u, 
  * every tree in ONE launch: workgroup (or wavefront, n + M <= 64) b runs instance b exactly as miosqp_qp_solve_tree would
  * after miosqp_qp_update_lin_cost(q_b).  All arrays are instance-major: q, x0, x_inc0, x_out B x n; l, u, y0 B x M;
  * upper0 B (>= 1.7e308: no incumbent; x_inc0 may be NULL when none has one); info B.  The engine's own linear cost and
- * bounds are not touched.  MIOSQP_EUNSUPPORTED as for miosqp_qp_solve_tree. */
+ * bounds are not touched.  MIOSQP_EUNSUPPORTED as for miosqp_qp_solve_tree.  tree_explor_rule 0 .. 3 and the tie rule
+ * as for miosqp_qp_solve_tree (rule 3: an instance with upper0 < 1.7e308 takes the best bound from its first node);
+ * overflow is per instance. */
 int miosqp_qp_solve_trees(miosqp_qp_engine *e, int32_t B, const double *q, const double *l, const double *u,
                           const double *x0, const double *y0, const double *upper0, const double *x_inc0,
                           int32_t tree_explor_rule, int32_t max_iter_bb, double *x_out, miosqp_tree_info *info);
@@ -402,7 +411,10 @@ int miosqp_qp_search_set_incumbent(miosqp_qp_engine *e, double upper, const doub
 int miosqp_qp_search_get_incumbent(miosqp_qp_engine *e, double *upper, double *x);
 /* solves nodes until the list is empty, max_nodes are done or budget_s seconds have passed (<= 0: no time limit).
  * The slot store grows by itself (the capacity of search_create is a starting size); MIOSQP_EFULL only when the
- * device has no memory left for it -- *info is filled with what was done up to then in that case too. */
+ * device has no memory left for it -- *info is filled with what was done up to then in that case too.
+ * tree_explor_rule 0 .. 3 as for miosqp_qp_solve_tree, with the same tie rule (the first leaf in list order); the leaf
+ * is chosen on the host between a record and the next mail, and an incumbent from miosqp_qp_search_set_incumbent counts
+ * for rules 1 and 3.  Any other value: MIOSQP_EARG. */
 int miosqp_qp_search_run(miosqp_qp_engine *e, int32_t tree_explor_rule, int64_t max_nodes, double budget_s,
                          miosqp_search_info *info);
 
@@ -579,6 +591,7 @@ int miosqp_qp_stream_take_leaf(miosqp_qp_engine *e, double *l_int, double *u_int
                                double *lower);
 int miosqp_qp_stream_set_incumbent(miosqp_qp_engine *e, double upper, const double *x);
 int miosqp_qp_stream_get_incumbent(miosqp_qp_engine *e, double *upper, double *x);
+/* tree_explor_rule 0 / 1 only (the best-bound rules 2 and 3 of miosqp_qp_solve_tree are not offered here: MIOSQP_EARG) */
 int miosqp_qp_stream_step(miosqp_qp_engine *e, int32_t tree_explor_rule, int32_t chunks, int32_t rounds,
                           int64_t max_nodes, miosqp_stream_info *info);
 

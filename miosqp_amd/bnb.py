@@ -124,6 +124,25 @@ def polish_repair_setting(settings):
     return int(it)
 
 
+def exploration_setting(settings):
+    """The exploration rule, checked (MIOSQP.setup calls this before anything is built).  0: depth first; 1: the
+    reference's default (depth first, then the largest bound); 2: best bound; 3: depth first until the first incumbent,
+    then best bound (Workspace.leaf_index)."""
+    rule = settings.get('tree_explor_rule', 1)
+    if rule not in (0, 1, 2, 3):
+        raise ValueError('Tree exploring strategy not recognized')
+    return rule
+
+
+def require_depth_first(settings, who):
+    """The leaf-pool streams and the sharded searches visit a wide frontier per round and keep the exploration rules 0
+    and 1: `who` (the search's name in the message) refuses the best-bound rules before anything is launched."""
+    rule = settings.get('tree_explor_rule', 1)
+    if rule in (2, 3):
+        raise ValueError("%s: tree_explor_rule 0 / 1 only (rule %d, best bound, runs in MIOSQP.solve and solve_many)"
+                         % (who, rule))
+
+
 def require_plain_search(settings, who, rule=True, heuristic=True, polish=True):
     """The searches beside MIOSQP.solve branch on the most fractional variable, run no primal heuristic and do not
     polish their incumbent: `who` (the search's name in the message) refuses the settings that ask for more."""
@@ -439,6 +458,7 @@ class Workspace(object):
     def __init__(self, data, settings, qp_settings=None, backend=None):
         self.data = data
         self.settings = settings
+        exploration_setting(settings)
         self.sb = branching_settings(settings, qp_settings)
         self.rf = heuristic_settings(settings, qp_settings)
         self.pol = polish_settings(settings)
@@ -520,11 +540,16 @@ class Workspace(object):
 
     # -- tree exploration ----------------------------------------------------------------
     def leaf_index(self, tree_explor_rule):
-        """Index of the next leaf (workspace.py:128-149; note argmax of `lower` in phase two)."""
-        if tree_explor_rule == 0 or (tree_explor_rule == 1 and np.isinf(self.upper_glob)):
+        """Index of the next leaf (workspace.py:128-149; note argmax of `lower` in phase two of rule 1).
+        Rule 2 is best bound: the leaf with the SMALLEST inherited `lower`, the first one on ties (np.argmin; two
+        siblings share their parent's bound, so the tie rule decides the tree).  Rule 3 dives like rule 0 until there
+        is an incumbent (from a node or from set_x0) and takes the best bound from then on."""
+        if tree_explor_rule == 0 or (tree_explor_rule in (1, 3) and np.isinf(self.upper_glob)):
             return int(np.argmax([lf.depth for lf in self.leaves]))
         if tree_explor_rule == 1:
             return int(np.argmax([lf.lower for lf in self.leaves]))
+        if tree_explor_rule in (2, 3):
+            return int(np.argmin([lf.lower for lf in self.leaves]))
         raise ValueError('Tree exploring strategy not recognized')
 
     def choose_leaf(self, tree_explor_rule):
@@ -1035,12 +1060,13 @@ class MIOSQP(object):
         """Small problems (the LDS-resident engine form; BASELINE config 4): the whole loop below runs inside ONE
         device launch with the same decisions (`miosqp_qp_solve_tree`, csrc/kernels_tree.inc); the host only sends
         the root and reads the outcome.  Falls through to the host loop when the engine does not cover the problem
-        (too large, no device digest) or the leaf list overflowed.  settings['device_tree'] = False keeps the host loop."""
+        (too large, no device digest) or the leaf list overflowed -- to be expected more often under tree_explor_rule 2,
+    which keeps many more leaves alive than depth first.  settings['device_tree'] = False keeps the host loop."""
         st = work.settings
         if not hasattr(work.solver, 'solve_tree') or getattr(work, '_no_tree', False) or not st.get('device_tree', True):
             self._solve_hosted(work)
             return
-        if st['branching_rule'] != 0 or work.rf['on'] or st['tree_explor_rule'] not in (0, 1) or len(work.leaves) != 1 \
+        if st['branching_rule'] != 0 or work.rf['on'] or st['tree_explor_rule'] not in (0, 1, 2, 3) or len(work.leaves) != 1 \
                 or work.iter_num != 1 or work.data.n_int == 0 or 'eps_abs' not in work.qp_settings \
                 or not st.get('device_digest', True):
             return
@@ -1052,6 +1078,7 @@ class MIOSQP(object):
             work._no_tree = True  # this engine form never will: do not ask again
             self._solve_hosted(work)
             return
+        work.tree_info = r.info  # the launch's own record (max_leaves, overflow, device_time): tests and probes read it
         if r.info.overflow:
             return  # more leaves alive than the launch holds: the host loop redoes the search from the root
         work.iter_num = r.info.nodes + 1
@@ -1073,7 +1100,7 @@ class MIOSQP(object):
         st = work.settings
         if not st.get('device_search', True) or not hasattr(work.solver, 'search_create'):
             return
-        if st['branching_rule'] != 0 or work.rf['on'] or st['tree_explor_rule'] not in (0, 1) or len(work.leaves) != 1 \
+        if st['branching_rule'] != 0 or work.rf['on'] or st['tree_explor_rule'] not in (0, 1, 2, 3) or len(work.leaves) != 1 \
                 or work.iter_num != 1 or work.data.n_int == 0 or 'eps_abs' not in work.qp_settings \
                 or not st.get('device_digest', True):
             return
@@ -1180,7 +1207,7 @@ class MIOSQP(object):
         n, m, M = data.n, data.m, data.m + data.n_int
         ok_engine = hasattr(work.solver, 'solve_trees') and st.get('device_tree', True) and st['branching_rule'] == 0 \
             and not work.rf['on'] \
-            and st['tree_explor_rule'] in (0, 1) and data.n_int > 0 and 'eps_abs' in work.qp_settings \
+            and st['tree_explor_rule'] in (0, 1, 2, 3) and data.n_int > 0 and 'eps_abs' in work.qp_settings \
             and st.get('device_digest', True) and not getattr(work, '_no_trees', False)
         Q, L, U = self._instance_vectors(instances)
         up = np.full(B, np.inf); XI = np.zeros((B, n)); any_inc = False
@@ -1209,6 +1236,7 @@ class MIOSQP(object):
                 work._no_trees = True
             else:
                 X, infos = r
+                work.trees_info = infos  # per instance, as work.tree_info
                 dt = time() - t0
                 redo = []
                 for k in range(B):

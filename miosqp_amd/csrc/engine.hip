@@ -1820,7 +1820,7 @@ int miosqp_qp_get_polish_stages(miosqp_qp_engine *e, double *seconds) {
 int miosqp_qp_solve_tree(miosqp_qp_engine *e, const double *l, const double *u, const double *x0, const double *y0,
                          double upper0, const double *x_inc0, int32_t tree_explor_rule, int32_t max_iter_bb,
                          double *x_out, miosqp_tree_info *info) {
-  if (!e || !l || !u || !x0 || !y0 || !x_out || !info || max_iter_bb < 1 || tree_explor_rule < 0 || tree_explor_rule > 1)
+  if (!e || !l || !u || !x0 || !y0 || !x_out || !info || max_iter_bb < 1 || tree_explor_rule < 0 || tree_explor_rule > 3)
     return MIOSQP_EARG;
   ENTER(e);
   if (!e->have_int || !e->d.digest) {
@@ -2026,7 +2026,7 @@ int miosqp_qp_solve_trees(miosqp_qp_engine *e, int32_t B, const double *q, const
                           const double *x0, const double *y0, const double *upper0, const double *x_inc0,
                           int32_t tree_explor_rule, int32_t max_iter_bb, double *x_out, miosqp_tree_info *info) {
   if (!e || B < 1 || !q || !l || !u || !x0 || !y0 || !upper0 || !x_out || !info || max_iter_bb < 1 || tree_explor_rule < 0 ||
-      tree_explor_rule > 1)
+      tree_explor_rule > 3)
     return MIOSQP_EARG;
   ENTER(e);
   if (!e->have_int || !e->d.digest) {

@@ -102,12 +102,17 @@ void search_prune(NodeSearch &S) {
 }
 
 // workspace.py:128-149: depth first (first deepest) -- always for rule 0, until there is an incumbent for rule 1,
-// then the leaf with the LARGEST inherited bound (sic), first one
+// then the leaf with the LARGEST inherited bound (sic), first one.  Rule 2 is best bound: the leaf with the SMALLEST
+// inherited bound, first one (np.argmin; siblings share their parent's bound, so ties are the normal case); rule 3
+// dives like rule 0 until there is an incumbent and takes the best bound from then on
 size_t search_choose(const NodeSearch &S, int rule) {
   size_t best = 0;
-  if (rule == 0 || !(S.upper < 1.7e308)) {
+  if (rule == 0 || (rule != 2 && !(S.upper < 1.7e308))) {
     for (size_t k = 1; k < S.open.size(); k++)
       if (S.depth[S.open[k]] > S.depth[S.open[best]]) best = k;
+  } else if (rule >= 2) {
+    for (size_t k = 1; k < S.open.size(); k++)
+      if (S.lower[S.open[k]] < S.lower[S.open[best]]) best = k;
   } else {
     for (size_t k = 1; k < S.open.size(); k++)
       if (S.lower[S.open[k]] > S.lower[S.open[best]]) best = k;
@@ -518,7 +523,7 @@ int miosqp_qp_search_get_incumbent(miosqp_qp_engine *e, double *upper, double *x
 // `budget_s` seconds have passed (<= 0: no time limit).
 int miosqp_qp_search_run(miosqp_qp_engine *e, int32_t tree_explor_rule, int64_t max_nodes, double budget_s,
                          miosqp_search_info *info) {
-  if (!e || !e->search || !info || tree_explor_rule < 0 || tree_explor_rule > 1) return MIOSQP_EARG;
+  if (!e || !e->search || !info || tree_explor_rule < 0 || tree_explor_rule > 3) return MIOSQP_EARG;
   ENTER(e);
   NodeSearch &S = *search_of(e);
   const double t0 = wall();

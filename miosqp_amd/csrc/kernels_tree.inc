@@ -60,7 +60,56 @@ __device__ __forceinline__ void tree_instance(Dev &d, TreeArgs &ta) {
 __host__ __device__ inline size_t tree_lds_doubles(int n, int M, bool wform) {
   // resident arrays + epilogue vectors (xf, xi: n; yf, rowbuf: M; prow: 2 n) + list (lower: CAP doubles; order, depth,
   // freelist: 3 CAP ints = 1.5 CAP doubles) + a few scalars
-  return resident_lds_doubles(n, M, wform) + 4 * (size_t)n + 2 * (size_t)M + (size_t)TREE_CAP * 5 / 2 + 16 + ((size_t)n + 1) / 2 + 1;
+  // (+ 16: the per-wavefront (value, position) pairs of the best-bound choice, first_min_wave)
+  return resident_lds_doubles(n, M, wform) + 4 * (size_t)n + 2 * (size_t)M + (size_t)TREE_CAP * 5 / 2 + 16 + 16 + ((size_t)n + 1) / 2 + 1;
+}
+
+// ------------------------------------------------------------------------------------------
+// The best-bound choice (tree_explor_rule 2, and 3 once an incumbent exists): the open leaf with the SMALLEST inherited
+// bound, the FIRST one in list order on ties (np.argmin; two siblings share their parent's bound, so ties are the
+// normal case and the tie rule decides the tree).  Under best bound the list is several times as long as under depth
+// first (up to TREE_CAP), and one thread walking it sits between every two nodes.  Every thread takes the positions
+// k = tid, tid + T, ... and keeps the pair (lf_lower[order[k]], k); pairs are reduced with "smaller value wins; on equal
+// values the smaller k wins", a total order, so the result is the same whatever the order of the reduction.
+// ------------------------------------------------------------------------------------------
+constexpr int TREE_NO_POS = 0x7fffffff;
+
+__device__ __forceinline__ void first_min_take(double &v, int &k, double ov, int ok) {
+  if (ov < v || (ov == v && ok < k)) { v = ov; k = ok; }
+}
+
+// this thread's pair over its positions of the list (ascending k: the strict comparison keeps the first)
+template <int T>
+__device__ __forceinline__ void first_min_scan(const double *lf_lower, const int *order, int count, int tid, double &v, int &k) {
+  v = 1.0 / 0.0;
+  k = TREE_NO_POS;
+  for (int q = tid; q < count; q += T) {
+    const double lv = lf_lower[order[q]];
+    if (lv < v || k == TREE_NO_POS) { v = lv; k = q; }
+  }
+}
+
+// across the wavefront: a butterfly, every lane ends with the winning pair
+__device__ __forceinline__ void first_min_wave(double &v, int &k) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const double ov = __shfl_xor(v, off, 64);
+    const int ok = __shfl_xor(k, off, 64);
+    first_min_take(v, k, ov, ok);
+  }
+}
+
+// order[best] leaves the list and the tail moves down by one, T positions at a time: every thread reads its element,
+// a barrier, every thread writes it one position lower (a round reads [base + 1, base + T] and writes [base, base + T):
+// nothing a later round reads).  Called by all T threads of the workgroup with the same best and count.
+template <int T>
+__device__ __forceinline__ void order_remove(int *order, int best, int count, int tid) {
+  for (int base = best; base + 1 < count; base += T) {
+    const int src = base + 1 + tid;
+    const int moved = src < count ? order[src] : 0;
+    __syncthreads();
+    if (src < count) order[src - 1] = moved;
+  }
 }
 
 __global__ __launch_bounds__(RES_THREADS) void k_tree(Dev d, TreeArgs ta) {
@@ -76,7 +125,9 @@ __global__ __launch_bounds__(RES_THREADS) void k_tree(Dev d, TreeArgs ta) {
   int *lf_depth = order + TREE_CAP;
   int *freelist = lf_depth + TREE_CAP;
   double *sc = reinterpret_cast<double *>(freelist + TREE_CAP);  // scalars shared by the workgroup
-  int *iiL = reinterpret_cast<int *>(sc + 16);                    // i_idx (thread 0 walks it for every node)
+  double *fm_v = sc + 16;                                         // best-bound choice: a pair per wavefront
+  int *fm_k = reinterpret_cast<int *>(fm_v + RES_WAVES);
+  int *iiL = reinterpret_cast<int *>(sc + 32);                    // i_idx (thread 0 walks it for every node)
   // sc[0] upper, sc[1] action, sc[2] slot, sc[3] status, sc[4] lower, sc[5] heur_obj, sc[6] nextvar, sc[7] child0, sc[8] child1
   const double rinv = d.rho_inv, sigma = d.sigma;
   const int unsolved = MIOSQP_QP_UNSOLVED;
@@ -121,10 +172,29 @@ __global__ __launch_bounds__(RES_THREADS) void k_tree(Dev d, TreeArgs ta) {
   }
   while (count > 0 && nodes + 1 < ta.max_nodes && !overflow) {
     // ---- choose_leaf (workspace.py:128-155): deepest leaf, or -- once an incumbent exists under rule 1 -- the leaf
-    //      with the LARGEST bound (sic); first index on ties; the rest of the list keeps its order
-    if (tid == 0) {
+    //      with the LARGEST bound (sic); first index on ties; the rest of the list keeps its order.  Rule 2, and rule 3
+    //      once an incumbent exists: the SMALLEST bound, by all threads (sc[0] was written before the last barrier)
+    const bool best_bound = ta.rule == 2 || (ta.rule == 3 && !isinf(sc[0]));
+    if (best_bound) {
+      double bv;
+      int bk;
+      first_min_scan<RES_THREADS>(lf_lower, order, count, tid, bv, bk);
+      first_min_wave(bv, bk);
+      if ((tid & 63) == 0) {
+        fm_v[tid >> 6] = bv;
+        fm_k[tid >> 6] = bk;
+      }
+      __syncthreads();
+      bv = fm_v[0];
+      bk = fm_k[0];
+#pragma unroll
+      for (int w = 1; w < RES_WAVES; w++) first_min_take(bv, bk, fm_v[w], fm_k[w]);
+      const int chosen = order[bk];  // (read by every thread before the barrier inside order_remove, or never overwritten)
+      order_remove<RES_THREADS>(order, bk, count, tid);
+      if (tid == 0) sc[2] = (double)chosen;
+    } else if (tid == 0) {
       const double upper = sc[0];
-      const bool by_depth = ta.rule == 0 || (ta.rule == 1 && isinf(upper));
+      const bool by_depth = ta.rule == 0 || isinf(upper);
       int best = 0;
       if (by_depth) {
         int bd = lf_depth[order[0]];
@@ -535,10 +605,19 @@ __global__ __launch_bounds__(64) void k_tree_w(Dev d, TreeArgs ta) {
     tl = now__;                                       \
   }
   while (count > 0 && nodes + 1 < ta.max_nodes && !overflow) {
-    // ---- choose_leaf ----
-    if (r == 0) {
+    // ---- choose_leaf (as k_tree; the best-bound choice inside the one wavefront) ----
+    const bool best_bound = ta.rule == 2 || (ta.rule == 3 && !isinf(sc[0]));
+    if (best_bound) {
+      double bv;
+      int bk;
+      first_min_scan<TW>(lf_lower, order, count, r, bv, bk);
+      first_min_wave(bv, bk);
+      const int chosen = order[bk];
+      order_remove<TW>(order, bk, count, r);
+      if (r == 0) sc[2] = (double)chosen;
+    } else if (r == 0) {
       const double upper = sc[0];
-      const bool by_depth = ta.rule == 0 || (ta.rule == 1 && isinf(upper));
+      const bool by_depth = ta.rule == 0 || isinf(upper);
       int best = 0;
       if (by_depth) {
         int bd = lf_depth[order[0]];

@@ -216,6 +216,7 @@ class ShardedSearch(object):
 
     def __init__(self, model, comm=None):
         bnb.require_plain_search(model.work.settings, "sharded search", rule=False)
+        bnb.require_depth_first(model.work.settings, "sharded search")
         self.model = model
         self.work = model.work
         self.comm = comm if comm is not None else LocalComm()
@@ -573,6 +574,7 @@ class ShardedStream(object):
         its step() is called with (HostedSearch: nodes=, budget=)."""
         from miosqp_amd import stream
         bnb.require_plain_search(model.work.settings, "sharded stream")
+        bnb.require_depth_first(model.work.settings, "sharded stream")
         self.model, self.work = model, model.work
         self.comm = comm if comm is not None else LocalComm()
         self.seq = ShardedSearch(model, self.comm)  # replicated ramp-up (its _visit / _agree / counters)

@@ -31,8 +31,8 @@ class HostedSearch(object):
         self.eng = w.solver
         if not hasattr(self.eng, "search_create"):
             raise RuntimeError("the engine has no hosted search (miosqp_qp_search_*)")
-        if w.settings['branching_rule'] != 0 or w.settings['tree_explor_rule'] not in (0, 1):
-            raise ValueError("hosted search: branching_rule 0 and tree_explor_rule 0 / 1 only")
+        if w.settings['branching_rule'] != 0 or w.settings['tree_explor_rule'] not in (0, 1, 2, 3):
+            raise ValueError("hosted search: branching_rule 0 and tree_explor_rule 0 .. 3 only")
         bnb.require_plain_search(w.settings, "hosted search", rule=False, polish=not owned)  # (MIOSQP.solve polishes after its own)
         self.p = w.data.n_int
         if capacity is None:

@@ -142,6 +142,7 @@ class StreamSearch(object):
         if not hasattr(self.eng, "pool_create"):
             raise TypeError("the streaming search needs the HIP engine (miosqp_amd.qp)")
         bnb.require_plain_search(w.settings, "streaming search")
+        bnb.require_depth_first(w.settings, "streaming search")
         self.columns = int(columns)
         self.p = w.data.n_int
         # every column dives on its own, and until the first incumbent nothing can be pruned: on config 2 the first
@@ -417,6 +418,7 @@ class NativeStreamSearch(object):
         if not hasattr(self.eng, "stream_create"):
             raise TypeError("the native streaming search needs the HIP engine (miosqp_amd.qp)")
         bnb.require_plain_search(w.settings, "streaming search")
+        bnb.require_depth_first(w.settings, "streaming search")
         if w.settings['tree_explor_rule'] not in (0, 1):
             raise ValueError('Tree exploring strategy not recognized')
         self.columns, self.p, self.rounds = int(columns), w.data.n_int, int(rounds)
