@@ -171,6 +171,17 @@ int miosqp_qp_solve_batch(miosqp_qp_engine *e, int32_t B, const double *l, const
                           const double *x0, const double *y0, double *x_out, double *y_out,
                           miosqp_qp_info *info);
 
+/* One MIQP per column: solve_batch with a linear cost of its own in every column, q [B][n] raw costs (node-major like the
+ * other arrays).  Replaces, per column, solver.update(q=q) of the reference's MIOSQP.update_vectors
+ * (miosqp/solver.py:183-185) followed by the update / warm_start / solve of its Node.solve
+ * (miosqp/node.py:102-108): column k is what the engine computes after miosqp_qp_update_lin_cost(q_k) and
+ * miosqp_qp_solve_node(l_k, u_k, x0_k, y0_k).  The engine's own q is neither read nor written.  Everything else --
+ * slices of max_batch columns, compaction, digest, epilogue, the refusal while pool chunks are in flight -- is
+ * miosqp_qp_solve_batch's.  The cost arrays are allocated on the first call. */
+int miosqp_qp_solve_batch_q(miosqp_qp_engine *e, int32_t B, const double *q, const double *l, const double *u,
+                            const double *x0, const double *y0, double *x_out, double *y_out,
+                            miosqp_qp_info *info);
+
 /* ---- strong branching: the 2K children of one node solved together and scored on the device ----------------
  * For K candidates (ascending positions in i_idx, 1 <= K <= 32) of a solved parent (l, u: its bounds; x, y: its
  * clamped x and its y), child k (down) has u[m + cand[k]] = floor(x[i_idx[cand[k]]]) and child K + k (up) has

@@ -118,6 +118,8 @@ SYMBOLS = {
     "miosqp_qp_stream_step": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.POINTER(StreamInfo)]),
     "miosqp_qp_solve_batch": (C.c_int, [C.c_void_p, C.c_int32, dp, dp, dp, dp, dp, dp,
                                         C.POINTER(Info)]),
+    "miosqp_qp_solve_batch_q": (C.c_int, [C.c_void_p, C.c_int32, dp, dp, dp, dp, dp, dp, dp,
+                                          C.POINTER(Info)]),
     "miosqp_qp_solve_tree": (C.c_int, [C.c_void_p, dp, dp, dp, dp, C.c_double, dp, C.c_int32, C.c_int32, dp,
                                        C.POINTER(TreeInfo)]),
     "miosqp_qp_pool_create": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),

@@ -1183,7 +1183,7 @@ class MIOSQP(object):
                 res['polished'] = True
         return results
 
-    def solve_many(self, instances, polish=False):
+    def solve_many(self, instances, polish=False, lockstep=None):
         """B MIQPs on this model's factorisation, solved TOGETHER: instance k is what
         `update_vectors(q=, l=, u=)` [+ `set_x0(x0)`] + `solve()` would solve (the reference's MPC pattern,
         /root/reference/miosqp/solver.py:174-212, examples/power_converter/power_converter.py:467-476), for a list of
@@ -1195,6 +1195,22 @@ class MIOSQP(object):
         fallback puts q, l, u, the leaf list and the statistics back when it is done or when an instance raises (leaves of
         an unfinished device-hosted search are placeholders and not resumable either way).
         Returns a list of dicts: x, upper_glob, status, nodes, osqp_iter, run_time.
+
+        lockstep: what happens beyond the one-launch trees (a tree must fit one workgroup there, n + M <= 192).  The
+        lock-step driver (miosqp_amd/lockstep.py) advances all B trees together, one node of every unfinished tree per
+        wave, the wave being ONE `solve_batch_q` -- the engine's lock-step batch with a linear cost per column -- and
+        every tree running the unchanged `bound_and_branch` on its own leaf list, incumbent and data view; each tree
+        makes the decisions of its sequential solve, node for node, and the dicts are formed the same way (run_time:
+        elapsed / B).  None (default): once the one-launch path has declined (no `solve_trees`, or it returned None),
+        the driver runs if the solver has `solve_batch_q`, branching_rule is 0 and primal_heuristic is 0; otherwise, and
+        on every backend without `solve_batch_q` (the CPU oracle), the sequential path as before.  False: always the
+        sequential path.  True: the driver on any backend (ValueError for another branching rule or a primal heuristic);
+        without `solve_batch_q` a wave is solved column by column on the model's solver (`update(q=)` + `Node.solve`)
+        and the solver's q is put back afterwards.  `work.lockstep` holds the last run's record (instances, waves,
+        nodes, batched, ADMM iterations per wave).  The model is left as it was, also when an instance raises.
+        Measured at n 500, m 1000, p 250: 3.4 x the sequential path at 256 instances and rho 0.1, 1.6 x at
+        rho "auto", even at about 32-64 instances and SLOWER below (a narrow wave costs what a wide one costs): with
+        few instances pass lockstep=False.
 
         polish=True: the incumbents are then polished together by `polish_many` (one more launch on the HIP engine) and
         every dict gains polished, polish_rounds, pri_after, dua_after.  Polishing many instances is asked for per call:
@@ -1228,6 +1244,7 @@ class MIOSQP(object):
                     print('Invalid initial solution!\n')
         out = [None] * B
         redo = list(range(B))
+        declined = True  # the one-launch path: absent, switched off, or it returned None
         if ok_engine:
             t0 = time()
             r = work.solver.solve_trees(Q, L, U, np.zeros((B, n)), np.zeros((B, M)), up, XI if any_inc else None,
@@ -1239,6 +1256,7 @@ class MIOSQP(object):
                 work.trees_info = infos  # per instance, as work.tree_info
                 dt = time() - t0
                 redo = []
+                declined = False
                 for k in range(B):
                     info = infos[k]
                     if info.overflow:
@@ -1259,6 +1277,15 @@ class MIOSQP(object):
                         x[data.i_idx] = np.round(x[data.i_idx])
                     out[k] = dict(x=x, upper_glob=upper, status=status, nodes=int(info.nodes),
                                   osqp_iter=int(info.osqp_iter), run_time=dt / B)
+        if redo and lockstep is not False:
+            from miosqp_amd import lockstep as ls
+            batched = hasattr(work.solver, 'solve_batch_q')
+            if lockstep and not ls.supported(work):
+                raise ValueError('solve_many(lockstep=True) needs branching_rule 0, primal_heuristic 0 and '
+                                 'tree_explor_rule 0-3')
+            if lockstep or (declined and batched and ls.supported(work)):
+                ls.run(self, redo, Q, L, U, up, XI, instances, out, batched)
+                redo = []
         if redo:
             # sequential path on a copy of the model's vectors, restored afterwards
             q_keep, l_keep, u_keep = data.q, data.l[:m].copy(), data.u[:m].copy()

@@ -189,6 +189,10 @@ struct Dev {
   double *b_out;            // node-major staging out: x[B][n] | y[B][M]
   int *c_done, *c_status, *c_iter;
   double *c_pri, *c_dua, *c_obj, *c_lower;
+  // ---- one linear cost per column (miosqp_qp_solve_batch_q; allocated on its first call) ----
+  double *b_q;     // scaled costs, [n][Bs] batch-fastest: what the <PQ = true> kernels read where the others read q
+  double *b_qs;    // the same instance-major [B][n], as k_scale_q_batch leaves them (kb_prepare lays them out)
+  double *b_qraw;  // raw costs, instance-major [B][n] (kb_obj_rows, through c_node)
 };
 
 struct SearchDigest {  // coherent host memory
@@ -248,7 +252,7 @@ namespace {
 // the dynamic-LDS ceiling of a kernel is a property of (process, device, kernel): raised to the chip's 160 KB once instead of
 // at every set-up (the call costs ~40 us, a fifth of a small problem's set-up)
 hipError_t lds_limit_once(const void *fn, int which) {
-  static bool done[12][64] = {};
+  static bool done[14][64] = {};
   int dev = 0;
   hipError_t rc = hipGetDevice(&dev);
   if (rc != hipSuccess) return rc;
@@ -638,15 +642,11 @@ int miosqp_qp_cleanup(miosqp_qp_engine *e) {
   if (e->hb_out) hipHostFree(e->hb_out);
   if (e->hb_int) hipHostFree(e->hb_int);
   if (e->hb_dbl) hipHostFree(e->hb_dbl);
+  if (e->hb_q) hipHostFree(e->hb_q);
   if (e->h_der) hipHostFree(e->h_der);
   polish_free(e);
   polish_many_free(e);
-  for (int k = 0; k < 16; k++) {
-    if (e->xb_full[k]) hipGraphExecDestroy(e->xb_full[k]);
-    if (e->xb_tail[k]) hipGraphExecDestroy(e->xb_tail[k]);
-    if (e->gb_full[k]) hipGraphDestroy(e->gb_full[k]);
-    if (e->gb_tail[k]) hipGraphDestroy(e->gb_tail[k]);
-  }
+  drop_chunk_graphs(e);
   rt_release(e->rt);  // stream, events and pinned staging go back to the per-process cache
   delete e;
   return 0;
@@ -1441,6 +1441,35 @@ int miosqp_qp_solve_batch(miosqp_qp_engine *e, int32_t B, const double *l, const
     const int nb = B - s0 < e->Bcap ? B - s0 : e->Bcap;
     int rc = solve_slice(e, nb, l + s0 * M, u + s0 * M, x0 + s0 * n, y0 + s0 * M, x_out + s0 * n, y_out + s0 * M,
                          info + s0);
+    if (rc) return rc;
+  }
+  return 0;
+}
+
+// One MIQP per column: the lock-step solve of solve_batch with a linear cost of its own in every column (B x n raw costs,
+// instance-major).  The engine's own q is neither read nor written.
+int miosqp_qp_solve_batch_q(miosqp_qp_engine *e, int32_t B, const double *q, const double *l, const double *u,
+                            const double *x0, const double *y0, double *x_out, double *y_out, miosqp_qp_info *info) {
+  if (!e || B < 0 || (B > 0 && (!q || !l || !u || !x0 || !y0 || !x_out || !y_out || !info))) return MIOSQP_EARG;
+  ENTER(e);
+  if (!e->have_int) {
+    g_err = "solve_batch_q: call miosqp_qp_set_integer_rows first";
+    return MIOSQP_EARG;
+  }
+  const size_t n = e->n, M = e->M;
+  for (size_t k = 0; k < (size_t)B * M; k++)
+    if (l[k] > u[k]) return MIOSQP_EBOUNDS;
+  if (int rc = ensure_batch(e)) return rc;
+  if (int rc = ensure_batch_q(e)) return rc;
+  struct PqScope {  // every launch helper and the chunk-graph cache look at e->pq; off again on every way out
+    miosqp_qp_engine *e;
+    explicit PqScope(miosqp_qp_engine *e_) : e(e_) { e->pq = 1; }
+    ~PqScope() { e->pq = 0; }
+  } scope(e);
+  for (int s0 = 0; s0 < B; s0 += e->Bcap) {
+    const int nb = B - s0 < e->Bcap ? B - s0 : e->Bcap;
+    int rc = solve_slice(e, nb, l + s0 * M, u + s0 * M, x0 + s0 * n, y0 + s0 * M, x_out + s0 * n, y_out + s0 * M,
+                         info + s0, q + s0 * n);
     if (rc) return rc;
   }
   return 0;
@@ -2506,7 +2535,7 @@ int miosqp_qp_time_kernel(miosqp_qp_engine *e, int32_t which, int32_t reps, doub
       return;
     }
     switch (which) {
-      case 10: hipLaunchKernelGGL(kb_panel_fwd, dim3((d.n + 3) / 4, ntiles), dim3(256), 0, e->stream, d); break;
+      case 10: hipLaunchKernelGGL(kb_panel_fwd<false>, dim3((d.n + 3) / 4, ntiles), dim3(256), 0, e->stream, d); break;
       case 11: hipLaunchKernelGGL(kb_tail_fwd, dim3((d.n + 3) / 4, ntiles), dim3(256), 0, e->stream, d); break;
       case 12: hipLaunchKernelGGL(kb_tail_bwd, dim3((d.n + 3) / 4, ntiles), dim3(256), 0, e->stream, d); break;
       case 13: hipLaunchKernelGGL(kb_panel_bwd, dim3((d.M + 3) / 4, ntiles), dim3(256), 0, e->stream, d); break;

@@ -181,8 +181,11 @@ struct miosqp_qp_engine {
   std::vector<double> A_raw;
   PolishScratch *pol = nullptr;
   miosqp::PolManyScratch *polm = nullptr;  // polishing of many instances in one launch (miosqp_qp_polish_many)
-  hipGraphExec_t xb_full[16] = {}, xb_tail[16] = {};
-  hipGraph_t gb_full[16] = {}, gb_tail[16] = {};
+  // captured chunks per tile count; set [1] holds the per-column-cost instantiations (solve_batch_q), set [0] the others
+  hipGraphExec_t xb_full[2][16] = {}, xb_tail[2][16] = {};
+  hipGraph_t gb_full[2][16] = {}, gb_tail[2][16] = {};
+  int pq = 0;                 // 1 while a solve_batch_q slice is queued: launches and chunk graphs take the <PQ = true> kernels
+  double *hb_q = nullptr;     // pinned staging of a slice's raw costs (solve_batch_q, allocated on its first call)
   bool compact = true;   // compaction of converged columns in solve_batch (MIOSQP_COMPACT=0 disables)
   int64_t compactions = 0;
   double bloop_ms = 0.0;
@@ -1244,6 +1247,19 @@ void maybe_rejoin_coop(miosqp_qp_engine *e) {
 }
 
 // ---- batched mode (host) -------------------------------------------------------------------
+// the captured chunks of both sets (they hold the iteration kernels and Dev by value); the stream must be idle
+void drop_chunk_graphs(miosqp_qp_engine *e) {
+  for (int s = 0; s < 2; s++)
+    for (int k = 0; k < 16; k++) {
+      if (e->xb_full[s][k]) hipGraphExecDestroy(e->xb_full[s][k]);
+      if (e->xb_tail[s][k]) hipGraphExecDestroy(e->xb_tail[s][k]);
+      if (e->gb_full[s][k]) hipGraphDestroy(e->gb_full[s][k]);
+      if (e->gb_tail[s][k]) hipGraphDestroy(e->gb_tail[s][k]);
+      e->xb_full[s][k] = e->xb_tail[s][k] = nullptr;
+      e->gb_full[s][k] = e->gb_tail[s][k] = nullptr;
+    }
+}
+
 // which: 0 forward sweep, 1 backward sweep; workgroup shape from e->bd_cfg (row groups x k slices)
 void launch_bd(miosqp_qp_engine *e, int ntiles, int which) {
   const Dev &d = e->d;
@@ -1251,7 +1267,11 @@ void launch_bd(miosqp_qp_engine *e, int ntiles, int which) {
     const int nbx = (d.n + 15) / 16, nbc = (d.wh_m + 15) / 16, ncol = ntiles * (64 / BM_COLS);
     // e->bm_var (MIOSQP_BM_VAR = 10 * forward + backward): waves per workgroup x pipeline depth, see the table
 #define BMF(KS, DP) hipLaunchKernelGGL((kbm_fwd<KS, DP>), dim3(bm_grid(nbx, ncol)), dim3(KS * 64), 0, e->stream, d, ncol)
-#define BMB(KS, DP) hipLaunchKernelGGL((kbm_bwd<KS, DP>), dim3(bm_grid(nbx + nbc, ncol)), dim3(KS * 64), 0, e->stream, d, ncol)
+#define BMB(KS, DP)                                                                                                             \
+  do {                                                                                                                          \
+    if (e->pq) hipLaunchKernelGGL((kbm_bwd<KS, DP, true>), dim3(bm_grid(nbx + nbc, ncol)), dim3(KS * 64), 0, e->stream, d, ncol); \
+    else hipLaunchKernelGGL((kbm_bwd<KS, DP>), dim3(bm_grid(nbx + nbc, ncol)), dim3(KS * 64), 0, e->stream, d, ncol);            \
+  } while (0)
     if (which == 0) {
       switch (e->bm_var / 10) {
         case 1: BMF(8, 6); break;
@@ -1280,6 +1300,7 @@ void launch_bd(miosqp_qp_engine *e, int ntiles, int which) {
     constexpr int R = BdCfg<RG, KS>::ROWS, T = BdCfg<RG, KS>::THREADS;                                      \
     const int nbx = (d.n + R - 1) / R, nbc = (d.M + R - 1) / R;                                            \
     if (which == 0) hipLaunchKernelGGL((kbd_fwd<RG, KS>), dim3(nbx, ntiles), dim3(T), 0, e->stream, d);      \
+    else if (e->pq) hipLaunchKernelGGL((kbd_bwd<RG, KS, true>), dim3(nbx + nbc, ntiles), dim3(T), 0, e->stream, d); \
     else hipLaunchKernelGGL((kbd_bwd<RG, KS>), dim3(nbx + nbc, ntiles), dim3(T), 0, e->stream, d);           \
   } while (0)
   switch (e->bd_cfg) {
@@ -1304,7 +1325,9 @@ void launch_kbp(miosqp_qp_engine *e, const Dev &d, int ntiles, int iters, bool p
   const bool one = ka.ncol <= KBP_G && !getenv("MIOSQP_KBP_GENERAL");  // one tile per group: the iterates stay in registers
   const size_t lds = KBP_LDS_DOUBLES * sizeof(double);
   ChipGuard turn(e);
-  if (one && prof) hipLaunchKernelGGL(kbp1<true>, dim3(KBP_WGS), dim3(512), lds, e->stream, d, ka);
+  if (e->pq && one) hipLaunchKernelGGL((kbp1<false, true>), dim3(KBP_WGS), dim3(512), lds, e->stream, d, ka);  // (no profiled form)
+  else if (e->pq) hipLaunchKernelGGL((kbp<false, true>), dim3(KBP_WGS), dim3(512), lds, e->stream, d, ka);
+  else if (one && prof) hipLaunchKernelGGL(kbp1<true>, dim3(KBP_WGS), dim3(512), lds, e->stream, d, ka);
   else if (one) hipLaunchKernelGGL(kbp1<false>, dim3(KBP_WGS), dim3(512), lds, e->stream, d, ka);
   else if (prof) hipLaunchKernelGGL(kbp<true>, dim3(KBP_WGS), dim3(512), lds, e->stream, d, ka);
   else hipLaunchKernelGGL(kbp<false>, dim3(KBP_WGS), dim3(512), lds, e->stream, d, ka);
@@ -1328,6 +1351,8 @@ int kbp_setup(miosqp_qp_engine *e, int want) {
   HIPCHK(lds_limit_once((const void *)kbp<true>, 6));
   HIPCHK(lds_limit_once((const void *)kbp1<false>, 7));
   HIPCHK(lds_limit_once((const void *)kbp1<true>, 8));
+  HIPCHK(lds_limit_once((const void *)kbp<false, true>, 11));
+  HIPCHK(lds_limit_once((const void *)kbp1<false, true>, 12));
   int per_cu = 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kbp<false>, 512, KBP_LDS_DOUBLES * sizeof(double)) != hipSuccess || per_cu < 1)
     return 0;
@@ -1350,14 +1375,7 @@ int kbp_leave(miosqp_qp_engine *e) {
   e->kbp_retry_gap = e->kbp_retry_gap ? std::min<int64_t>(2 * e->kbp_retry_gap, 1 << 14) : 64;
   e->kbp_retry_in = e->kbp_retry_gap;
   HIPCHK(hipStreamSynchronize(e->stream));
-  for (int k = 0; k < 16; k++) {
-    if (e->xb_full[k]) hipGraphExecDestroy(e->xb_full[k]);
-    if (e->xb_tail[k]) hipGraphExecDestroy(e->xb_tail[k]);
-    if (e->gb_full[k]) hipGraphDestroy(e->gb_full[k]);
-    if (e->gb_tail[k]) hipGraphDestroy(e->gb_tail[k]);
-    e->xb_full[k] = e->xb_tail[k] = nullptr;
-    e->gb_full[k] = e->gb_tail[k] = nullptr;
-  }
+  drop_chunk_graphs(e);
   drop_stream_graph(e);
   HIPCHK(hipMemsetAsync(&e->d.ctrl->pad, 0, sizeof(int), e->stream));
   HIPCHK(hipMemsetAsync(e->kbpa.reg + 32, 0, sizeof(unsigned long long), e->stream));
@@ -1372,14 +1390,7 @@ int maybe_rejoin_kbp(miosqp_qp_engine *e, int64_t n) {
   if (e->kbp_retry_in > 0) return 0;
   e->kbp_retry_in = 0;
   HIPCHK(hipStreamSynchronize(e->stream));
-  for (int k = 0; k < 16; k++) {  // (the captured chunks hold the launches)
-    if (e->xb_full[k]) hipGraphExecDestroy(e->xb_full[k]);
-    if (e->xb_tail[k]) hipGraphExecDestroy(e->xb_tail[k]);
-    if (e->gb_full[k]) hipGraphDestroy(e->gb_full[k]);
-    if (e->gb_tail[k]) hipGraphDestroy(e->gb_tail[k]);
-    e->xb_full[k] = e->xb_tail[k] = nullptr;
-    e->gb_full[k] = e->gb_tail[k] = nullptr;
-  }
+  drop_chunk_graphs(e);  // (the captured chunks hold the launches)
   drop_stream_graph(e);
   e->kbp = true;
   return 0;
@@ -1392,7 +1403,8 @@ void launch_iteration_b(miosqp_qp_engine *e, int ntiles) {
     launch_bd(e, ntiles, 1);
     return;
   }
-  hipLaunchKernelGGL(kb_panel_fwd, dim3((d.n + 3) / 4, ntiles), dim3(256), 0, e->stream, d);
+  if (e->pq) hipLaunchKernelGGL(kb_panel_fwd<true>, dim3((d.n + 3) / 4, ntiles), dim3(256), 0, e->stream, d);
+  else hipLaunchKernelGGL(kb_panel_fwd<false>, dim3((d.n + 3) / 4, ntiles), dim3(256), 0, e->stream, d);
   hipLaunchKernelGGL(kb_tail_fwd, dim3((d.n + 3) / 4, ntiles), dim3(256), 0, e->stream, d);
   hipLaunchKernelGGL(kb_tail_bwd, dim3((d.n + 3) / 4, ntiles), dim3(256), 0, e->stream, d);
   hipLaunchKernelGGL(kb_panel_bwd, dim3((d.M + 3) / 4, ntiles), dim3(256), 0, e->stream, d);
@@ -1417,7 +1429,8 @@ int capture_chunk_b(miosqp_qp_engine *e, int iters, int ntiles, hipGraph_t *g, h
     hipLaunchKernelGGL(kb_check_con, dim3((d.M + 3) / 4, ntiles), dim3(256), 0, e->stream, d);
     hipLaunchKernelGGL(kb_check_var, dim3(2 * ((d.n + 3) / 4), ntiles), dim3(256), 0, e->stream, d);
   }
-  hipLaunchKernelGGL(kb_check_reduce, dim3(ntiles, KR), dim3(256), 0, e->stream, d);
+  if (e->pq) hipLaunchKernelGGL(kb_check_reduce<true>, dim3(ntiles, KR), dim3(256), 0, e->stream, d);
+  else hipLaunchKernelGGL(kb_check_reduce<false>, dim3(ntiles, KR), dim3(256), 0, e->stream, d);
   hipLaunchKernelGGL(kb_check_decide, dim3(ntiles), dim3(256), 0, e->stream, d);
   e->in_capture = false;
   HIPCHK(hipStreamEndCapture(e->stream, g));
@@ -1486,10 +1499,10 @@ int slice_begin(miosqp_qp_engine *e, int B) {
   if (e->pool_pending) { g_err = "solve_batch: streaming chunks are still in flight (pool_collect first)"; return MIOSQP_EARG; }
   e->pool_dirty = true;
   if (int rcj = maybe_rejoin_kbp(e, 8)) return rcj;
-  if (!e->xb_full[ntiles - 1]) {
-    int rc = capture_chunk_b(e, e->chunk, ntiles, &e->gb_full[ntiles - 1], &e->xb_full[ntiles - 1]);
+  if (!e->xb_full[e->pq][ntiles - 1]) {
+    int rc = capture_chunk_b(e, e->chunk, ntiles, &e->gb_full[e->pq][ntiles - 1], &e->xb_full[e->pq][ntiles - 1]);
     if (!rc && e->tail_iters > 0)
-      rc = capture_chunk_b(e, e->tail_iters, ntiles, &e->gb_tail[ntiles - 1], &e->xb_tail[ntiles - 1]);
+      rc = capture_chunk_b(e, e->tail_iters, ntiles, &e->gb_tail[e->pq][ntiles - 1], &e->xb_tail[e->pq][ntiles - 1]);
     if (rc) return rc;
   }
   return 0;
@@ -1505,7 +1518,8 @@ int slice_run(miosqp_qp_engine *e, int B, int max_iter) {
   const int ntiles = (B + 63) / 64;
   hipLaunchKernelGGL(kb_reset, dim3((d.Bs + 255) / 256), dim3(256), 0, e->stream, d, B);
   const int big = (int)(n > M ? n : M);
-  hipLaunchKernelGGL(kb_prepare, dim3((big + 3) / 4, ntiles), dim3(256), 0, e->stream, d, B);
+  if (e->pq) hipLaunchKernelGGL(kb_prepare<true>, dim3((big + 3) / 4, ntiles), dim3(256), 0, e->stream, d, B);
+  else hipLaunchKernelGGL(kb_prepare<false>, dim3((big + 3) / 4, ntiles), dim3(256), 0, e->stream, d, B);
   hipLaunchKernelGGL(kb_warm_z, dim3((d.M + 3) / 4, ntiles), dim3(256), 0, e->stream, d);
   const int nfull = max_iter / e->chunk;
   const bool tail = max_iter == e->st.max_iter && e->tail_iters > 0;
@@ -1516,7 +1530,7 @@ int slice_run(miosqp_qp_engine *e, int B, int max_iter) {
     HIPCHK(hipEventRecord(e->evc0, e->stream));
     {
       ChipGuard turn(e);  // (the captured chunk may hold a whole-chip launch)
-      HIPCHK(hipGraphLaunch(e->xb_full[cur - 1], e->stream));
+      HIPCHK(hipGraphLaunch(e->xb_full[e->pq][cur - 1], e->stream));
     }
     HIPCHK(hipEventRecord(e->evc1, e->stream));
     HIPCHK(hipMemcpyAsync(e->h_ctrl, d.ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost, e->stream));
@@ -1535,8 +1549,8 @@ int slice_run(miosqp_qp_engine *e, int B, int max_iter) {
       e->bloop_iters -= e->chunk;
       e->bloop_node_iters -= (int64_t)e->chunk * (B - decided);
       int rc = kbp_leave(e);
-      if (!rc) rc = capture_chunk_b(e, e->chunk, cur, &e->gb_full[cur - 1], &e->xb_full[cur - 1]);
-      if (!rc && e->tail_iters > 0) rc = capture_chunk_b(e, e->tail_iters, cur, &e->gb_tail[cur - 1], &e->xb_tail[cur - 1]);
+      if (!rc) rc = capture_chunk_b(e, e->chunk, cur, &e->gb_full[e->pq][cur - 1], &e->xb_full[e->pq][cur - 1]);
+      if (!rc && e->tail_iters > 0) rc = capture_chunk_b(e, e->tail_iters, cur, &e->gb_tail[e->pq][cur - 1], &e->xb_tail[e->pq][cur - 1]);
       if (rc) return rc;
       k--;
       continue;
@@ -1565,13 +1579,14 @@ int slice_run(miosqp_qp_engine *e, int B, int max_iter) {
       if (np > 0) {
         HIPCHK(hipMemcpyAsync(d.c_pairs, pairs, sizeof(int) * 2 * np, hipMemcpyHostToDevice, e->stream));
         const int rows = (int)(M + n);
-        hipLaunchKernelGGL(kb_swap_cols, dim3((rows + 255) / 256, np), dim3(256), 0, e->stream, d, np);
+        if (e->pq) hipLaunchKernelGGL(kb_swap_cols<true>, dim3((rows + 255) / 256, np), dim3(256), 0, e->stream, d, np);
+        else hipLaunchKernelGGL(kb_swap_cols<false>, dim3((rows + 255) / 256, np), dim3(256), 0, e->stream, d, np);
       }
       cur = want;
-      if (!e->xb_full[cur - 1]) {
-        int rc = capture_chunk_b(e, e->chunk, cur, &e->gb_full[cur - 1], &e->xb_full[cur - 1]);
+      if (!e->xb_full[e->pq][cur - 1]) {
+        int rc = capture_chunk_b(e, e->chunk, cur, &e->gb_full[e->pq][cur - 1], &e->xb_full[e->pq][cur - 1]);
         if (!rc && e->tail_iters > 0)
-          rc = capture_chunk_b(e, e->tail_iters, cur, &e->gb_tail[cur - 1], &e->xb_tail[cur - 1]);
+          rc = capture_chunk_b(e, e->tail_iters, cur, &e->gb_tail[e->pq][cur - 1], &e->xb_tail[e->pq][cur - 1]);
         if (rc) return rc;
       }
       e->compactions++;
@@ -1582,7 +1597,7 @@ int slice_run(miosqp_qp_engine *e, int B, int max_iter) {
     // launch that was called off iterated nothing and its test decided nothing, so the tail is redone as launches
     {
       ChipGuard turn(e);
-      HIPCHK(hipGraphLaunch(e->xb_tail[cur - 1], e->stream));
+      HIPCHK(hipGraphLaunch(e->xb_tail[e->pq][cur - 1], e->stream));
     }
     HIPCHK(hipMemcpyAsync(e->h_ctrl, d.ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
@@ -1592,13 +1607,14 @@ int slice_run(miosqp_qp_engine *e, int B, int max_iter) {
       return MIOSQP_EHIP;
     }
     int rc = kbp_leave(e);
-    if (!rc) rc = capture_chunk_b(e, e->chunk, cur, &e->gb_full[cur - 1], &e->xb_full[cur - 1]);
-    if (!rc) rc = capture_chunk_b(e, e->tail_iters, cur, &e->gb_tail[cur - 1], &e->xb_tail[cur - 1]);
+    if (!rc) rc = capture_chunk_b(e, e->chunk, cur, &e->gb_full[e->pq][cur - 1], &e->xb_full[e->pq][cur - 1]);
+    if (!rc) rc = capture_chunk_b(e, e->tail_iters, cur, &e->gb_tail[e->pq][cur - 1], &e->xb_tail[e->pq][cur - 1]);
     if (rc) return rc;
   }
   hipLaunchKernelGGL(kb_finish, dim3(ntiles), dim3(1024), 0, e->stream, d, B);
   if (d.digest) hipLaunchKernelGGL(kb_heur_rows, dim3((d.M + 3) / 4, ntiles), dim3(256), 0, e->stream, d);
-  hipLaunchKernelGGL(kb_obj_rows, dim3((d.n + 3) / 4, ntiles), dim3(256), 0, e->stream, d);
+  if (e->pq) hipLaunchKernelGGL(kb_obj_rows<true>, dim3((d.n + 3) / 4, ntiles), dim3(256), 0, e->stream, d);
+  else hipLaunchKernelGGL(kb_obj_rows<false>, dim3((d.n + 3) / 4, ntiles), dim3(256), 0, e->stream, d);
   hipLaunchKernelGGL(kb_obj_sum, dim3(ntiles), dim3(1024), 0, e->stream, d);
   return 0;
 }
@@ -1645,9 +1661,25 @@ int derived_end(miosqp_qp_engine *e, size_t rec_doubles, double *device_seconds)
   return 0;
 }
 
-// one slice of at most Bcap nodes
+// solve_batch_q on first use: the three cost arrays behind the batched ones, and the pinned block the raw costs travel through
+int ensure_batch_q(miosqp_qp_engine *e) {
+  if (e->d.b_q) return 0;
+  const size_t n = e->n, Bs = (size_t)e->d.Bs;
+  double *bq = nullptr, *bqs = nullptr, *bqr = nullptr;
+  int rc = dalloc(e, &bq, n * Bs);
+  if (!rc) rc = dalloc(e, &bqs, n * Bs);
+  if (!rc) rc = dalloc(e, &bqr, n * Bs);
+  if (rc) return rc;
+  HIPCHK(hipHostMalloc((void **)&e->hb_q, sizeof(double) * Bs * n, hipHostMallocDefault));
+  e->d.b_qs = bqs;
+  e->d.b_qraw = bqr;
+  e->d.b_q = bq;  // (the captured chunks of set [0] hold a Dev without these: they never read them)
+  return 0;
+}
+
+// one slice of at most Bcap nodes; q: the slice's raw costs, instance-major (e->pq is set), or nullptr
 int solve_slice(miosqp_qp_engine *e, int B, const double *l, const double *u, const double *x0, const double *y0,
-                double *x_out, double *y_out, miosqp_qp_info *info) {
+                double *x_out, double *y_out, miosqp_qp_info *info, const double *q = nullptr) {
   const Dev &d = e->d;
   const size_t n = e->n, M = e->M;
   const double t0 = wall();
@@ -1660,6 +1692,12 @@ int solve_slice(miosqp_qp_engine *e, int B, const double *l, const double *u, co
   memcpy(h + 2 * B * M + B * n, y0, sizeof(double) * B * M);
   HIPCHK(hipEventRecord(e->ev0, e->stream));
   HIPCHK(hipMemcpyAsync(d.b_raw, h, sizeof(double) * B * (3 * M + n), hipMemcpyHostToDevice, e->stream));
+  if (q) {
+    // qbar_k = c D q_k by the kernel that scales solve_trees' costs: the bits update_lin_cost leaves in d.q
+    memcpy(e->hb_q, q, sizeof(double) * B * n);
+    HIPCHK(hipMemcpyAsync(d.b_qraw, e->hb_q, sizeof(double) * B * n, hipMemcpyHostToDevice, e->stream));
+    hipLaunchKernelGGL(k_scale_q_batch, dim3((unsigned)(((size_t)B * n + 255) / 256)), dim3(256), 0, e->stream, d, d.b_qraw, d.b_qs, B);
+  }
   if (int rcr = slice_run(e, B, e->st.max_iter)) return rcr;
   const int big = (int)(n > M ? n : M);
   hipLaunchKernelGGL(kb_export, dim3((big + 3) / 4, ntiles), dim3(256), 0, e->stream, d, B);

@@ -34,7 +34,7 @@ void enqueue_stream_chunk(miosqp_qp_engine *e, int part = 0) {
     hipLaunchKernelGGL(kb_check_con, dim3((d.M + 3) / 4, ntiles), dim3(256), 0, e->stream, d);
     hipLaunchKernelGGL(kb_check_var, dim3(2 * ((d.n + 3) / 4), ntiles), dim3(256), 0, e->stream, d);
   }
-  hipLaunchKernelGGL(kb_check_reduce, dim3(ntiles, KR), dim3(256), 0, e->stream, d);
+  hipLaunchKernelGGL(kb_check_reduce<false>, dim3(ntiles, KR), dim3(256), 0, e->stream, d);
   hipLaunchKernelGGL(kb_check_decide, dim3(ntiles), dim3(256), 0, e->stream, d);
   // harvest: the decided columns, gathered into one tile
   hipLaunchKernelGGL(kp_harvest, dim3((big + 3) / 4), dim3(256), 0, e->stream, d, h);

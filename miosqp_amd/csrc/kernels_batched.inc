@@ -57,13 +57,23 @@ __device__ __forceinline__ double bdense_dot(const double *__restrict__ row, int
   return (a0 + a1) + (a2 + a3);
 }
 
+// The linear cost of column b at `row` (o = row * Bs + b).  PQ = false: the engine's own scaled q, one value per row shared
+// by every column (solve_batch, the derived batches, the pool, kbs).  PQ = true: the column's own cost from the
+// batch-fastest array b_q[n x Bs] (miosqp_qp_solve_batch_q: one MIQP per column on the shared factor).
+template <bool PQ>
+__device__ __forceinline__ double bq_at(const Dev &d, int row, size_t o) {
+  if constexpr (PQ) return d.b_q[o];
+  else return d.q[row];
+}
+
+template <bool PQ>
 __global__ __launch_bounds__(256) void kb_panel_fwd(Dev d) {
   if (d.ctrl->done) return;
   BSETUP
   const int row = blockIdx.x * 4 + wv;
   if (row >= d.n) return;
   const double acc = brow_dot(d.pv_idx, d.pv_L, d.pv_ptr[row], d.pv_ptr[row + 1], d.b_wh + b, Bs);
-  d.b_cv[row * Bs + b] = d.sigma * d.b_x[row * Bs + b] - d.q[row] - acc;
+  d.b_cv[row * Bs + b] = d.sigma * d.b_x[row * Bs + b] - bq_at<PQ>(d, row, row * Bs + b) - acc;
 }
 
 __global__ __launch_bounds__(256) void kb_tail_fwd(Dev d) {
@@ -268,7 +278,7 @@ __global__ __launch_bounds__(RG *KS * 64) void kbd_fwd(Dev d) {
 }
 
 // rows of L^-T: blocks [0, nbx) the x rows (strict upper Linv^T), the rest the constraint rows (-G)^T
-template <int RG, int KS>
+template <int RG, int KS, bool PQ = false>
 __global__ __launch_bounds__(RG *KS * 64) void kbd_bwd(Dev d) {
   if (d.ctrl->done) return;
   using C = BdCfg<RG, KS>;
@@ -296,7 +306,7 @@ __global__ __launch_bounds__(RG *KS * 64) void kbd_bwd(Dev d) {
         const double xn = d.alpha * xt + (1.0 - d.alpha) * xp;
         d.b_x[o] = xn;
         d.b_dx[o] = xn - xp;
-        d.b_rx[o] = d.sigma * xn - d.q[row];
+        d.b_rx[o] = d.sigma * xn - bq_at<PQ>(d, row, o);
       }
     }
     return;
@@ -503,7 +513,7 @@ __global__ __launch_bounds__(KS * 64, KS / 4) void kbm_fwd(Dev d, int ncol) {
   if (stamp) stamp[5] = wall_clock64();
 }
 
-template <int KS, int DEPTH>
+template <int KS, int DEPTH, bool PQ = false>
 __global__ __launch_bounds__(KS * 64, KS / 4) void kbm_bwd(Dev d, int ncol) {
   __shared__ double lds[KS * BM_NT * 256];
   const int nbx = (d.n + 15) / 16, nbc = (d.wh_m + 15) / 16;
@@ -520,7 +530,7 @@ __global__ __launch_bounds__(KS * 64, KS / 4) void kbm_bwd(Dev d, int ncol) {
     const int row0 = rb * 16, row = row0 + o.row;
     const bool mine = out && row < d.n;
     const size_t oo = (size_t)row * Bs + b;
-    const double ut = mine ? d.b_ut[oo] : 0.0, xp = mine ? d.b_x[oo] : 0.0, q = mine ? d.q[row] : 0.0;
+    const double ut = mine ? d.b_ut[oo] : 0.0, xp = mine ? d.b_x[oo] : 0.0, q = mine ? bq_at<PQ>(d, row, oo) : 0.0;
     const bool frozen = mine ? d.c_done[b] != 0 : true;
     // the variable's own bound row (identity rows, see above): its operands are requested before the sweep too
     const int pos = (mine && d.wh_m < d.M) ? d.int_pos[row] : -1;
@@ -659,6 +669,7 @@ __global__ __launch_bounds__(BMC_KS * 64, 2) void kbm_check_var(Dev d, int ncol)
 // Stage 1 of the batched decision: grid (column tiles, KR row slices); every workgroup folds its
 // slice of rows for 64 columns and 17 quantities into b_part[tile][slice][q][64].
 constexpr int KR = 32;
+template <bool PQ>
 __global__ __launch_bounds__(256) void kb_check_reduce(Dev d) {
   if (d.ctrl->done) return;
   __shared__ double part[NQ][4][64];
@@ -682,7 +693,7 @@ __global__ __launch_bounds__(256) void kb_check_reduce(Dev d) {
   }
   for (int i = sl * 4 + rg; i < n; i += 4 * KR) {
     const size_t o = i * Bs + b;
-    const double di = d.Dinv[i], px = d.b_sn[0 * NB + o], aty = d.b_sn[2 * NB + o], q = d.q[i], x = d.b_x[o],
+    const double di = d.Dinv[i], px = d.b_sn[0 * NB + o], aty = d.b_sn[2 * NB + o], q = bq_at<PQ>(d, i, o), x = d.b_x[o],
                  dx = d.b_dx[o];
     v[6] = fmax(v[6], fabs(di * (px + q + aty)));
     v[7] = fmax(v[7], fabs(di * px));
@@ -795,7 +806,9 @@ __global__ void kb_reset(Dev d, int B) {
   }
 }
 
-// node-major staging -> scaled, batch-fastest working vectors (block = 64 columns x 4 rows)
+// node-major staging -> scaled, batch-fastest working vectors (block = 64 columns x 4 rows).  PQ: the columns' scaled costs
+// (instance-major b_qs, from k_scale_q_batch) are laid out batch-fastest in b_q on the way; padding columns get a zero cost
+template <bool PQ>
 __global__ __launch_bounds__(256) void kb_prepare(Dev d, int B) {
   const int lane = threadIdx.x & 63, b = blockIdx.y * 64 + lane;
   const int j = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -814,7 +827,13 @@ __global__ __launch_bounds__(256) void kb_prepare(Dev d, int B) {
     const double xs = act ? d.Dinv[j] * rx[(size_t)b * n + j] : 0.0;
     d.b_x[o] = xs;
     d.b_dx[o] = 0.0;
-    d.b_rx[o] = d.sigma * xs - d.q[j];
+    if constexpr (PQ) {
+      const double qs = act ? d.b_qs[(size_t)b * n + j] : 0.0;
+      d.b_q[o] = qs;
+      d.b_rx[o] = d.sigma * xs - qs;
+    } else {
+      d.b_rx[o] = d.sigma * xs - d.q[j];
+    }
   }
 }
 
@@ -834,7 +853,9 @@ __global__ __launch_bounds__(256) void kb_warm_z(Dev d) {
 }
 
 // Compaction of a wave: decided columns are swapped towards the tail so that the columns still
-// iterating fill the first tiles and later chunks launch fewer tiles.  grid (row chunks, pairs).
+// iterating fill the first tiles and later chunks launch fewer tiles.  grid (row chunks, pairs).  PQ: the column's scaled
+// cost moves with its iterates (its raw cost stays where it is: kb_obj_rows finds it through c_node).
+template <bool PQ>
 __global__ __launch_bounds__(256) void kb_swap_cols(Dev d, int npairs) {
   const int p = blockIdx.y;
   if (p >= npairs) return;
@@ -850,6 +871,7 @@ __global__ __launch_bounds__(256) void kb_swap_cols(Dev d, int npairs) {
   SWAPROW(d.b_l, d.M) SWAPROW(d.b_u, d.M) SWAPROW(d.b_z, d.M) SWAPROW(d.b_y, d.M) SWAPROW(d.b_dy, d.M)
   SWAPROW(d.b_wh, d.M + d.n)  // wh | rx
   SWAPROW(d.b_x, d.n) SWAPROW(d.b_dx, d.n)
+  if constexpr (PQ) { SWAPROW(d.b_q, d.n) }
 #undef SWAPROW
   if (r == 0) {
 #define SWAP1(T, arr) { const T t_ = arr[a]; arr[a] = arr[b]; arr[b] = t_; }
@@ -952,16 +974,21 @@ __global__ __launch_bounds__(256) void kb_heur_rows(Dev d) {
   d.b_sm[row * Bs + b] = fmax(d.root_l[row] - d.eps_lin - z, z - d.root_u[row] - d.eps_lin);
 }
 
+// PQ: the raw cost of the node this column holds, instance-major b_qraw, through c_node (columns move when a wave is compacted)
+template <bool PQ>
 __global__ __launch_bounds__(256) void kb_obj_rows(Dev d) {
   if (d.stream && !d.t_has[blockIdx.y]) return;
   BSETUP
   const int row = blockIdx.x * 4 + wv;
   if (row >= d.n) return;
+  double qr;
+  if constexpr (PQ) qr = d.b_qraw[(size_t)d.c_node[b] * d.n + row];
+  else qr = d.qraw[row];
   double acc, acc2;
   brow_dot2(d.pr_idx, d.pr_val, d.pr_ptr[row], d.pr_ptr[row + 1], d.b_xfin + b, (d.digest ? d.b_xi : d.b_xfin) + b, Bs,
             acc, acc2);
-  d.b_sn[row * Bs + b] = d.b_xfin[row * Bs + b] * (0.5 * acc + d.qraw[row]);
-  if (d.digest) d.b_sn[(size_t)d.n * Bs + row * Bs + b] = d.b_xi[row * Bs + b] * (0.5 * acc2 + d.qraw[row]);
+  d.b_sn[row * Bs + b] = d.b_xfin[row * Bs + b] * (0.5 * acc + qr);
+  if (d.digest) d.b_sn[(size_t)d.n * Bs + row * Bs + b] = d.b_xi[row * Bs + b] * (0.5 * acc2 + qr);
 }
 
 __global__ __launch_bounds__(1024) void kb_obj_sum(Dev d) {

@@ -255,7 +255,8 @@ __device__ __forceinline__ void kbp_st_pair(__amdgpu_buffer_rsrc_t rs, unsigned 
 }
 
 // PROF (miosqp_qp_debug_timeline which = 5): shader clocks of thread 0 per phase, 16 words per workgroup in d.prof
-template <bool PROF>
+// PQ: one linear cost per column (b_q, batch-fastest) instead of the engine's shared q
+template <bool PROF, bool PQ = false>
 __global__ __launch_bounds__(512) void kbp(Dev d, KbpArgs ka) {
   extern __shared__ __attribute__((aligned(16))) double kbp_smem[];
   double *lds = kbp_smem;                  // the reduction (and, between uses, the barrier's flag word)
@@ -331,6 +332,7 @@ __global__ __launch_bounds__(512) void kbp(Dev d, KbpArgs ka) {
       {
         const size_t oo = (size_t)xrow * Bs + b;
         const double ut = xmine ? kbp_ld(d.b_ut + oo) : 0.0, xp = xmine ? d.b_x[oo] : 0.0;
+        const double qc = PQ ? (xmine ? bq_at<PQ>(d, xrow, oo) : 0.0) : qx;  // this column block's cost, requested before the sweep
         const size_t oj = pos >= 0 ? (size_t)(d.m_orig + pos) * Bs + b : 0;  // the variable's own bound row: z, y, l, u, dy
         const size_t ow = pos >= 0 ? whrow(d, d.m_orig + pos) * Bs + b : 0;  // its wh entry
         double zp = 0, yp = 0, whp = 0, lo = 0, up = 0;
@@ -345,7 +347,7 @@ __global__ __launch_bounds__(512) void kbp(Dev d, KbpArgs ka) {
             const double xn = alpha * xt + (1.0 - alpha) * xp;
             d.b_x[oo] = xn;
             d.b_dx[oo] = xn - xp;
-            double rx = sigma * xn - qx;
+            double rx = sigma * xn - qc;
             if (pos >= 0) {
               const double nu = -rho * whp + aj * xt;  // aj = rho a_j
               const double zt = zp + rinv * (nu - yp);
@@ -413,7 +415,7 @@ __global__ __launch_bounds__(512) void kbp(Dev d, KbpArgs ka) {
 // other members read (ut, wh, r~: agent-scope 16-byte stores, two columns per even lane); x, z, y and the last iteration's
 // x~, dx, dy go to memory once, when the launch ends.  Same arithmetic, same bits as kbm_fwd / kbm_bwd.
 // ------------------------------------------------------------------------------------------
-template <bool PROF>
+template <bool PROF, bool PQ = false>
 __global__ __launch_bounds__(512) void kbp1(Dev d, KbpArgs ka) {
   extern __shared__ __attribute__((aligned(16))) double kbp_smem[];
   double *lds = kbp_smem;
@@ -451,7 +453,8 @@ __global__ __launch_bounds__(512) void kbp1(Dev d, KbpArgs ka) {
   const int xrow = row0 + o.row;
   const bool xmine = xrow < n;
   const size_t ox = (size_t)xrow * Bs + b;
-  const double di = xmine ? d.d2inv[xrow] : 0.0, qx = xmine ? d.q[xrow] : 0.0;
+  // (PQ: the thread owns one column for the whole launch, so its column's cost is one register as the shared one is)
+  const double di = xmine ? d.d2inv[xrow] : 0.0, qx = xmine ? bq_at<PQ>(d, xrow, ox) : 0.0;
   const int pos = (xmine && whm < d.M) ? d.int_pos[xrow] : -1;  // the variable's own bound row (identity rows)
   const double aj = pos >= 0 ? d.a_int[xrow] : 0.0;
   const size_t oj = pos >= 0 ? (size_t)(d.m_orig + pos) * Bs + b : 0;   // its z, y, l, u, dy

@@ -1,0 +1,146 @@
+"""B branch-and-bound trees on one factorisation, advanced in lock step: one node of every unfinished tree per wave.
+
+`MIOSQP.solve_many` calls `run` for problems beyond the one-launch trees (`miosqp_qp_solve_trees`: a whole tree per
+workgroup, n + M <= 192).  Every tree keeps its own state -- leaf list, incumbent, counters and a view of the model's
+`Data` whose q, l, u are the instance's -- in a `Workspace` that shares the model's solver and settings and was never
+set up itself (`_Tree`).  One wave:
+
+  * every tree that can continue takes its next leaf by `leaf_index(tree_explor_rule)`;
+  * the chosen leaves go out together, each with its tree's linear cost: ONE `solve_batch_q` on the HIP engine
+    (`miosqp_qp_solve_batch_q`, which slices a wave wider than max_batch), column by column (`update(q=)` +
+    `Node.solve`) on a solver without it -- the generic wave, which is the restatement the CPU tests run;
+  * every tree runs the unchanged `Workspace.bound_and_branch` on its leaf and counts the node.
+
+A node is a pure function of (q, l, u, x0, y0), so every tree makes exactly the decisions of its sequential solve
+(`update_vectors` + `set_x0` + `solve`), node for node.  The wave waits for its slowest column; trees finish at
+different waves and later waves are narrower.
+
+The rounding heuristic of the device digest tests the rounded point against the ENGINE's root bounds (set_root: the
+model's).  For an instance with l, u of its own that verdict is replaced on the host with the test against the
+instance's root bounds (`Workspace.satisfies_lin_constraints`, one product with A) at the nodes where
+`bound_and_branch` asks for it -- those whose rounded point would improve the incumbent; everything else of the digest
+depends on the node alone.
+"""
+import copy
+from time import time
+
+import numpy as np
+
+from miosqp_amd import bnb
+
+
+class _Tree(bnb.Workspace):
+    """One instance's tree: a Workspace on the model's solver and settings with its own data view and state"""
+
+    def __init__(self, work, q, l, u, own_bounds, upper, x0):
+        # (no Workspace.__init__: nothing is set up, the solver is the model's)
+        for name in ('settings', 'sb', 'rf', 'pol', 'pol_repair_iter', '_second', 'backend', 'constant', 'ok', 'solver',
+                     'qp_settings', 'root_on_device'):
+            setattr(self, name, getattr(work, name))
+        data = copy.copy(work.data)
+        data.q, data.l, data.u = q, l, u
+        self.data = data
+        self.own_bounds = own_bounds
+        self._reset_counters()
+        self.defer_lower = True  # lower_glob is only reported: once, when the trees are done (as a wave of solve_wave defers it)
+        self.leaves = [self._make_root()]
+        # Workspace.set_x0 (workspace.py:94-111), judged by solve_many on the instance's vectors
+        self.upper_glob = upper
+        self.x = x0 if np.isfinite(upper) else np.empty(data.n)
+
+    def absorb_digest(self, leaf):
+        """see the module text: the heuristic's feasibility verdict against this instance's root bounds"""
+        dg = leaf.digest
+        if dg is None or not self.own_bounds or leaf.status not in self.ok:
+            return
+        if not dg.heur_obj < self.upper_glob:
+            return  # bound_and_branch asks for the verdict only when the rounded point would improve the incumbent
+        x_int = self.get_integer_solution(leaf.x)
+        dg.heur_feasible = bool(self.satisfies_lin_constraints(x_int, self.data.l, self.data.u))
+
+
+def supported(work):
+    """the settings the lock-step trees cover: most-fractional branching, no round and fix, rules 0-3"""
+    st = work.settings
+    return st['branching_rule'] == 0 and not work.rf['on'] and st['tree_explor_rule'] in (0, 1, 2, 3)
+
+
+def _wave_batched(solver, trees, live, leaves):
+    r = solver.solve_batch_q(np.stack([trees[k].data.q for k in live]),
+                             np.stack([lf.l for lf in leaves]), np.stack([lf.u for lf in leaves]),
+                             np.stack([lf.x for lf in leaves]), np.stack([lf.y for lf in leaves]))
+    for c, lf in enumerate(leaves):
+        lower = None if np.isnan(r.lower[c]) else float(r.lower[c])
+        lf._absorb(int(r.status_val[c]), int(r.iter[c]), float(r.run_time[c]), r.x[c].copy(), r.y[c].copy(), lower)
+        lf.digest = r.digest[c] if getattr(r, 'digest', None) is not None else None
+    return int(np.max(r.iter)), float(np.mean(r.iter))
+
+
+def _wave_generic(model, trees, live, leaves):
+    work = model.work
+    for k, lf in zip(live, leaves):
+        q = trees[k].data.q
+        work.solver.update(q=q)
+        for second in work._second.values():
+            second.update(q=q)
+        lf.solve()
+    it = [lf.num_iter for lf in leaves]
+    return int(max(it)), float(np.mean(it))
+
+
+def run(model, todo, Q, L, U, up, XI, instances, out, batched):
+    """The trees of instances `todo` in lock step; fills out[k] with what the sequential path of solve_many puts there.
+    Q, L, U: instance-major vectors; up, XI: upper bound and point of an accepted x0 (inf without one).  batched: the
+    wave is one solve_batch_q; otherwise the generic wave, after which the solver's q is put back.  Leaves
+    work.lockstep = dict(instances, waves, nodes, batched, max_width, iters_max, iters_mean, finished_at): per wave the
+    largest and the mean ADMM iteration count of its columns; per instance the wave after which its tree was done."""
+    work, data = model.work, model.work.data
+    rule = work.settings['tree_explor_rule']
+    t0 = time()
+    trees = {}
+    for k in todo:
+        inst = instances[k]
+        own = inst.get('l') is not None or inst.get('u') is not None
+        trees[k] = _Tree(work, Q[k].copy(), L[k].copy(), U[k].copy(), own, float(up[k]), XI[k].copy())
+    info = dict(instances=len(todo), waves=0, nodes=0, batched=bool(batched), max_width=0, iters_max=[], iters_mean=[],
+                finished_at={})
+    q_keep = data.q
+    try:
+        while True:
+            live = [k for k in todo if trees[k].can_continue()]
+            if not live:
+                break
+            leaves = [trees[k].choose_leaf(rule) for k in live]
+            if batched:
+                imax, imean = _wave_batched(work.solver, trees, live, leaves)
+            else:
+                imax, imean = _wave_generic(model, trees, live, leaves)
+            info['waves'] += 1
+            info['nodes'] += len(live)
+            info['max_width'] = max(info['max_width'], len(live))
+            info['iters_max'].append(imax)
+            info['iters_mean'].append(imean)
+            for k, lf in zip(live, leaves):
+                tree = trees[k]
+                tree.absorb_digest(lf)
+                tree.bound_and_branch(lf)
+                tree.iter_num += 1
+                if not tree.can_continue():
+                    info['finished_at'][k] = info['waves']
+    finally:
+        if not batched:
+            work.solver.update(q=q_keep)
+            for second in work._second.values():
+                second.update(q=q_keep)
+        work.lockstep = info
+    dt = time() - t0
+    for k in todo:
+        tree = trees[k]
+        info['finished_at'].setdefault(k, 0)  # (a tree with nothing to do: max_iter_bb <= 1)
+        if tree.leaves:
+            tree.lower_glob = min(lf.lower for lf in tree.leaves)
+        tree.osqp_iter_avg = tree.osqp_iter / tree.iter_num
+        tree.get_return_status()
+        tree.get_return_solution()
+        out[k] = dict(x=np.array(tree.x, dtype=float), upper_glob=tree.upper_glob, status=tree.status,
+                      nodes=tree.iter_num - 1, osqp_iter=tree.osqp_iter, run_time=dt / len(todo))

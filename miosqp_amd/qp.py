@@ -203,6 +203,15 @@ class OSQP(object):
 
     def solve_batch(self, l, u, x0, y0):
         """B independent nodes sharing the factor; arrays are [B, .]."""
+        return self._solve_batch(None, l, u, x0, y0)
+
+    def solve_batch_q(self, q, l, u, x0, y0):
+        """B independent nodes sharing the factor, each with a linear cost of its own (q is [B, n]): column k is
+        update(q=q[k]) + solve_node(l[k], u[k], x0[k], y0[k]); the solver's own q stays as it is.  Returns what
+        solve_batch returns."""
+        return self._solve_batch(q, l, u, x0, y0)
+
+    def _solve_batch(self, q, l, u, x0, y0):
         l = np.ascontiguousarray(l, dtype=np.float64)
         B = l.shape[0]
         u = np.ascontiguousarray(u, dtype=np.float64).reshape(B, self.m)
@@ -210,9 +219,15 @@ class OSQP(object):
         y0 = np.ascontiguousarray(y0, dtype=np.float64).reshape(B, self.m)
         x, y = np.empty((B, self.n)), np.empty((B, self.m))
         infos = (_lib.Info * B)()
-        rc = _check(self._lib.miosqp_qp_solve_batch(self._h, B, _lib.as_d(l), _lib.as_d(u),
-                                                    _lib.as_d(x0), _lib.as_d(y0), _lib.as_d(x),
-                                                    _lib.as_d(y), infos), "solve_batch")
+        if q is None:
+            rc = _check(self._lib.miosqp_qp_solve_batch(self._h, B, _lib.as_d(l), _lib.as_d(u),
+                                                        _lib.as_d(x0), _lib.as_d(y0), _lib.as_d(x),
+                                                        _lib.as_d(y), infos), "solve_batch")
+        else:
+            q = np.ascontiguousarray(q, dtype=np.float64).reshape(B, self.n)
+            rc = _check(self._lib.miosqp_qp_solve_batch_q(self._h, B, _lib.as_d(q), _lib.as_d(l), _lib.as_d(u),
+                                                          _lib.as_d(x0), _lib.as_d(y0), _lib.as_d(x),
+                                                          _lib.as_d(y), infos), "solve_batch_q")
         if rc == 1:
             raise ValueError("Lower bound must be lower than or equal to upper bound")
         return types.SimpleNamespace(
