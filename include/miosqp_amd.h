@@ -338,6 +338,31 @@ int miosqp_qp_polish_many(miosqp_qp_engine *e, int32_t B, const double *q, const
  * lower-active, 1 upper-active, 0 inactive).  MIOSQP_EARG when that call had no instance b. */
 int miosqp_qp_get_polish_many_classes(miosqp_qp_engine *e, int32_t b, int8_t *cls);
 
+/* ---- polishing of many larger instances in one launch ----------------------------------------------------------
+ * miosqp_qp_polish_many beyond one workgroup's LDS: the same MPC re-solve pattern
+ * (/root/reference/miosqp/solver.py:174-212, examples/power_converter/power_converter.py:467-476; `polish` reaches OSQP
+ * through qp_settings, /root/reference/miosqp/workspace.py:67-68) for the problems the lock-step trees of solve_many
+ * were written for.  OSQP has NO batched polish and no repair loop.
+ * Arguments, validation, error codes, records, the meaning of q == NULL and the guarantee that the engine is not touched
+ * are those of miosqp_qp_polish_many, and per instance the contract is the same, step for step: the classification
+ * rule, S = P + delta I + A_act^T A_act / delta, an LDL^T that stops at the first pivot with !(d > 0), 1 + refine_iter
+ * solves against the unregularised system, the revision at tol 1e-10, stops 0 / 1 / 2 with the kept point of the round
+ * before a bad pivot, the acceptance test and reasons 0-3, accepted0 / reason0, the input bit for bit on rejection.
+ * One workgroup owns an instance from classification to record; S (n x ld) and the work vectors live in that
+ * workgroup's slab of device scratch, A is read from the sparse unscaled rows, the factorisation is blocked (panels of
+ * 32 factorised in LDS, the trailing update streams S) and so are the substitutions.  W = min(B, 2 x the compute
+ * units, 1 GiB / slab) workgroups are launched; workgroup w takes instances w, w + W, ..  Slabs and pinned blocks are
+ * allocated on first use, grown on demand and freed with the engine.  Every sum has a fixed order: an instance's answer
+ * has the same bits whatever B is, wherever it sits in the batch and whichever slab it lands in.  It need not have
+ * miosqp_qp_polish_many's or miosqp_qp_polish_repair's bits: only the order of the sums differs.
+ * There is no lower size limit.  MIOSQP_EUNSUPPORTED: n > 512 or M > 65536 (nothing is allocated). */
+int miosqp_qp_polish_many_large(miosqp_qp_engine *e, int32_t B, const double *q, const double *l, const double *u,
+                                const double *x, const double *y, double delta, int32_t refine_iter, int32_t repair_iter,
+                                double *x_out, double *y_out, miosqp_polish_repair_info *info);
+
+/* of the last miosqp_qp_polish_many_large call, as miosqp_qp_get_polish_many_classes */
+int miosqp_qp_get_polish_many_large_classes(miosqp_qp_engine *e, int32_t b, int8_t *cls);
+
 /* ---- a whole tree search in one launch (small problems) ------------------------------------------------
  * the MPC re-solve path (/root/reference/miosqp/solver.py:65-172 per MIQP,
  * examples/power_converter/power_converter.py:421-508 per sampling step).  For problems the LDS-resident solver
@@ -567,7 +592,8 @@ int miosqp_qp_get_batch_stats(miosqp_qp_engine *e, double *ms, int64_t *batch_it
  * 7 -> launches of the stream's persistent kernel (kbs) the leaf pool has queued, 8 -> chunks queued that way, 9 -> chunks
  * queued as the chunk graph / kernel by kernel instead (a launch of kbs that is called off leaves its chunks undone: 1);
  * 10 -> the poll delay the resident search grid ran with last (-1: it has not run), 11 -> synthetic nodes the calibration of
- * that delay has run on this engine (0: looked up) */
+ * that delay has run on this engine (0: looked up); 12 -> bytes of device scratch the slabs of
+ * miosqp_qp_polish_many_large hold (0 before its first call; a call that declines allocates none) */
 int64_t miosqp_qp_debug_counter(miosqp_qp_engine *e, int32_t which);
 
 /* debug: per-workgroup (start, end) stamps (100 MHz wall clock) of ONE launch of a product-form

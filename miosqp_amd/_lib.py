@@ -100,6 +100,9 @@ SYMBOLS = {
     "miosqp_qp_polish_many": (C.c_int, [C.c_void_p, C.c_int32, dp, dp, dp, dp, dp, C.c_double, C.c_int32, C.c_int32, dp, dp,
                                         C.POINTER(PolishRepairInfo)]),
     "miosqp_qp_get_polish_many_classes": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int8)]),
+    "miosqp_qp_polish_many_large": (C.c_int, [C.c_void_p, C.c_int32, dp, dp, dp, dp, dp, C.c_double, C.c_int32, C.c_int32,
+                                              dp, dp, C.POINTER(PolishRepairInfo)]),
+    "miosqp_qp_get_polish_many_large_classes": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int8)]),
     "miosqp_qp_solve_trees": (C.c_int, [C.c_void_p, C.c_int32, dp, dp, dp, dp, dp, dp, dp, C.c_int32, C.c_int32, dp,
                                         C.POINTER(TreeInfo)]),
     "miosqp_qp_search_create": (C.c_int, [C.c_void_p, C.c_int32]),

@@ -1130,7 +1130,7 @@ class MIOSQP(object):
                 U[k, :m] = inst['u']
         return Q, L, U
 
-    def polish_many(self, instances, results, tau=None, repair_iter=20):
+    def polish_many(self, instances, results, tau=None, repair_iter=20, large=False):
         """Polishes the answers of `solve_many(instances)` in place, all in ONE device call.  For every result with status
         MI_SOLVED / MI_MAX_ITER_FEASIBLE: its x with the integers rounded, the instance's l, u with the integer rows fixed
         to them, and -- a tree returns no y -- the multipliers of `primal_guess_multipliers(l, u, A x, tau)`
@@ -1141,7 +1141,11 @@ class MIOSQP(object):
         point is adopted when `accepted and stop == 0`: the guessed y makes dua_before meaningless, so the fixed point of
         the revision is the certificate.  On adoption x is the polished point with its integers set exactly and
         upper_glob its objective with the instance's q.  Every result gains polished (bool), polish_rounds, pri_after,
-        dua_after (NaN where nothing was polished).  The model is not touched.  Returns `results`."""
+        dua_after (NaN where nothing was polished).  The model is not touched.  Returns `results`.
+
+        large=True: once the one-workgroup entry is absent or has declined, `OSQP.polish_many_large` is tried before
+        the restatement -- still one launch, an instance's reduced matrix in a slab of device scratch (n <= 512); a
+        decline is remembered per model.  On a backend without the entry large=True is the restatement."""
         work, data = self.work, self.work.data
         if len(instances) != len(results):
             raise ValueError('polish_many: one result per instance')
@@ -1168,6 +1172,11 @@ class MIOSQP(object):
             recs = work.solver.polish_many(Q, L, U, X, Y, pol['delta'], pol['refine_iter'], repair_iter)
             if recs is None:
                 work._no_polish_many = True  # this problem is beyond one workgroup: do not ask again
+        if recs is None and large and hasattr(work.solver, 'polish_many_large') and \
+                not getattr(work, '_no_polish_many_large', False):
+            recs = work.solver.polish_many_large(Q, L, U, X, Y, pol['delta'], pol['refine_iter'], repair_iter)
+            if recs is None:
+                work._no_polish_many_large = True  # beyond the slabs as well
         if recs is None:
             recs = [polish_restatement(data.P, Q[b], data.A, L[b], U[b], X[b], Y[b], pol['delta'], pol['refine_iter'],
                                        repair_iter=repair_iter) for b in range(len(todo))]
@@ -1214,7 +1223,12 @@ class MIOSQP(object):
 
         polish=True: the incumbents are then polished together by `polish_many` (one more launch on the HIP engine) and
         every dict gains polished, polish_rounds, pri_after, dua_after.  Polishing many instances is asked for per call:
-        the setting polish_incumbent, which polishes the incumbent of `solve`, stays refused here."""
+        the setting polish_incumbent, which polishes the incumbent of `solve`, stays refused here.  polish="device" is
+        `polish_many(..., large=True)`: a problem beyond one workgroup (everything the lock-step driver takes) is
+        polished by `OSQP.polish_many_large` in one launch instead of the host's restatement per instance.  Any other
+        value raises ValueError."""
+        if not (polish is False or polish is True or (isinstance(polish, str) and polish == "device")):
+            raise ValueError('solve_many: polish must be False, True or "device"')
         work, data, st = self.work, self.work.data, self.work.settings
         require_plain_search(st, "solve_many", rule=False, heuristic=False)
         B = len(instances)
@@ -1307,7 +1321,7 @@ class MIOSQP(object):
                 for a, v in keep.items():
                     setattr(work, a, v)
         if polish:
-            self.polish_many(instances, out)
+            self.polish_many(instances, out, large=polish == "device")
         return out
 
     def update_vectors(self, q=None, l=None, u=None):

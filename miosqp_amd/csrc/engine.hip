@@ -38,6 +38,7 @@
 #include "../../include/miosqp_amd.h"
 #include "factor.hpp"
 #include "polish_many.hpp"  // polishing of many small instances in one launch (polish_many.hip)
+#include "polish_many_large.hpp"  // ... and of larger ones, S in a slab of device scratch per workgroup (polish_many_large.hip)
 
 #define QP_INFTY 1e30
 #define QP_MIN_SCALING 1e-4
@@ -487,8 +488,7 @@ int polish_queue_round0(miosqp_qp_engine *e, int refine_iter) {
 }
 
 // ---- polishing of many instances (miosqp_qp_polish_many): the pinned blocks and their device copies, grown with B ----
-void polish_many_free(miosqp_qp_engine *e) {
-  miosqp::PolManyScratch *s = e->polm;
+void polish_many_free(miosqp::PolManyScratch *&s) {
   if (!s) return;
   for (void *ev : s->ev)
     if (ev) hipEventDestroy((hipEvent_t)ev);
@@ -496,16 +496,25 @@ void polish_many_free(miosqp_qp_engine *e) {
   if (s->h_out) hipHostFree(s->h_out);
   if (s->d_in) hipFree(s->d_in);
   if (s->d_out) hipFree(s->d_out);
+  if (s->slab) hipFree(s->slab);
   delete s;
-  e->polm = nullptr;
+  s = nullptr;
 }
 
-int polish_many_ensure(miosqp_qp_engine *e, size_t n_in, size_t n_out) {
-  if (!e->polm) {
-    e->polm = new miosqp::PolManyScratch();
-    for (void *&ev : e->polm->ev) HIPCHK(hipEventCreate((hipEvent_t *)&ev));
+int polish_many_ensure(miosqp_qp_engine *e, miosqp::PolManyScratch *&slot, size_t n_in, size_t n_out, size_t n_slab) {
+  if (!slot) {
+    slot = new miosqp::PolManyScratch();
+    for (void *&ev : slot->ev) HIPCHK(hipEventCreate((hipEvent_t *)&ev));
   }
-  miosqp::PolManyScratch *s = e->polm;
+  miosqp::PolManyScratch *s = slot;
+  if (n_slab > s->cap_slab) {  // (the large entry's slabs: one per workgroup of the launch)
+    HIPCHK(hipStreamSynchronize(e->stream));
+    if (s->slab) hipFree(s->slab);
+    s->slab = nullptr;
+    s->cap_slab = 0;
+    HIPCHK(hipMalloc((void **)&s->slab, n_slab * sizeof(double)));
+    s->cap_slab = n_slab;
+  }
   if (n_in > s->cap_in) {
     HIPCHK(hipStreamSynchronize(e->stream));
     if (s->h_in) hipHostFree(s->h_in);
@@ -645,7 +654,8 @@ int miosqp_qp_cleanup(miosqp_qp_engine *e) {
   if (e->hb_q) hipHostFree(e->hb_q);
   if (e->h_der) hipHostFree(e->h_der);
   polish_free(e);
-  polish_many_free(e);
+  polish_many_free(e->polm);
+  polish_many_free(e->polml);
   drop_chunk_graphs(e);
   rt_release(e->rt);  // stream, events and pinned staging go back to the per-process cache
   delete e;
@@ -1722,9 +1732,12 @@ int miosqp_qp_get_polish_repair_trace(miosqp_qp_engine *e, int8_t *cls, double *
   return 0;
 }
 
-int miosqp_qp_polish_many(miosqp_qp_engine *e, int32_t B, const double *q, const double *l, const double *u,
-                          const double *x, const double *y, double delta, int32_t refine_iter, int32_t repair_iter,
-                          double *x_out, double *y_out, miosqp_polish_repair_info *info) {
+// Both batched polish entries: the argument checks, one pinned block down, the one launch -- k_pol_many, or with `large`
+// k_pol_many_g on W slabs of device scratch --, one pinned block back, the records.  The answers stay in the entry's
+// scratch for its class getter.
+static int polish_many_run(miosqp_qp_engine *e, bool large, int32_t B, const double *q, const double *l, const double *u,
+                           const double *x, const double *y, double delta, int32_t refine_iter, int32_t repair_iter,
+                           double *x_out, double *y_out, miosqp_polish_repair_info *info) {
   if (!e || !l || !u || !x || !y || !x_out || !y_out || !info) return MIOSQP_EARG;
   ENTER(e);
   if (B < 1) {
@@ -1756,16 +1769,30 @@ int miosqp_qp_polish_many(miosqp_qp_engine *e, int32_t B, const double *q, const
       g_err = "polish_many: NaN in x or q";
       return MIOSQP_EARG;
     }
-  if (miosqp::polish_many_lds_bytes((int)n, (int)M) > 160 * 1024) {
+  size_t slab = 0;
+  int W = 0;
+  if (large) {
+    // W = min(B, two workgroups per compute unit, what the slab budget allows); beyond the limits nothing is allocated
+    slab = miosqp::polish_many_large_slab_doubles((int)n, (int)M);
+    if (slab == (size_t)-1 || slab * sizeof(double) > miosqp::POLG_BUDGET) {
+      g_err = "polish_many_large: only for n <= 512 and M <= 65536";
+      return MIOSQP_EUNSUPPORTED;
+    }
+    int cus = 0;
+    HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->device));
+    const size_t fit = miosqp::POLG_BUDGET / (slab * sizeof(double));
+    W = (int)std::min(std::min(nB, (size_t)2 * (size_t)std::max(cus, 1)), fit);
+  } else if (miosqp::polish_many_lds_bytes((int)n, (int)M) > 160 * 1024) {
     g_err = "polish_many: only for problems whose reduced system and rows of A fit one workgroup's 160 KB of LDS";
     return MIOSQP_EUNSUPPORTED;
   }
   if (int rc = polish_ensure(e)) return rc;  // (places the unscaled rows of A on the device; nothing of it is written here)
   const size_t so = miosqp::polm_out_stride((int)n, (int)M);
   const size_t n_in = nB * ((q ? 2 : 1) * n + 3 * M), n_out = nB * so;
-  if (int rc = polish_many_ensure(e, n_in, n_out)) return rc;
+  miosqp::PolManyScratch *&slot = large ? e->polml : e->polm;
+  if (int rc = polish_many_ensure(e, slot, n_in, n_out, (size_t)W * slab)) return rc;
   const double t0 = wall();
-  miosqp::PolManyScratch *s = e->polm;
+  miosqp::PolManyScratch *s = slot;
   s->last_B = 0;
   // one block down: [q] | l | u | x | y, each instance-major
   double *h = s->h_in;
@@ -1788,8 +1815,18 @@ int miosqp_qp_polish_many(miosqp_qp_engine *e, int32_t B, const double *q, const
   hipStream_t st = e->stream;
   HIPCHK(hipEventRecord((hipEvent_t)s->ev[0], st));
   HIPCHK(hipMemcpyAsync(s->d_in, h, sizeof(double) * n_in, hipMemcpyHostToDevice, st));
-  if (int rc = miosqp::polish_many_launch(a, (void *)st)) {
-    set_err("polish_many: launch", (hipError_t)rc, __FILE__, __LINE__);
+  int lrc;
+  if (large) {
+    miosqp::PolManyLargeArgs g{};
+    g.a = a;
+    g.pv_ptr = p.pv_ptr; g.pv_idx = p.pv_idx; g.At = p.At;
+    g.slab = s->slab; g.slab_doubles = slab;
+    lrc = miosqp::polish_many_large_launch(g, W, (void *)st);
+  } else {
+    lrc = miosqp::polish_many_launch(a, (void *)st);
+  }
+  if (lrc) {
+    set_err("polish_many: launch", (hipError_t)lrc, __FILE__, __LINE__);
     return MIOSQP_EHIP;
   }
   HIPCHK(hipMemcpyAsync(s->h_out, s->d_out, sizeof(double) * n_out, hipMemcpyDeviceToHost, st));
@@ -1827,9 +1864,20 @@ int miosqp_qp_polish_many(miosqp_qp_engine *e, int32_t B, const double *q, const
   return 0;
 }
 
-int miosqp_qp_get_polish_many_classes(miosqp_qp_engine *e, int32_t b, int8_t *cls) {
+int miosqp_qp_polish_many(miosqp_qp_engine *e, int32_t B, const double *q, const double *l, const double *u,
+                          const double *x, const double *y, double delta, int32_t refine_iter, int32_t repair_iter,
+                          double *x_out, double *y_out, miosqp_polish_repair_info *info) {
+  return polish_many_run(e, false, B, q, l, u, x, y, delta, refine_iter, repair_iter, x_out, y_out, info);
+}
+
+int miosqp_qp_polish_many_large(miosqp_qp_engine *e, int32_t B, const double *q, const double *l, const double *u,
+                                const double *x, const double *y, double delta, int32_t refine_iter, int32_t repair_iter,
+                                double *x_out, double *y_out, miosqp_polish_repair_info *info) {
+  return polish_many_run(e, true, B, q, l, u, x, y, delta, refine_iter, repair_iter, x_out, y_out, info);
+}
+
+static int polish_many_classes(miosqp_qp_engine *e, const miosqp::PolManyScratch *s, int32_t b, int8_t *cls) {
   if (!e || !cls) return MIOSQP_EARG;
-  const miosqp::PolManyScratch *s = e->polm;
   if (!s || b < 0 || b >= s->last_B) {
     g_err = "get_polish_many_classes: no such instance in the last polish_many call";
     return MIOSQP_EARG;
@@ -1838,6 +1886,14 @@ int miosqp_qp_get_polish_many_classes(miosqp_qp_engine *e, int32_t b, int8_t *cl
   const double *o = s->h_out + (size_t)b * miosqp::polm_out_stride((int)n, (int)M);
   memcpy(cls, o + miosqp::POLM_REC_DOUBLES + n + M, M);
   return 0;
+}
+
+int miosqp_qp_get_polish_many_classes(miosqp_qp_engine *e, int32_t b, int8_t *cls) {
+  return polish_many_classes(e, e ? e->polm : nullptr, b, cls);
+}
+
+int miosqp_qp_get_polish_many_large_classes(miosqp_qp_engine *e, int32_t b, int8_t *cls) {
+  return polish_many_classes(e, e ? e->polml : nullptr, b, cls);
 }
 
 int miosqp_qp_get_polish_stages(miosqp_qp_engine *e, double *seconds) {
@@ -2496,6 +2552,7 @@ int64_t miosqp_qp_debug_counter(miosqp_qp_engine *e, int32_t which) {
   if (which == 9) return e->graph_chunks_run;
   if (which == 10) return e->run_nap_in_use;
   if (which == 11) return e->run_cal_nodes;
+  if (which == 12) return e->polml ? (int64_t)(e->polml->cap_slab * sizeof(double)) : 0;  // slabs of polish_many_large
   return which == 0 ? e->compactions : which == 1 ? e->kbp_fallbacks : -1;
 }
 

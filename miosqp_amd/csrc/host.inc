@@ -181,6 +181,7 @@ struct miosqp_qp_engine {
   std::vector<double> A_raw;
   PolishScratch *pol = nullptr;
   miosqp::PolManyScratch *polm = nullptr;  // polishing of many instances in one launch (miosqp_qp_polish_many)
+  miosqp::PolManyScratch *polml = nullptr;  // ... beyond one workgroup's LDS (miosqp_qp_polish_many_large): with the slabs
   // captured chunks per tile count; set [1] holds the per-column-cost instantiations (solve_batch_q), set [0] the others
   hipGraphExec_t xb_full[2][16] = {}, xb_tail[2][16] = {};
   hipGraph_t gb_full[2][16] = {}, gb_tail[2][16] = {};

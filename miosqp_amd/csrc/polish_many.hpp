@@ -37,6 +37,8 @@ struct PolManyScratch {
   size_t cap_in = 0, cap_out = 0;  // doubles
   void *ev[2] = {nullptr, nullptr};
   int last_B = 0;
+  double *slab = nullptr;  // miosqp_qp_polish_many_large only: the workgroups' slabs (polish_many_large.hpp)
+  size_t cap_slab = 0;     // doubles
 };
 
 // bytes of LDS one instance's workgroup needs (the caller compares with the chip's 160 KB)

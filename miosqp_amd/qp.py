@@ -326,32 +326,42 @@ class OSQP(object):
         order of the sums, without touching the engine's q.  Returns a list of B records shaped like
         `polish(..., repair_iter=)`'s, `active` included (device_time / run_time are the call's totals), or None when the
         problem is beyond what one workgroup holds."""
+        return self._polish_many("polish_many", q, l, u, x, y, delta, refine_iter, repair_iter)
+
+    def polish_many_large(self, q, l, u, x, y, delta=1e-6, refine_iter=3, repair_iter=0):
+        """`polish_many` beyond one workgroup's LDS (miosqp_qp_polish_many_large): the same arguments, the same records,
+        the same contract per instance up to the order of the sums; an instance's reduced matrix lives in a slab of
+        device scratch, min(B, 2 x compute units, 1 GiB / slab) workgroups take the instances in turn.  No lower size
+        limit; None for n > 512 or M > 65536."""
+        return self._polish_many("polish_many_large", q, l, u, x, y, delta, refine_iter, repair_iter)
+
+    def _polish_many(self, entry, q, l, u, x, y, delta, refine_iter, repair_iter):
+        run = getattr(self._lib, "miosqp_qp_" + entry)
+        get_classes = getattr(self._lib, "miosqp_qp_get_%s_classes" % entry)
         x = np.ascontiguousarray(x, dtype=np.float64)
         if x.ndim != 2:
-            raise ValueError("polish_many: instance-major arrays (B x n, B x M)")
+            raise ValueError(entry + ": instance-major arrays (B x n, B x M)")
         B = x.shape[0]
         l, u = np.ascontiguousarray(l, dtype=np.float64), np.ascontiguousarray(u, dtype=np.float64)
         y = np.ascontiguousarray(y, dtype=np.float64)
         q = None if q is None else np.ascontiguousarray(q, dtype=np.float64)
         if x.shape != (B, self.n) or l.shape != (B, self.m) or u.shape != (B, self.m) or y.shape != (B, self.m) or \
                 (q is not None and q.shape != (B, self.n)):
-            raise ValueError("polish_many: instance-major arrays (B x n, B x M)")
+            raise ValueError(entry + ": instance-major arrays (B x n, B x M)")
         xo, yo = np.empty((B, self.n)), np.empty((B, self.m))
         infos = (_lib.PolishRepairInfo * max(B, 1))()
-        rc = self._lib.miosqp_qp_polish_many(self._h, B, None if q is None else _lib.as_d(q), _lib.as_d(l), _lib.as_d(u),
-                                             _lib.as_d(x), _lib.as_d(y), float(delta), int(refine_iter), int(repair_iter),
-                                             _lib.as_d(xo), _lib.as_d(yo), infos)
+        rc = run(self._h, B, None if q is None else _lib.as_d(q), _lib.as_d(l), _lib.as_d(u), _lib.as_d(x), _lib.as_d(y),
+                 float(delta), int(refine_iter), int(repair_iter), _lib.as_d(xo), _lib.as_d(yo), infos)
         if rc == -5:
             return None
-        _check(rc, "polish_many")
+        _check(rc, entry)
         if rc == 1:
             raise ValueError("Lower bound must be lower than or equal to upper bound")
         out = []
         for b in range(B):
             rep, info = infos[b], infos[b].polish
             cls = np.zeros(self.m, dtype=np.int8)
-            _check(self._lib.miosqp_qp_get_polish_many_classes(self._h, b, cls.ctypes.data_as(C.POINTER(C.c_int8))),
-                   "get_polish_many_classes")
+            _check(get_classes(self._h, b, cls.ctypes.data_as(C.POINTER(C.c_int8))), "get_%s_classes" % entry)
             out.append(types.SimpleNamespace(
                 x=xo[b].copy(), y=yo[b].copy(), accepted=bool(info.accepted), reason=info.reason, n_lower=info.n_lower,
                 n_upper=info.n_upper, pri_before=info.pri_before, dua_before=info.dua_before, pri_after=info.pri_after,
@@ -671,6 +681,10 @@ class OSQP(object):
         """Tiles of S^-1 (on and above the diagonal, one per workgroup) the persistent streaming solver reads per iteration
         when it takes the matrix as symmetric; 0: it streams whole rows."""
         return int(self._lib.miosqp_qp_debug_counter(self._h, 6))
+
+    def polish_many_large_slab_bytes(self):
+        """Bytes of device scratch the slabs of `polish_many_large` hold on this engine (0 before its first call)."""
+        return int(self._lib.miosqp_qp_debug_counter(self._h, 12))
 
     def call_off_word(self):
         """The control block's call-off / time-out word once the engine's stream is idle (0: nothing happened)."""
