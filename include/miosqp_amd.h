@@ -405,6 +405,51 @@ int miosqp_qp_solve_trees(miosqp_qp_engine *e, int32_t B, const double *q, const
                           const double *x0, const double *y0, const double *upper0, const double *x_inc0,
                           int32_t tree_explor_rule, int32_t max_iter_bb, double *x_out, miosqp_tree_info *info);
 
+/* ---- B trees in lock step, driven from the host in C++ on device-resident leaves -----------------------
+ * miosqp_qp_solve_trees for problems of any size: the B instances of the reference's MPC pattern
+ * (MIOSQP.update_vectors + set_x0 + solve per instance, /root/reference/miosqp/solver.py:174-212, each solve the loop of
+ * solver.py:65-172) advance together, one node of every unfinished tree per wave, the wave being the lock-step batch with a
+ * linear cost per column (what miosqp_qp_solve_batch_q runs, sliced at max_batch columns the same way).  The loop
+ * `while can_continue: choose_leaf -> Node.solve -> bound_and_branch` (workspace.py:113-155, 274-334) runs per tree in
+ * C++ with the list semantics of the Python mirror; the open leaves of all trees are slots of ONE device store and the
+ * children are written on the device (workspace.py:157-203).  Per wave the host uploads five integers per column and
+ * reads a 64-byte record per column; no vector crosses PCIe between the roots going up and the incumbents coming down.
+ * Every tree makes the decisions of its own sequential solve, node for node (a node is a pure function of q, l, u, x0,
+ * y0); the value of an incumbent found by the rounding heuristic is the device's sum, as in miosqp_qp_search_run.
+ * The rounded point is tested against the INSTANCE's root rows (l, u of that instance), not the engine's root. */
+typedef struct miosqp_lockstep_stats {
+  int32_t waves;          /* waves run = the largest node count of a tree */
+  int32_t max_width;      /* columns of the widest wave */
+  int32_t grown;          /* times the slot store grew */
+  int32_t wave_cap;       /* IN: entries the three per-wave arrays below can take (max_iter_bb suffices); later waves are not recorded */
+  int64_t nodes;          /* over all trees */
+  int64_t iters_slowest;  /* sum over waves of the slowest column's ADMM iterations */
+  int64_t iters_all;      /* ... and of all columns' iterations */
+  double device_time;     /* seconds between the events around the call (the waits for the host between waves included) */
+  double run_time;        /* wall seconds */
+  double host_time;       /* of those: the tree logic on the host (choosing, absorbing the records), between the waves */
+  int32_t *wave_width;    /* IN, optional (NULL: not wanted): columns per wave */
+  int32_t *wave_iter_max; /* IN, optional: largest iteration count per wave */
+  double *wave_iter_mean; /* IN, optional: mean iteration count per wave */
+  int32_t *finished_at;   /* IN, optional, B entries: the wave after which tree b was done (0: it had nothing to do) */
+  double *node_hviol;     /* IN, optional debug, B x node_cap: the rounded point's violation at tree b's k-th node */
+  int32_t node_cap;       /* IN: nodes per tree node_hviol can take */
+  int32_t reserved;
+} miosqp_lockstep_stats;
+
+/* Arguments, layouts and meaning as for miosqp_qp_solve_trees (instance-major; upper0 >= 1.7e308: no incumbent;
+ * tree_explor_rule 0 .. 3 with the first-in-list tie rule; branching_rule 0 implied).  capacity: the starting number of
+ * node slots (0: max(64, 4 B), or whatever an earlier call left); the store doubles on demand.  info[b] as
+ * miosqp_qp_solve_trees fills it; overflow is always 0.  The engine's own q, bounds, root and search state are neither
+ * read nor written.  The per-call device data is allocated on first use, grown on demand and freed with the engine.
+ * Errors: MIOSQP_EARG as for miosqp_qp_solve_trees (also while pool chunks are in flight, as for miosqp_qp_solve_batch);
+ * MIOSQP_EBOUNDS for l > u in a root (nothing has been queued then) or for a branching that produced l > u;
+ * MIOSQP_EFULL only when the device has no memory for the slot store. */
+int miosqp_qp_solve_trees_lockstep(miosqp_qp_engine *e, int32_t B, const double *q, const double *l, const double *u,
+                                   const double *x0, const double *y0, const double *upper0, const double *x_inc0,
+                                   int32_t tree_explor_rule, int32_t max_iter_bb, int32_t capacity,
+                                   double *x_out, miosqp_tree_info *info, miosqp_lockstep_stats *stats);
+
 /* ---- node-at-a-time branch and bound, driven from the host in C++ -------------------------------------
  * The loop of /root/reference/miosqp/solver.py:65-172 (choose_leaf -> Node.solve -> bound_and_branch, workspace.py:
  * 113-155, 274-334) for problems of any size, one relaxation at a time in whatever form the engine uses for single

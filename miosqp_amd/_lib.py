@@ -36,6 +36,13 @@ class TreeInfo(C.Structure):
                 ("device_time", C.c_double), ("run_time", C.c_double)]
 
 
+class LockstepStats(C.Structure):
+    _fields_ = [("waves", C.c_int32), ("max_width", C.c_int32), ("grown", C.c_int32), ("wave_cap", C.c_int32),
+                ("nodes", C.c_int64), ("iters_slowest", C.c_int64), ("iters_all", C.c_int64), ("device_time", C.c_double),
+                ("run_time", C.c_double), ("host_time", C.c_double), ("wave_width", ip), ("wave_iter_max", ip), ("wave_iter_mean", dp),
+                ("finished_at", ip), ("node_hviol", dp), ("node_cap", C.c_int32), ("reserved", C.c_int32)]
+
+
 class SearchInfo(C.Structure):
     _fields_ = [("nodes", C.c_int64), ("osqp_iter", C.c_int64), ("open_leaves", C.c_int32), ("free_slots", C.c_int32),
                 ("improved", C.c_int32), ("reserved", C.c_int32), ("upper_glob", C.c_double), ("lower_glob", C.c_double),
@@ -105,6 +112,8 @@ SYMBOLS = {
     "miosqp_qp_get_polish_many_large_classes": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int8)]),
     "miosqp_qp_solve_trees": (C.c_int, [C.c_void_p, C.c_int32, dp, dp, dp, dp, dp, dp, dp, C.c_int32, C.c_int32, dp,
                                         C.POINTER(TreeInfo)]),
+    "miosqp_qp_solve_trees_lockstep": (C.c_int, [C.c_void_p, C.c_int32, dp, dp, dp, dp, dp, dp, dp, C.c_int32, C.c_int32,
+                                                 C.c_int32, dp, C.POINTER(TreeInfo), C.POINTER(LockstepStats)]),
     "miosqp_qp_search_create": (C.c_int, [C.c_void_p, C.c_int32]),
     "miosqp_qp_search_reset": (C.c_int, [C.c_void_p]),
     "miosqp_qp_search_add_leaf": (C.c_int, [C.c_void_p, dp, dp, dp, dp, C.c_int32, C.c_double]),

@@ -1220,6 +1220,11 @@ class MIOSQP(object):
         Measured at n 500, m 1000, p 250: 3.4 x the sequential path at 256 instances and rho 0.1, 1.6 x at
         rho "auto", even at about 32-64 instances and SLOWER below (a narrow wave costs what a wide one costs): with
         few instances pass lockstep=False.
+        "device": the same waves driven inside the library (`lockstep.run_device`, `OSQP.solve_trees_lockstep`): the
+        leaves of all trees stay in device slots and the tree logic runs in C++, so no vector crosses PCIe per wave and
+        no interpreter runs per node; the trees are those of True, the heuristic incumbent's value is the device's sum
+        (1e-12 relative).  ValueError when the solver lacks the entry or the settings are not the lock-step trees'.
+        Asked for by name only: None never chooses it (DESIGN 3k has the measurements).
 
         polish=True: the incumbents are then polished together by `polish_many` (one more launch on the HIP engine) and
         every dict gains polished, polish_rounds, pri_after, dua_after.  Polishing many instances is asked for per call:
@@ -1291,6 +1296,20 @@ class MIOSQP(object):
                         x[data.i_idx] = np.round(x[data.i_idx])
                     out[k] = dict(x=x, upper_glob=upper, status=status, nodes=int(info.nodes),
                                   osqp_iter=int(info.osqp_iter), run_time=dt / B)
+        if isinstance(lockstep, str):
+            # the driver in the library, asked for by name (the default is not this one)
+            from miosqp_amd import lockstep as ls
+            if lockstep != "device":
+                raise ValueError('solve_many: lockstep must be None, True, False or "device"')
+            if not ls.device_supported(work):
+                raise ValueError('solve_many(lockstep="device") needs the HIP engine with solve_trees_lockstep and the '
+                                 'device digest')
+            if not ls.supported(work):
+                raise ValueError('solve_many(lockstep="device") needs branching_rule 0, primal_heuristic 0 and '
+                                 'tree_explor_rule 0-3')
+            if redo:
+                ls.run_device(self, redo, Q, L, U, up, XI, instances, out)
+                redo = []
         if redo and lockstep is not False:
             from miosqp_amd import lockstep as ls
             batched = hasattr(work.solver, 'solve_batch_q')

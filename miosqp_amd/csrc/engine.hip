@@ -39,6 +39,7 @@
 #include "factor.hpp"
 #include "polish_many.hpp"  // polishing of many small instances in one launch (polish_many.hip)
 #include "polish_many_large.hpp"  // ... and of larger ones, S in a slab of device scratch per workgroup (polish_many_large.hip)
+#include "lockstep_trees.hpp"  // the tree logic of B trees in lock step (plain C++; host_lockstep.inc drives it)
 
 #define QP_INFTY 1e30
 #define QP_MIN_SCALING 1e-4
@@ -241,10 +242,12 @@ struct CoopNode {
 #include "kernels_bstream.inc"  // the streaming batch as ONE persistent launch: iterations, test, harvest and refill per column group (kbs)
 #include "kernels_derived.inc"  // nodes derived from one parent on the device, judged after the batch solve: strong branching, round and fix
 #include "kernels_polish.inc"  // polishing of a node's solution: active set, weighted Schur rows, solves and refinement, acceptance
+#include "kernels_lockstep.inc"  // B trees in lock step on device-resident leaves: gather / heuristic rows / scatter / incumbent around slice_run
 #include "host.inc"  // host side: engine object, allocation, launches, graph capture, solve loops
 #include "host_pool.inc"  // host side of the leaf pool (C ABI miosqp_qp_pool_*)
 #include "host_search.inc"  // node-at-a-time branch and bound driven from the host in C++ (C ABI miosqp_qp_search_*)
 #include "host_stream.inc"  // the host side of the streaming search in C++ (C ABI miosqp_qp_stream_*)
+#include "host_lockstep.inc"  // B trees in lock step driven from the host in C++ (C ABI miosqp_qp_solve_trees_lockstep)
 
 // ------------------------------------------------------------------------------------------
 // C ABI
@@ -644,6 +647,7 @@ int miosqp_qp_cleanup(miosqp_qp_engine *e) {
     if (S->mail_host) hipHostFree(S->mail_host);
     delete S;
   }
+  lockstep_free(e->lockstep);
   if (e->h_ready) hipHostFree(e->h_ready);
   if (e->h_dg) hipHostFree(e->h_dg);
   if (e->h_pctl) hipHostFree(e->h_pctl);

@@ -69,6 +69,7 @@ struct miosqp_qp_engine {
   std::vector<TreeOut> tb_hout;
   void *search = nullptr;  // NodeSearch (host_search.inc)
   void *sdriver = nullptr;  // StreamDriver (host_stream.inc)
+  void *lockstep = nullptr;  // LockstepStore (host_lockstep.inc)
   std::vector<int> h_iidx;  // host copy of the integer variables' indices
   unsigned long long pool_chunk_total = 0, pool_target[POOL_EVENTS] = {};  // chunks launched since the last reset; per launch: the count when it is done
   bool stage_busy[2] = {false, false};  // an upload out of that part of h_in may still be under way (rt.ev_stage)
@@ -1509,11 +1510,15 @@ int slice_begin(miosqp_qp_engine *e, int B) {
   return 0;
 }
 
+void launch_ls_heur_rows(miosqp_qp_engine *e, const LsRoots &roots, int ntiles);  // (host_lockstep.inc)
+
 // The lock-step solve of the B nodes staged in d.b_raw (node-major l | u | x0 | y0), up to `max_iter` iterations:
 // full chunks of check_termination iterations, then the tail graph for the rest only when max_iter is the engine's own
 // (a strong-branching cap is a multiple of check_termination: no tail).  Ends with the per-column epilogue
 // (unscale, clamp, digest, objective) in c_status / c_iter / c_lower / b_xfin / b_yfin, node order through c_node.
-int slice_run(miosqp_qp_engine *e, int B, int max_iter) {
+// roots: the columns belong to trees with root bounds of their own (kernels_lockstep.inc) -- the rounded points are
+// judged against those; nullptr (every other caller): against the engine's root, today's launches.
+int slice_run(miosqp_qp_engine *e, int B, int max_iter, const LsRoots *roots = nullptr) {
   const Dev &d = e->d;
   const size_t n = e->n, M = e->M;
   const int ntiles = (B + 63) / 64;
@@ -1613,7 +1618,8 @@ int slice_run(miosqp_qp_engine *e, int B, int max_iter) {
     if (rc) return rc;
   }
   hipLaunchKernelGGL(kb_finish, dim3(ntiles), dim3(1024), 0, e->stream, d, B);
-  if (d.digest) hipLaunchKernelGGL(kb_heur_rows, dim3((d.M + 3) / 4, ntiles), dim3(256), 0, e->stream, d);
+  if (d.digest && roots) launch_ls_heur_rows(e, *roots, ntiles);
+  else if (d.digest) hipLaunchKernelGGL(kb_heur_rows, dim3((d.M + 3) / 4, ntiles), dim3(256), 0, e->stream, d);
   if (e->pq) hipLaunchKernelGGL(kb_obj_rows<true>, dim3((d.n + 3) / 4, ntiles), dim3(256), 0, e->stream, d);
   else hipLaunchKernelGGL(kb_obj_rows<false>, dim3((d.n + 3) / 4, ntiles), dim3(256), 0, e->stream, d);
   hipLaunchKernelGGL(kb_obj_sum, dim3(ntiles), dim3(1024), 0, e->stream, d);

@@ -11,6 +11,10 @@ set up itself (`_Tree`).  One wave:
     `Node.solve`) on a solver without it -- the generic wave, which is the restatement the CPU tests run;
   * every tree runs the unchanged `Workspace.bound_and_branch` on its leaf and counts the node.
 
+`run_device` is the same wave loop in the library (`OSQP.solve_trees_lockstep`, miosqp_qp_solve_trees_lockstep): the
+leaves of all trees stay in device slots, the per-tree logic runs in C++ and Python sees the B results.  It is asked for
+by name: `solve_many(lockstep="device")`.
+
 A node is a pure function of (q, l, u, x0, y0), so every tree makes exactly the decisions of its sequential solve
 (`update_vectors` + `set_x0` + `solve`), node for node.  The wave waits for its slowest column; trees finish at
 different waves and later waves are narrower.
@@ -92,8 +96,9 @@ def run(model, todo, Q, L, U, up, XI, instances, out, batched):
     """The trees of instances `todo` in lock step; fills out[k] with what the sequential path of solve_many puts there.
     Q, L, U: instance-major vectors; up, XI: upper bound and point of an accepted x0 (inf without one).  batched: the
     wave is one solve_batch_q; otherwise the generic wave, after which the solver's q is put back.  Leaves
-    work.lockstep = dict(instances, waves, nodes, batched, max_width, iters_max, iters_mean, finished_at): per wave the
-    largest and the mean ADMM iteration count of its columns; per instance the wave after which its tree was done."""
+    work.lockstep = dict(instances, waves, nodes, batched, max_width, iters_max, iters_mean, finished_at, driver): per
+    wave the largest and the mean ADMM iteration count of its columns; per instance the wave after which its tree was
+    done; driver 'python' (run_device leaves 'device')."""
     work, data = model.work, model.work.data
     rule = work.settings['tree_explor_rule']
     t0 = time()
@@ -103,7 +108,7 @@ def run(model, todo, Q, L, U, up, XI, instances, out, batched):
         own = inst.get('l') is not None or inst.get('u') is not None
         trees[k] = _Tree(work, Q[k].copy(), L[k].copy(), U[k].copy(), own, float(up[k]), XI[k].copy())
     info = dict(instances=len(todo), waves=0, nodes=0, batched=bool(batched), max_width=0, iters_max=[], iters_mean=[],
-                finished_at={})
+                finished_at={}, driver='python')
     q_keep = data.q
     try:
         while True:
@@ -144,3 +149,48 @@ def run(model, todo, Q, L, U, up, XI, instances, out, batched):
         tree.get_return_solution()
         out[k] = dict(x=np.array(tree.x, dtype=float), upper_glob=tree.upper_glob, status=tree.status,
                       nodes=tree.iter_num - 1, osqp_iter=tree.osqp_iter, run_time=dt / len(todo))
+
+
+def device_supported(work):
+    """the device driver needs the HIP engine's entry and the on-device digest (set_root)"""
+    return hasattr(work.solver, 'solve_trees_lockstep') and work.root_on_device and work.data.n_int > 0
+
+
+def run_device(model, todo, Q, L, U, up, XI, instances, out, capacity=0):
+    """`run` in the library: the trees of instances `todo` advance in lock step inside ONE call of
+    `OSQP.solve_trees_lockstep` -- leaves in device slots, the tree logic in C++ (csrc/lockstep_trees.hpp), per wave five
+    integers per column up and a 64-byte record per column down.  Fills out[k] with the dicts `run` forms and leaves
+    work.lockstep with the same keys, driver='device', plus grown (times the slot store grew), iters_slowest,
+    iters_all, device_time, run_time and host_time (the library's call and, of it, the tree logic between the waves).  The value of an incumbent found by the rounding heuristic is the device's sum
+    (`run` recomputes it with numpy: ~1e-12 relative apart), as in the hosted search.  The model's q, l, u, leaves and
+    counters are not touched.  capacity: starting number of node slots (0: the engine's default)."""
+    work, data, st = model.work, model.work.data, model.work.settings
+    todo = list(todo)
+    n, M = data.n, data.m + data.n_int
+    t0 = time()
+    any_inc = bool(np.any(np.isfinite(up[todo])))
+    X, infos, s = work.solver.solve_trees_lockstep(
+        Q[todo], L[todo], U[todo], np.zeros((len(todo), n)), np.zeros((len(todo), M)), up[todo],
+        XI[todo] if any_inc else None, st['tree_explor_rule'], st['max_iter_bb'], capacity=capacity)
+    dt = time() - t0
+    work.lockstep = dict(instances=len(todo), waves=s.waves, nodes=int(s.nodes), batched=True, max_width=s.max_width,
+                         iters_max=s.iters_max, iters_mean=s.iters_mean,
+                         finished_at={k: int(s.finished_at[j]) for j, k in enumerate(todo)}, driver='device',
+                         grown=s.grown, iters_slowest=int(s.iters_slowest), iters_all=int(s.iters_all),
+                         device_time=s.device_time, run_time=s.run_time, host_time=s.host_time)
+    for j, k in enumerate(todo):
+        info = infos[j]
+        upper = info.upper_glob
+        # workspace.py:352-373 decides on the loop counter (iter_num = nodes + 1), as solve_many's one-launch path does
+        finished = int(info.nodes) + 1 < st['max_iter_bb']
+        if upper != np.inf:
+            status = bnb.MI_SOLVED if finished else bnb.MI_MAX_ITER_FEASIBLE
+        elif upper >= 0:
+            status = bnb.MI_PRIMAL_INFEASIBLE if finished else bnb.MI_MAX_ITER_UNSOLVED
+        else:
+            status = bnb.MI_DUAL_INFEASIBLE
+        x = X[j].copy() if (info.found or np.isfinite(up[k])) else np.empty(n)
+        if status in (bnb.MI_SOLVED, bnb.MI_MAX_ITER_FEASIBLE):
+            x[data.i_idx] = np.round(x[data.i_idx])
+        out[k] = dict(x=x, upper_glob=upper, status=status, nodes=int(info.nodes), osqp_iter=int(info.osqp_iter),
+                      run_time=dt / len(todo))

@@ -428,6 +428,54 @@ class OSQP(object):
             raise ValueError("Lower bound must be lower than or equal to upper bound")
         return x, list(infos)
 
+    def solve_trees_lockstep(self, q, l, u, x0, y0, upper0, x_inc0, tree_explor_rule, max_iter_bb, capacity=0,
+                             node_hviol=0):
+        """B MIQPs on this engine's factor for problems of any size (arrays as for solve_trees): the trees advance in lock
+        step, one node of every unfinished tree per wave, driven in C++ on device-resident leaves
+        (miosqp_qp_solve_trees_lockstep).  capacity: starting number of node slots (0: the engine's default).
+        node_hviol: debug, > 0 records the rounded point's violation at each tree's first `node_hviol` nodes.
+        Returns (x B x n, [TreeInfo], stats): stats has waves, nodes, max_width, grown, iters_slowest, iters_all,
+        device_time, run_time, host_time (the tree logic between the waves), the per-wave lists width, iters_max, iters_mean (the first 65536 waves), finished_at
+        (per instance) and node_hviol (B x node_hviol, NaN where there was no node; None when not asked for)."""
+        q = np.ascontiguousarray(q, dtype=np.float64)
+        B = q.shape[0]
+        l, u = np.ascontiguousarray(l, dtype=np.float64), np.ascontiguousarray(u, dtype=np.float64)
+        x0, y0 = np.ascontiguousarray(x0, dtype=np.float64), np.ascontiguousarray(y0, dtype=np.float64)
+        if B < 1 or q.shape != (B, self.n) or x0.shape != (B, self.n) or l.shape != (B, self.m) or u.shape != (B, self.m) \
+                or y0.shape != (B, self.m):
+            raise ValueError("solve_trees_lockstep: instance-major arrays (B x n, B x M)")
+        up = np.minimum(np.ascontiguousarray(upper0, dtype=np.float64).reshape(B), 1.7e308)
+        xin = None if x_inc0 is None else np.ascontiguousarray(x_inc0, dtype=np.float64).reshape(B, self.n)
+        x = np.zeros((B, self.n))
+        infos = (_lib.TreeInfo * B)()
+        max_iter_bb = 2 ** 31 - 1 if not np.isfinite(max_iter_bb) else int(min(int(max_iter_bb), 2 ** 31 - 1))
+        wcap = max(1, min(max_iter_bb, 65536))
+        width, imax = np.zeros(wcap, dtype=np.int32), np.zeros(wcap, dtype=np.int32)
+        imean, fin = np.zeros(wcap), np.zeros(B, dtype=np.int32)
+        hv = np.full((B, int(node_hviol)), np.nan) if node_hviol > 0 else None
+        st = _lib.LockstepStats()
+        st.wave_cap = wcap
+        st.wave_width, st.wave_iter_max, st.wave_iter_mean = _lib.as_i(width), _lib.as_i(imax), _lib.as_d(imean)
+        st.finished_at = _lib.as_i(fin)
+        if hv is not None:
+            st.node_hviol, st.node_cap = _lib.as_d(hv), int(node_hviol)
+        rc = self._lib.miosqp_qp_solve_trees_lockstep(
+            self._h, B, _lib.as_d(q), _lib.as_d(l), _lib.as_d(u), _lib.as_d(x0), _lib.as_d(y0), _lib.as_d(up),
+            None if xin is None else _lib.as_d(xin), int(tree_explor_rule), max_iter_bb, int(capacity), _lib.as_d(x), infos,
+            C.byref(st))
+        _check(rc, "solve_trees_lockstep")
+        if rc == 1:
+            msg = _lib.last_error()
+            if "branching" in msg:
+                raise RuntimeError("branching produced l > u")
+            raise ValueError("Lower bound must be lower than or equal to upper bound")
+        k = min(st.waves, wcap)
+        stats = types.SimpleNamespace(
+            waves=st.waves, nodes=st.nodes, max_width=st.max_width, grown=st.grown, iters_slowest=st.iters_slowest,
+            iters_all=st.iters_all, device_time=st.device_time, run_time=st.run_time, host_time=st.host_time, width=width[:k].tolist(),
+            iters_max=imax[:k].tolist(), iters_mean=imean[:k].tolist(), finished_at=fin.tolist(), node_hviol=hv)
+        return x, list(infos), stats
+
     # -- node-at-a-time branch and bound driven from the host in C++ (miosqp_qp_search_*) --------------
     def search_create(self, capacity):
         _check(self._lib.miosqp_qp_search_create(self._h, int(capacity)), "search_create")
