@@ -450,6 +450,52 @@ int miosqp_qp_solve_trees_lockstep(miosqp_qp_engine *e, int32_t B, const double 
                                    int32_t tree_explor_rule, int32_t max_iter_bb, int32_t capacity,
                                    double *x_out, miosqp_tree_info *info, miosqp_lockstep_stats *stats);
 
+/* ---- the same B trees on columns that are refilled between chunks ---------------------------------------
+ * miosqp_qp_solve_trees_lockstep without the wave.  The engine's batch runs in chunks of check_termination iterations
+ * with one termination test each; here a column holds one node of one tree, counts its own iterations from the chunk it
+ * was loaded in and reaches max_iter on its own.  After every chunk the columns the test has just decided are harvested
+ * on the device (unscale, clamp, digest, objective, the rounded point against the INSTANCE's root rows, solution into
+ * the node's slot, children into the two slots reserved when the column was filled, one 64-byte record per column),
+ * their trees absorb the records on the host (bound_and_branch, workspace.py:282-334) and -- at that same boundary --
+ * every free column is loaded with the next leaf (choose_leaf, workspace.py:128-155) of a tree that has no node in
+ * flight and can continue, lowest tree index first, lowest free column first.  A tree has at most ONE node in flight:
+ * its next leaf is chosen only after its previous node was absorbed, so every tree runs the loop of solver.py:85-123
+ * node for node, exactly as its sequential solve and as a tree of miosqp_qp_solve_trees_lockstep does, whatever the
+ * other trees do (a node is a pure function of q, l, u, x0, y0): status, node and iteration counts are those of the
+ * sequential solve, upper_glob and x those of miosqp_qp_solve_trees_lockstep bit for bit.  A column that cannot be
+ * refilled (every tree that can continue has its node in flight) stays decided until a tree is free.
+ * Columns: min(B, the engine's batch width = max_batch rounded up to 64, at most 1024).  Per boundary the host reads
+ * the list of harvested columns with their records (one download, one synchronisation) and sends six integers per
+ * filled column and the incumbent pairs (one upload). */
+typedef struct miosqp_refill_stats {
+  int32_t chunks;           /* chunks run: with B <= columns, the largest iteration count of a tree / check_termination */
+  int32_t columns;          /* columns used */
+  int32_t grown;            /* times the slot store grew */
+  int32_t chunk_cap;        /* IN: entries chunk_busy can take; later chunks are not recorded */
+  int64_t nodes;            /* over all trees */
+  int64_t iters_all;        /* ADMM iterations over all nodes */
+  int64_t col_chunks_busy;  /* sum over chunks of the columns holding a node in flight ... */
+  int64_t col_chunks_total; /* ... and of the columns: busy / total is the occupancy */
+  double device_time;       /* seconds between the events around the call (the waits for the host at the boundaries included) */
+  double run_time;          /* wall seconds */
+  double host_time;         /* of those: the tree logic on the host (absorbing, choosing, filling), between the chunks */
+  double chunk_time;        /* device seconds inside the chunks themselves (iterations + test): device_time - chunk_time is the boundaries' */
+  int64_t nodes_max_iter;   /* nodes whose column ended MAX_ITER_REACHED, by its own count ... */
+  int64_t iters_max_iter;   /* ... and their iterations: nodes_max_iter * max_iter, whatever chunk each was loaded in */
+  int32_t *chunk_busy;      /* IN, optional (NULL: not wanted): busy columns per chunk */
+  int32_t *finished_at;     /* IN, optional, B entries: the chunk after which tree b was done (0: it had nothing to do) */
+} miosqp_refill_stats;
+
+/* Arguments, layouts, info[b], capacity and errors as for miosqp_qp_solve_trees_lockstep.  Also MIOSQP_EARG when
+ * settings.max_iter is not a multiple of settings.check_termination (a column counts whole chunks, as
+ * miosqp_qp_pool_create demands) and while pool chunks are in flight; the call marks the leaf pool's columns as used
+ * (miosqp_qp_pool_reset before the next miosqp_qp_pool_launch), as miosqp_qp_solve_batch does.  The engine's own q,
+ * bounds, root and search state are neither read nor written. */
+int miosqp_qp_solve_trees_refill(miosqp_qp_engine *e, int32_t B, const double *q, const double *l, const double *u,
+                                 const double *x0, const double *y0, const double *upper0, const double *x_inc0,
+                                 int32_t tree_explor_rule, int32_t max_iter_bb, int32_t capacity,
+                                 double *x_out, miosqp_tree_info *info, miosqp_refill_stats *stats);
+
 /* ---- node-at-a-time branch and bound, driven from the host in C++ -------------------------------------
  * The loop of /root/reference/miosqp/solver.py:65-172 (choose_leaf -> Node.solve -> bound_and_branch, workspace.py:
  * 113-155, 274-334) for problems of any size, one relaxation at a time in whatever form the engine uses for single

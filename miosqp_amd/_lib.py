@@ -43,6 +43,14 @@ class LockstepStats(C.Structure):
                 ("finished_at", ip), ("node_hviol", dp), ("node_cap", C.c_int32), ("reserved", C.c_int32)]
 
 
+class RefillStats(C.Structure):
+    _fields_ = [("chunks", C.c_int32), ("columns", C.c_int32), ("grown", C.c_int32), ("chunk_cap", C.c_int32),
+                ("nodes", C.c_int64), ("iters_all", C.c_int64), ("col_chunks_busy", C.c_int64),
+                ("col_chunks_total", C.c_int64), ("device_time", C.c_double), ("run_time", C.c_double),
+                ("host_time", C.c_double), ("chunk_time", C.c_double), ("nodes_max_iter", C.c_int64),
+                ("iters_max_iter", C.c_int64), ("chunk_busy", ip), ("finished_at", ip)]
+
+
 class SearchInfo(C.Structure):
     _fields_ = [("nodes", C.c_int64), ("osqp_iter", C.c_int64), ("open_leaves", C.c_int32), ("free_slots", C.c_int32),
                 ("improved", C.c_int32), ("reserved", C.c_int32), ("upper_glob", C.c_double), ("lower_glob", C.c_double),
@@ -114,6 +122,8 @@ SYMBOLS = {
                                         C.POINTER(TreeInfo)]),
     "miosqp_qp_solve_trees_lockstep": (C.c_int, [C.c_void_p, C.c_int32, dp, dp, dp, dp, dp, dp, dp, C.c_int32, C.c_int32,
                                                  C.c_int32, dp, C.POINTER(TreeInfo), C.POINTER(LockstepStats)]),
+    "miosqp_qp_solve_trees_refill": (C.c_int, [C.c_void_p, C.c_int32, dp, dp, dp, dp, dp, dp, dp, C.c_int32, C.c_int32,
+                                               C.c_int32, dp, C.POINTER(TreeInfo), C.POINTER(RefillStats)]),
     "miosqp_qp_search_create": (C.c_int, [C.c_void_p, C.c_int32]),
     "miosqp_qp_search_reset": (C.c_int, [C.c_void_p]),
     "miosqp_qp_search_add_leaf": (C.c_int, [C.c_void_p, dp, dp, dp, dp, C.c_int32, C.c_double]),

@@ -1225,6 +1225,13 @@ class MIOSQP(object):
         no interpreter runs per node; the trees are those of True, the heuristic incumbent's value is the device's sum
         (1e-12 relative).  ValueError when the solver lacks the entry or the settings are not the lock-step trees'.
         Asked for by name only: None never chooses it (DESIGN 3k has the measurements).
+        "refill": the trees of "device" without the wave (`lockstep.run_refill`, `OSQP.solve_trees_refill`): a column of
+        the batch holds one node of one tree and counts its own iterations; after every chunk of check_termination
+        iterations the decided columns are harvested and, at that same boundary, loaded again with the next leaf of a
+        tree that has no node in flight (a tree still has one node in flight at the most), so no column waits for the
+        slowest of a wave and B trees need only min(B, max_batch) columns.  Status, nodes and iterations are those of
+        False, upper_glob and x those of "device" bit for bit.  Needs what "device" needs and max_iter a multiple of
+        check_termination (ValueError otherwise).  Asked for by name only (DESIGN 3k has the measurements).
 
         polish=True: the incumbents are then polished together by `polish_many` (one more launch on the HIP engine) and
         every dict gains polished, polish_rounds, pri_after, dua_after.  Polishing many instances is asked for per call:
@@ -1299,16 +1306,25 @@ class MIOSQP(object):
         if isinstance(lockstep, str):
             # the driver in the library, asked for by name (the default is not this one)
             from miosqp_amd import lockstep as ls
-            if lockstep != "device":
-                raise ValueError('solve_many: lockstep must be None, True, False or "device"')
-            if not ls.device_supported(work):
+            if lockstep not in ("device", "refill"):
+                raise ValueError('solve_many: lockstep must be None, True, False, "device" or "refill"')
+            if lockstep == "device" and not ls.device_supported(work):
                 raise ValueError('solve_many(lockstep="device") needs the HIP engine with solve_trees_lockstep and the '
                                  'device digest')
+            if lockstep == "refill" and not ls.refill_supported(work):
+                raise ValueError('solve_many(lockstep="refill") needs the HIP engine with solve_trees_refill and the '
+                                 'device digest')
             if not ls.supported(work):
-                raise ValueError('solve_many(lockstep="device") needs branching_rule 0, primal_heuristic 0 and '
-                                 'tree_explor_rule 0-3')
+                raise ValueError('solve_many(lockstep="%s") needs branching_rule 0, primal_heuristic 0 and '
+                                 'tree_explor_rule 0-3' % lockstep)
+            if lockstep == "refill":
+                qs = work.solver.settings  # (the engine's own: aliases and defaults resolved)
+                mi, ct = int(qs.max_iter), int(qs.check_termination)
+                if ct < 1 or mi % ct != 0:
+                    raise ValueError('solve_many(lockstep="refill") needs max_iter to be a multiple of check_termination '
+                                     '(a column counts whole chunks): max_iter %d, check_termination %d' % (mi, ct))
             if redo:
-                ls.run_device(self, redo, Q, L, U, up, XI, instances, out)
+                (ls.run_refill if lockstep == "refill" else ls.run_device)(self, redo, Q, L, U, up, XI, instances, out)
                 redo = []
         if redo and lockstep is not False:
             from miosqp_amd import lockstep as ls

@@ -40,6 +40,7 @@
 #include "polish_many.hpp"  // polishing of many small instances in one launch (polish_many.hip)
 #include "polish_many_large.hpp"  // ... and of larger ones, S in a slab of device scratch per workgroup (polish_many_large.hip)
 #include "lockstep_trees.hpp"  // the tree logic of B trees in lock step (plain C++; host_lockstep.inc drives it)
+#include "lockstep_refill.hpp"  // which tree goes into which free column when the columns are refilled between chunks (plain C++; host_refill.inc drives it)
 
 #define QP_INFTY 1e30
 #define QP_MIN_SCALING 1e-4
@@ -248,6 +249,7 @@ struct CoopNode {
 #include "host_search.inc"  // node-at-a-time branch and bound driven from the host in C++ (C ABI miosqp_qp_search_*)
 #include "host_stream.inc"  // the host side of the streaming search in C++ (C ABI miosqp_qp_stream_*)
 #include "host_lockstep.inc"  // B trees in lock step driven from the host in C++ (C ABI miosqp_qp_solve_trees_lockstep)
+#include "host_refill.inc"  // the same trees on columns refilled between chunks (C ABI miosqp_qp_solve_trees_refill)
 
 // ------------------------------------------------------------------------------------------
 // C ABI

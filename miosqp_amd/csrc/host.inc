@@ -186,6 +186,9 @@ struct miosqp_qp_engine {
   // captured chunks per tile count; set [1] holds the per-column-cost instantiations (solve_batch_q), set [0] the others
   hipGraphExec_t xb_full[2][16] = {}, xb_tail[2][16] = {};
   hipGraph_t gb_full[2][16] = {}, gb_tail[2][16] = {};
+  // solve_trees_refill (host_refill.inc): the chunk with the streaming test on that driver's own column arrays, per tile count
+  hipGraphExec_t xr_full[16] = {};
+  hipGraph_t gr_full[16] = {};
   int pq = 0;                 // 1 while a solve_batch_q slice is queued: launches and chunk graphs take the <PQ = true> kernels
   double *hb_q = nullptr;     // pinned staging of a slice's raw costs (solve_batch_q, allocated on its first call)
   bool compact = true;   // compaction of converged columns in solve_batch (MIOSQP_COMPACT=0 disables)
@@ -1260,6 +1263,12 @@ void drop_chunk_graphs(miosqp_qp_engine *e) {
       e->xb_full[s][k] = e->xb_tail[s][k] = nullptr;
       e->gb_full[s][k] = e->gb_tail[s][k] = nullptr;
     }
+  for (int k = 0; k < 16; k++) {
+    if (e->xr_full[k]) hipGraphExecDestroy(e->xr_full[k]);
+    if (e->gr_full[k]) hipGraphDestroy(e->gr_full[k]);
+    e->xr_full[k] = nullptr;
+    e->gr_full[k] = nullptr;
+  }
 }
 
 // which: 0 forward sweep, 1 backward sweep; workgroup shape from e->bd_cfg (row groups x k slices)

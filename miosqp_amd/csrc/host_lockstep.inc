@@ -23,7 +23,10 @@ struct LockstepStore {
   std::vector<double> stage;
   miosqp::lockstep::Slots slots;
   std::vector<miosqp::lockstep::Tree> trees;
+  void *refill = nullptr;  // RefillCols (host_refill.inc): the per-column arrays of solve_trees_refill
 };
+
+void refill_free(void *p);  // (host_refill.inc)
 
 // kls_heur_rows in place of kb_heur_rows at the end of slice_run (declared in host.inc; the kernel is used here, see kernels_lockstep.inc)
 void launch_ls_heur_rows(miosqp_qp_engine *e, const LsRoots &roots, int ntiles) {
@@ -38,6 +41,7 @@ void lockstep_free(void *p) {
   if (L->d_trip) hipFree(L->d_trip);
   if (L->h_trip) hipHostFree(L->h_trip);
   if (L->h_rec) hipHostFree(L->h_rec);
+  refill_free(L->refill);
   delete L;
 }
 

@@ -4,8 +4,9 @@
 // scaled cost and incumbent.  A wave is the unchanged lock-step batch (slice_run) between kls_gather and kls_scatter.
 // The kernels here are copies and row sums over vector loads and stores: no spin wait, no hand-off between workgroups,
 // no whole-chip launch.
-// They are templates (one instantiation each, LS = 0) for the sake of the code object's layout: a template is emitted where
-// it is first used, and every use is in host_lockstep.inc, the last file of the translation unit -- so the four kernels
+// They are templates (one instantiation each, LS = 0; kls_heur_rows a second one for the refilled columns at the end of this
+// file) for the sake of the code object's layout: a template is emitted where it is first used, and every use is in
+// host_lockstep.inc and host_refill.inc, the last files of the translation unit -- so these kernels
 // sit behind every other kernel and adding them moves none of those (the exchange loops of the cooperative kernels are
 // tuned to a fraction of a microsecond per iteration).
 
@@ -62,6 +63,9 @@ __global__ __launch_bounds__(256) void kls_gather(Dev d, LsDev ls, const int *__
 // product, the same expression -- for a tree whose root is the engine's, the same bits
 template <int LS>
 __global__ __launch_bounds__(256) void kls_heur_rows(Dev d, LsRoots r) {
+  if constexpr (LS == 1) {  // refilled columns (below): only the tiles with a column harvested at this boundary
+    if (!d.t_has[blockIdx.y]) return;
+  }
   BSETUP
   const int row = blockIdx.x * 4 + wv;
   if (row >= d.M) return;
@@ -162,5 +166,280 @@ __global__ __launch_bounds__(256) void kls_incumbent(Dev d, LsDev ls, const int 
   for (int j = threadIdx.x; j < d.n_int; j += 256) {
     const size_t i = (size_t)d.i_idx[j];
     ls.inc[t * n + i] = rint(ls.x[s * n + i]);
+  }
+}
+
+// ------------------------------------------------------------------------------------------
+// Refilled columns (host_refill.inc, C ABI miosqp_qp_solve_trees_refill): the same trees on columns that never wait for a
+// wave.  The chunk is the streaming one (Dev.stream = 1: a column counts from c_start and reaches max_iter on its own,
+// kb_check_decide); at every chunk boundary the columns the test has just decided are harvested IN PLACE -- the masked
+// epilogue kb_finish / kls_heur_rows / kb_obj_rows<true> / kb_obj_sum through c_harv and t_has, the expressions of a wave's
+// epilogue -- scattered to their slots with their children and records (kls_scatter_cols), and the columns the host hands
+// back are loaded from the store (kls_refill + kls_refill_z: the bits kb_prepare<true> and kb_warm_z give a column of a
+// wave).  Decided columns are frozen by the iteration kernels (c_done), so a column nobody refills simply waits.
+// Like the kernels above: copies and row sums over vector loads and stores, one launch each, no spin wait, no hand-off
+// between workgroups; templates instantiated from host_refill.inc only, behind every other kernel of the code object.
+
+struct RfHead {  // first 64 bytes of what the host reads back per boundary
+  int count;     // columns harvested at this boundary (their numbers follow in `list`, in column order)
+  int pad;       // Ctrl.pad: the chunk's persistent launch was called off (1) or timed out (> 1)
+  int iter;      // Ctrl.iter after the chunk
+  int res[13];
+};
+
+struct RfDev {
+  int *c_trip;             // [Bs][LS_TRIP]: what each column holds, as a wave's triples (kls_heur_rows reads the tree there)
+  int *c_slot, *c_tree;    // [Bs] the same slot and tree on their own: c_node of kb_finish (pl_lo / pl_hi) and of kb_obj_rows<true> (b_qraw)
+  int *c_ident;            // [Bs] b -> b: c_node of kls_heur_rows
+  int *c_busy;             // [Bs] 1: the column holds a node that has not been harvested
+  int *c_fill, *t_fill;    // [Bs], [16]: the boundary (epoch) at which the column / a column of the tile was last loaded
+  RfHead *head;            // | head | list[Bs] | rec[Bs] |, one device block: ONE download per boundary
+  int *list;
+  LsRec *rec;
+  int C;                   // columns in use (the rest of the last tile is padding: decided, never busy)
+};
+
+// before the first fill: every column decided and idle (kb_reset, kb_prepare<true> and kb_warm_z with B = 0 have zeroed the
+// working vectors, as a wave zeroes its padding)
+template <int LS>
+__global__ __launch_bounds__(256) void kls_cols_reset(Dev d, RfDev r) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b < d.Bs) {
+    for (int k = 0; k < LS_TRIP; k++) r.c_trip[LS_TRIP * b + k] = 0;
+    r.c_slot[b] = r.c_tree[b] = 0;
+    r.c_ident[b] = b;
+    r.c_busy[b] = 0;
+    r.c_fill[b] = 0;
+    d.c_start[b] = 0;
+    d.c_harv[b] = 0;
+  }
+  if (b < 16) {
+    r.t_fill[b] = 0;
+    d.t_has[b] = 0;
+  }
+}
+
+// After the chunk's test: the columns decided in this chunk (busy and done), their list in column order, the masks of
+// the epilogue.  One workgroup (<= 1024 columns), the ranks as kp_assign takes them.
+template <int LS>
+__global__ __launch_bounds__(1024) void kls_harvest(Dev d, RfDev r) {
+  __shared__ int s_wave[16];
+  const int t = threadIdx.x;
+  const bool in = t < d.Bs;
+  const bool harv = in && t < r.C && r.c_busy[t] != 0 && d.c_done[t] != 0;
+  int total;
+  const int rank = block_rank(harv, s_wave, &total);
+  if (in) d.c_harv[t] = harv ? 1 : 0;
+  if (harv) {
+    r.list[rank] = t;
+    r.c_busy[t] = 0;
+  }
+  const unsigned long long m = __ballot(harv);
+  if ((t & 63) == 0) d.t_has[t >> 6] = m != 0ull;
+  if (t == 0) {
+    r.head->count = total;
+    r.head->pad = d.ctrl->pad;
+    r.head->iter = d.ctrl->iter;
+  }
+}
+
+// kls_scatter for the harvested columns of the tile: answers into their slots, the children of fractional nodes into the
+// slots reserved when the column was filled, the record at the column's number.  grid as kls_scatter.
+template <int LS>
+__global__ __launch_bounds__(256) void kls_scatter_cols(Dev d, LsDev ls, RfDev rf) {
+  __shared__ double tile[64][65];
+  __shared__ int slot_of[64];
+  if (!d.t_has[blockIdx.y]) return;
+  const int n = d.n, M = d.M, p = d.n_int;
+  const int nxt = (n + 63) / 64, nyt = (M + 63) / 64;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int b0 = blockIdx.y * 64;
+  const size_t Bs = (size_t)d.Bs;
+  if (threadIdx.x < 64) {
+    const int b = b0 + (int)threadIdx.x;
+    slot_of[threadIdx.x] = d.c_harv[b] ? rf.c_slot[b] : -1;
+  }
+  if ((int)blockIdx.x < nxt + nyt) {
+    const bool isx = (int)blockIdx.x < nxt;
+    const int rows = isx ? n : M, r0 = (isx ? (int)blockIdx.x : (int)blockIdx.x - nxt) * 64;
+    const double *src = isx ? d.b_xfin : d.b_yfin;
+    double *dst = isx ? ls.x : ls.y;
+    for (int r = wv; r < 64; r += 4)
+      if (r0 + r < rows) tile[r][lane] = src[(size_t)(r0 + r) * Bs + b0 + lane];
+    __syncthreads();
+    for (int cc = wv; cc < 64; cc += 4) {
+      const int s = slot_of[cc];
+      if (s >= 0 && r0 + lane < rows) dst[(size_t)s * rows + r0 + lane] = tile[lane][cc];
+    }
+    return;
+  }
+  __syncthreads();
+  for (int cc = 0; cc < 64; cc++) {
+    if (slot_of[cc] < 0) continue;
+    const int b = b0 + cc;
+    const int *tr = rf.c_trip + LS_TRIP * b;
+    const size_t s = (size_t)tr[LS_SLOT], c0 = (size_t)tr[LS_CHILD0], c1 = (size_t)tr[LS_CHILD1];
+    const int intinf = d.c_intinf[b], nv = d.c_nextvar[b];
+    int crossed = 0;
+    if (intinf > 0 && nv >= 0) {
+      const double xv = d.b_xfin[(size_t)d.i_idx[nv] * Bs + b];
+      const double dn = floor(xv), up = ceil(xv);
+      for (int k = threadIdx.x; k < p; k += 256) {
+        const double lo = ls.lo[s * p + k], hi = ls.hi[s * p + k];
+        ls.lo[c0 * p + k] = lo;
+        ls.hi[c0 * p + k] = k == nv ? dn : hi;
+        ls.lo[c1 * p + k] = k == nv ? up : lo;
+        ls.hi[c1 * p + k] = hi;
+        if (k == nv) crossed = lo > dn || up > hi;  // one thread sees position nv: it also writes the record
+      }
+    }
+    const bool writer = intinf > 0 && nv >= 0 ? ((int)threadIdx.x == nv % 256) : threadIdx.x == 0;
+    if (writer) {
+      LsRec g;
+      g.status = d.c_status[b];
+      g.iter = d.c_iter[b];
+      g.int_inf = intinf;
+      g.nextvar = nv;
+      g.node = b;
+      g.crossed = crossed;
+      g.pad[0] = g.pad[1] = 0;
+      g.lower = d.c_lower[b];
+      g.hviol = d.c_hviol[b];
+      g.hobj = d.c_hobj[b];
+      g.pad2 = 0.0;
+      rf.rec[b] = g;
+    }
+  }
+}
+
+// The columns the host filled at this boundary: fills[k] = (column, tree, slot, warm-start slot, child slots).  Bounds,
+// warm start and cost from the store into the column's scaled working vectors -- per entry the expressions of
+// kb_prepare<true> on what kls_gather would have staged --, then the column's bookkeeping.  grid (tiles of 64 rows of the
+// n-vectors, then of the M-vectors, then one block for the bookkeeping; tiles of 64 fills).  The store is slot-major and the
+// working set batch-fastest: a tile goes through LDS so that the loads (64 consecutive entries of a slot) and the stores
+// (the fills' columns of a row: consecutive while the columns are) are both as contiguous as they can be.
+constexpr int RF_FILL = 6;
+template <int LS>
+__global__ __launch_bounds__(256) void kls_refill(Dev d, LsDev ls, RfDev rf, const int *__restrict__ fills, int nfill, int epoch) {
+  __shared__ double tile[64][65];
+  __shared__ int s_col[64], s_tree[64], s_slot[64], s_warm[64];
+  const int n = d.n, M = d.M, m = d.m_orig, p = d.n_int;
+  const int nxt = (n + 63) / 64, nyt = (M + 63) / 64;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int k0 = blockIdx.y * 64;
+  const size_t Bs = (size_t)d.Bs;
+  if (threadIdx.x < 64) {
+    const int k = k0 + (int)threadIdx.x;
+    const bool on = k < nfill;
+    s_col[threadIdx.x] = on ? fills[RF_FILL * k] : -1;
+    s_tree[threadIdx.x] = on ? fills[RF_FILL * k + 1] : 0;
+    s_slot[threadIdx.x] = on ? fills[RF_FILL * k + 2] : 0;
+    s_warm[threadIdx.x] = on ? fills[RF_FILL * k + 3] : 0;
+  }
+  __syncthreads();
+  const int mycol = s_col[lane];  // the column of fill `lane` (store phase: lane = fill)
+  if ((int)blockIdx.x < nxt) {
+    const int r0 = (int)blockIdx.x * 64;
+    // x0 = the warm-start slot's solution
+    for (int e = wv; e < 64; e += 4)
+      if (s_col[e] >= 0 && r0 + lane < n) tile[e][lane] = ls.x[(size_t)s_warm[e] * n + r0 + lane];
+    __syncthreads();
+    double xs[16];
+#pragma unroll
+    for (int i = 0; i < 16; i++) {
+      const int j = r0 + wv + 4 * i;
+      xs[i] = 0.0;
+      if (mycol >= 0 && j < n) {
+        xs[i] = d.Dinv[j] * tile[lane][wv + 4 * i];
+        d.b_x[(size_t)j * Bs + mycol] = xs[i];
+        d.b_dx[(size_t)j * Bs + mycol] = 0.0;
+      }
+    }
+    __syncthreads();
+    // the tree's scaled cost
+    for (int e = wv; e < 64; e += 4)
+      if (s_col[e] >= 0 && r0 + lane < n) tile[e][lane] = ls.qs[(size_t)s_tree[e] * n + r0 + lane];
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 16; i++) {
+      const int j = r0 + wv + 4 * i;
+      if (mycol >= 0 && j < n) {
+        const double qs = tile[lane][wv + 4 * i];
+        d.b_q[(size_t)j * Bs + mycol] = qs;
+        d.b_rx[(size_t)j * Bs + mycol] = d.sigma * xs[i] - qs;
+      }
+    }
+    return;
+  }
+  if ((int)blockIdx.x < nxt + nyt) {
+    const int r0 = ((int)blockIdx.x - nxt) * 64;
+    const int j_l = r0 + lane;  // load phase: lane = row
+    // l: the tree's root on the general rows, the node's on the integer rows
+    for (int e = wv; e < 64; e += 4)
+      if (s_col[e] >= 0 && j_l < M)
+        tile[e][lane] = j_l < m ? ls.root_l[(size_t)s_tree[e] * M + j_l] : ls.lo[(size_t)s_slot[e] * p + (j_l - m)];
+    __syncthreads();
+    for (int i = 0; i < 16; i++) {
+      const int j = r0 + wv + 4 * i;
+      if (mycol >= 0 && j < M) d.b_l[(size_t)j * Bs + mycol] = d.E[j] * fmax(tile[lane][wv + 4 * i], -QP_INFTY);
+    }
+    __syncthreads();
+    for (int e = wv; e < 64; e += 4)
+      if (s_col[e] >= 0 && j_l < M)
+        tile[e][lane] = j_l < m ? ls.root_u[(size_t)s_tree[e] * M + j_l] : ls.hi[(size_t)s_slot[e] * p + (j_l - m)];
+    __syncthreads();
+    for (int i = 0; i < 16; i++) {
+      const int j = r0 + wv + 4 * i;
+      if (mycol >= 0 && j < M) d.b_u[(size_t)j * Bs + mycol] = d.E[j] * fmin(tile[lane][wv + 4 * i], QP_INFTY);
+    }
+    __syncthreads();
+    // y0 = the warm-start slot's multipliers
+    for (int e = wv; e < 64; e += 4)
+      if (s_col[e] >= 0 && j_l < M) tile[e][lane] = ls.y[(size_t)s_warm[e] * M + j_l];
+    __syncthreads();
+    for (int i = 0; i < 16; i++) {
+      const int j = r0 + wv + 4 * i;
+      if (mycol >= 0 && j < M) {
+        d.b_y[(size_t)j * Bs + mycol] = d.c * d.Einv[j] * tile[lane][wv + 4 * i];
+        d.b_dy[(size_t)j * Bs + mycol] = 0.0;
+      }
+    }
+    return;
+  }
+  // the bookkeeping: one thread per fill
+  if (threadIdx.x < 64 && mycol >= 0) {
+    const int k = k0 + lane, b = mycol;
+    for (int i = 0; i < LS_TRIP; i++) rf.c_trip[LS_TRIP * b + i] = fills[RF_FILL * k + 1 + i];
+    rf.c_tree[b] = s_tree[lane];
+    rf.c_slot[b] = s_slot[lane];
+    rf.c_busy[b] = 1;
+    rf.c_fill[b] = epoch;
+    rf.t_fill[b >> 6] = epoch;  // (several fills of a tile store the same value)
+    d.c_start[b] = d.ctrl->iter;
+    d.c_status[b] = MIOSQP_QP_UNSOLVED;
+    d.c_iter[b] = 0;
+    d.c_pri[b] = d.c_dua[b] = d.c_obj[b] = 0.0;
+    d.c_lower[b] = __builtin_nan("");
+    d.c_done[b] = 0;
+  }
+}
+
+// kb_warm_z for the columns loaded at this boundary: the same row product over the tile, stored where the column was
+// just filled (the others are iterating or waiting: their z, wh and rx stay)
+template <int LS>
+__global__ __launch_bounds__(256) void kls_refill_z(Dev d, RfDev rf, int epoch) {
+  if (rf.t_fill[blockIdx.y] != epoch) return;
+  BSETUP
+  const int row = blockIdx.x * 4 + wv;
+  if (row >= d.M) return;
+  const double z = brow_dot(d.pc_idx, d.pc_A, d.pc_ptr[row], d.pc_ptr[row + 1], d.b_x + b, Bs);
+  if (rf.c_fill[b] != epoch) return;
+  const size_t o = row * Bs + b;
+  const double wh = z - d.rho_inv * d.b_y[o];
+  d.b_z[o] = z;
+  d.b_wh[whrow(d, row) * Bs + b] = wh;
+  if (row >= d.wh_m) {  // a bound row taken out of the products: its share of the right-hand side, r~ = rx + t
+    const int i = d.i_idx[row - d.m_orig];
+    d.b_rx[(size_t)i * Bs + b] += d.a_int[i] * wh;  // kls_refill wrote rx in the launch before; one row per variable
   }
 }

@@ -15,6 +15,12 @@ set up itself (`_Tree`).  One wave:
 leaves of all trees stay in device slots, the per-tree logic runs in C++ and Python sees the B results.  It is asked for
 by name: `solve_many(lockstep="device")`.
 
+`run_refill` drops the wave (`OSQP.solve_trees_refill`, miosqp_qp_solve_trees_refill): a column of the batch holds one
+node of one tree and counts its own iterations; after every chunk of check_termination iterations the decided columns
+are harvested and, at that same boundary, loaded again with the next leaf of a tree that has no node in flight.  A tree
+still has at most one node in flight, so its decisions are those of the wave drivers.  Asked for by name as well:
+`solve_many(lockstep="refill")`.
+
 A node is a pure function of (q, l, u, x0, y0), so every tree makes exactly the decisions of its sequential solve
 (`update_vectors` + `set_x0` + `solve`), node for node.  The wave waits for its slowest column; trees finish at
 different waves and later waves are narrower.
@@ -182,6 +188,52 @@ def run_device(model, todo, Q, L, U, up, XI, instances, out, capacity=0):
         info = infos[j]
         upper = info.upper_glob
         # workspace.py:352-373 decides on the loop counter (iter_num = nodes + 1), as solve_many's one-launch path does
+        finished = int(info.nodes) + 1 < st['max_iter_bb']
+        if upper != np.inf:
+            status = bnb.MI_SOLVED if finished else bnb.MI_MAX_ITER_FEASIBLE
+        elif upper >= 0:
+            status = bnb.MI_PRIMAL_INFEASIBLE if finished else bnb.MI_MAX_ITER_UNSOLVED
+        else:
+            status = bnb.MI_DUAL_INFEASIBLE
+        x = X[j].copy() if (info.found or np.isfinite(up[k])) else np.empty(n)
+        if status in (bnb.MI_SOLVED, bnb.MI_MAX_ITER_FEASIBLE):
+            x[data.i_idx] = np.round(x[data.i_idx])
+        out[k] = dict(x=x, upper_glob=upper, status=status, nodes=int(info.nodes), osqp_iter=int(info.osqp_iter),
+                      run_time=dt / len(todo))
+
+
+def refill_supported(work):
+    """the refill driver needs the HIP engine's entry and the on-device digest (set_root)"""
+    return hasattr(work.solver, 'solve_trees_refill') and work.root_on_device and work.data.n_int > 0
+
+
+def run_refill(model, todo, Q, L, U, up, XI, instances, out, capacity=0):
+    """`run_device` without the wave: the trees of instances `todo` inside ONE call of `OSQP.solve_trees_refill` -- a
+    column holds one node of one tree, the columns decided in a chunk are harvested at its boundary and refilled there
+    with the next leaf of a tree that has no node in flight (csrc/lockstep_refill.hpp, csrc/host_refill.inc).  Fills out[k]
+    with the dicts `run_device` forms (the same device sums: upper_glob and x are equal bit for bit) and leaves
+    work.lockstep = dict(driver='refill', instances, chunks, nodes, columns, occupancy (busy column-chunks / all
+    column-chunks), chunk_busy (busy columns per chunk), finished_at (per instance, a chunk number), grown, iters_all,
+    device_time, run_time, host_time, chunk_time, batched=True).  The model's q, l, u, leaves and counters are not
+    touched.  capacity: starting number of node slots (0: the engine's default)."""
+    work, data, st = model.work, model.work.data, model.work.settings
+    todo = list(todo)
+    n, M = data.n, data.m + data.n_int
+    t0 = time()
+    any_inc = bool(np.any(np.isfinite(up[todo])))
+    X, infos, s = work.solver.solve_trees_refill(
+        Q[todo], L[todo], U[todo], np.zeros((len(todo), n)), np.zeros((len(todo), M)), up[todo],
+        XI[todo] if any_inc else None, st['tree_explor_rule'], st['max_iter_bb'], capacity=capacity)
+    dt = time() - t0
+    work.lockstep = dict(instances=len(todo), chunks=s.chunks, nodes=int(s.nodes), batched=True, columns=s.columns,
+                         occupancy=(s.busy / s.total if s.total else 0.0), chunk_busy=s.chunk_busy,
+                         finished_at={k: int(s.finished_at[j]) for j, k in enumerate(todo)}, driver='refill',
+                         grown=s.grown, iters_all=int(s.iters_all), device_time=s.device_time, run_time=s.run_time,
+                         host_time=s.host_time, chunk_time=s.chunk_time)
+    for j, k in enumerate(todo):
+        info = infos[j]
+        upper = info.upper_glob
+        # workspace.py:352-373 decides on the loop counter (iter_num = nodes + 1), as run_device does
         finished = int(info.nodes) + 1 < st['max_iter_bb']
         if upper != np.inf:
             status = bnb.MI_SOLVED if finished else bnb.MI_MAX_ITER_FEASIBLE

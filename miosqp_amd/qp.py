@@ -476,6 +476,54 @@ class OSQP(object):
             iters_max=imax[:k].tolist(), iters_mean=imean[:k].tolist(), finished_at=fin.tolist(), node_hviol=hv)
         return x, list(infos), stats
 
+    def solve_trees_refill(self, q, l, u, x0, y0, upper0, x_inc0, tree_explor_rule, max_iter_bb, capacity=0):
+        """The trees of solve_trees_lockstep (same arrays) on columns that are refilled between chunks
+        (miosqp_qp_solve_trees_refill): a column holds one node of one tree, every tree has at most one node in flight, and
+        at every chunk boundary the decided columns are harvested and loaded again with the next leaf of a waiting tree.
+        capacity: starting number of node slots (0: the engine's default).  Needs max_iter to be a multiple of
+        check_termination (ValueError otherwise).
+        Returns (x B x n, [TreeInfo], stats): stats has chunks, nodes, columns, grown, iters_all, busy and total
+        (column-chunks: busy / total is the occupancy), device_time, run_time, host_time (the tree logic between the
+        chunks), chunk_time (device seconds inside the chunks), nodes_max_iter and iters_max_iter (the nodes that ended
+        MAX_ITER_REACHED and their iterations), chunk_busy (busy columns per chunk, the first 65536) and
+        finished_at (per instance, a chunk number)."""
+        q = np.ascontiguousarray(q, dtype=np.float64)
+        B = q.shape[0]
+        l, u = np.ascontiguousarray(l, dtype=np.float64), np.ascontiguousarray(u, dtype=np.float64)
+        x0, y0 = np.ascontiguousarray(x0, dtype=np.float64), np.ascontiguousarray(y0, dtype=np.float64)
+        if B < 1 or q.shape != (B, self.n) or x0.shape != (B, self.n) or l.shape != (B, self.m) or u.shape != (B, self.m) \
+                or y0.shape != (B, self.m):
+            raise ValueError("solve_trees_refill: instance-major arrays (B x n, B x M)")
+        up = np.minimum(np.ascontiguousarray(upper0, dtype=np.float64).reshape(B), 1.7e308)
+        xin = None if x_inc0 is None else np.ascontiguousarray(x_inc0, dtype=np.float64).reshape(B, self.n)
+        x = np.zeros((B, self.n))
+        infos = (_lib.TreeInfo * B)()
+        max_iter_bb = 2 ** 31 - 1 if not np.isfinite(max_iter_bb) else int(min(int(max_iter_bb), 2 ** 31 - 1))
+        ccap = 65536
+        busy, fin = np.zeros(ccap, dtype=np.int32), np.zeros(B, dtype=np.int32)
+        st = _lib.RefillStats()
+        st.chunk_cap = ccap
+        st.chunk_busy, st.finished_at = _lib.as_i(busy), _lib.as_i(fin)
+        rc = self._lib.miosqp_qp_solve_trees_refill(
+            self._h, B, _lib.as_d(q), _lib.as_d(l), _lib.as_d(u), _lib.as_d(x0), _lib.as_d(y0), _lib.as_d(up),
+            None if xin is None else _lib.as_d(xin), int(tree_explor_rule), max_iter_bb, int(capacity), _lib.as_d(x), infos,
+            C.byref(st))
+        if rc == -1 and "multiple of check_termination" in _lib.last_error():
+            raise ValueError("solve_trees_refill: max_iter must be a multiple of check_termination")
+        _check(rc, "solve_trees_refill")
+        if rc == 1:
+            msg = _lib.last_error()
+            if "branching" in msg:
+                raise RuntimeError("branching produced l > u")
+            raise ValueError("Lower bound must be lower than or equal to upper bound")
+        stats = types.SimpleNamespace(
+            chunks=st.chunks, nodes=st.nodes, columns=st.columns, grown=st.grown, iters_all=st.iters_all,
+            busy=st.col_chunks_busy, total=st.col_chunks_total, device_time=st.device_time, run_time=st.run_time,
+            host_time=st.host_time, chunk_time=st.chunk_time, nodes_max_iter=st.nodes_max_iter,
+            iters_max_iter=st.iters_max_iter, chunk_busy=busy[:min(st.chunks, ccap)].tolist(),
+            finished_at=fin.tolist())
+        return x, list(infos), stats
+
     # -- node-at-a-time branch and bound driven from the host in C++ (miosqp_qp_search_*) --------------
     def search_create(self, capacity):
         _check(self._lib.miosqp_qp_search_create(self._h, int(capacity)), "search_create")
