@@ -450,6 +450,49 @@ int miosqp_qp_solve_trees_lockstep(miosqp_qp_engine *e, int32_t B, const double 
                                    int32_t tree_explor_rule, int32_t max_iter_bb, int32_t capacity,
                                    double *x_out, miosqp_tree_info *info, miosqp_lockstep_stats *stats);
 
+/* ---- the lock-step trees with round and fix ---------------------------------------------------------------
+ * miosqp_qp_solve_trees_lockstep with the primal heuristic of miosqp_qp_round_and_fix inside the trees: per tree the
+ * decisions of its sequential solve with primal_heuristic = 1 (miosqp_amd/bnb.py: Workspace.bound_and_branch ->
+ * Workspace.primal_heuristic -> Workspace.round_and_fix, between the reference's rounding heuristic, workspace.py:321-328,
+ * and its branching, workspace.py:330-331).  On a solved fractional node that is not cut off, after the rounding
+ * heuristic of the digest: fire = rf_nodes % rf_every == 0, rf_nodes++ -- a counter per tree, 0 at the start of the call,
+ * counting exactly the nodes that get here.  The trees that fire in a wave send rf_candidates copies of their node into
+ * ONE more batch (F trees, F * rf_candidates columns, sliced at max_batch like a wave; a tree's candidates may straddle
+ * two slices): candidate k has the node's bounds with every integer row fixed to
+ * fmin(fmax(floor(x_i + (double)(k + 1) / (double)(K + 1)), lo), hi) (rf_roundings of bnb.py), the tree's cost and the
+ * node's OWN x, y as the warm start, and at most rf_max_iter iterations.  A candidate counts when its status is SOLVED
+ * or MAX_ITER_REACHED and its rounded point keeps the INSTANCE's root rows; the one of lowest objective wins (ties to the
+ * lowest k) and becomes the tree's incumbent when that objective is below upper_glob -- the device's sum, like the
+ * rounding heuristic's here --, followed by the reference's pruning traversal (workspace.py:274-280).  Then the node's
+ * two children enter the list.  Candidates are built, solved and judged on the device; per firing tree a 32-byte record
+ * comes back.  A wave in which no tree fires queues nothing more than miosqp_qp_solve_trees_lockstep does. */
+typedef struct miosqp_lockstep_rf_stats {
+  int32_t batches;        /* heuristic batches run (waves in which at least one tree fired) */
+  int32_t reserved;
+  int64_t columns;        /* their columns: rf_candidates per firing tree */
+  int64_t iters_slowest;  /* sum over the batches of the slowest candidate's ADMM iterations */
+  double device_time;     /* seconds between the events around the batches (part of miosqp_lockstep_stats.device_time) */
+  int32_t *calls;         /* IN, optional (NULL: not wanted), B entries each: times tree b fired ... */
+  int32_t *candidates;    /* ... its candidates (calls * rf_candidates) ... */
+  int32_t *feasible;      /* ... those that counted ... */
+  int32_t *improved;      /* ... the calls that gave the tree a new incumbent ... */
+  int64_t *iters;         /* ... and the candidates' ADMM iterations (info[b].osqp_iter counts node relaxations only) */
+  int32_t *cand_status;   /* IN, optional debug, B x rf_candidates each: the candidates of tree b's FIRST call as the batch */
+  int32_t *cand_iter;     /* epilogue left them -- status, iterations, the rounded point's objective and its worst violation */
+  double *cand_obj;       /* of the instance's root rows (<= 0: feasible), what miosqp_qp_round_and_fix returns per candidate; */
+  double *cand_viol;      /* rows of trees that never fired are not written */
+} miosqp_lockstep_rf_stats;
+
+/* Arguments, layouts, info[b], stats, capacity and errors as for miosqp_qp_solve_trees_lockstep.  rf_candidates in 1 .. 32;
+ * rf_max_iter a positive multiple of settings.check_termination or settings.max_iter itself (the rule of
+ * miosqp_qp_round_and_fix); rf_every >= 1: MIOSQP_EARG with a last_error text otherwise, nothing queued. */
+int miosqp_qp_solve_trees_lockstep_rf(miosqp_qp_engine *e, int32_t B, const double *q, const double *l, const double *u,
+                                      const double *x0, const double *y0, const double *upper0, const double *x_inc0,
+                                      int32_t tree_explor_rule, int32_t max_iter_bb, int32_t capacity,
+                                      int32_t rf_candidates, int32_t rf_max_iter, int32_t rf_every, double *x_out,
+                                      miosqp_tree_info *info, miosqp_lockstep_stats *stats,
+                                      miosqp_lockstep_rf_stats *rf_stats);
+
 /* ---- the same B trees on columns that are refilled between chunks ---------------------------------------
  * miosqp_qp_solve_trees_lockstep without the wave.  The engine's batch runs in chunks of check_termination iterations
  * with one termination test each; here a column holds one node of one tree, counts its own iterations from the chunk it

@@ -43,6 +43,12 @@ class LockstepStats(C.Structure):
                 ("finished_at", ip), ("node_hviol", dp), ("node_cap", C.c_int32), ("reserved", C.c_int32)]
 
 
+class LockstepRfStats(C.Structure):
+    _fields_ = [("batches", C.c_int32), ("reserved", C.c_int32), ("columns", C.c_int64), ("iters_slowest", C.c_int64),
+                ("device_time", C.c_double), ("calls", ip), ("candidates", ip), ("feasible", ip), ("improved", ip),
+                ("iters", i64p), ("cand_status", ip), ("cand_iter", ip), ("cand_obj", dp), ("cand_viol", dp)]
+
+
 class RefillStats(C.Structure):
     _fields_ = [("chunks", C.c_int32), ("columns", C.c_int32), ("grown", C.c_int32), ("chunk_cap", C.c_int32),
                 ("nodes", C.c_int64), ("iters_all", C.c_int64), ("col_chunks_busy", C.c_int64),
@@ -122,6 +128,9 @@ SYMBOLS = {
                                         C.POINTER(TreeInfo)]),
     "miosqp_qp_solve_trees_lockstep": (C.c_int, [C.c_void_p, C.c_int32, dp, dp, dp, dp, dp, dp, dp, C.c_int32, C.c_int32,
                                                  C.c_int32, dp, C.POINTER(TreeInfo), C.POINTER(LockstepStats)]),
+    "miosqp_qp_solve_trees_lockstep_rf": (C.c_int, [C.c_void_p, C.c_int32, dp, dp, dp, dp, dp, dp, dp, C.c_int32, C.c_int32,
+                                                    C.c_int32, C.c_int32, C.c_int32, C.c_int32, dp, C.POINTER(TreeInfo),
+                                                    C.POINTER(LockstepStats), C.POINTER(LockstepRfStats)]),
     "miosqp_qp_solve_trees_refill": (C.c_int, [C.c_void_p, C.c_int32, dp, dp, dp, dp, dp, dp, dp, C.c_int32, C.c_int32,
                                                C.c_int32, dp, C.POINTER(TreeInfo), C.POINTER(RefillStats)]),
     "miosqp_qp_search_create": (C.c_int, [C.c_void_p, C.c_int32]),

@@ -1225,6 +1225,12 @@ class MIOSQP(object):
         no interpreter runs per node; the trees are those of True, the heuristic incumbent's value is the device's sum
         (1e-12 relative).  ValueError when the solver lacks the entry or the settings are not the lock-step trees'.
         Asked for by name only: None never chooses it (DESIGN 3k has the measurements).
+        "device" is also the one driver that takes primal_heuristic = 1 (`OSQP.solve_trees_lockstep_rf`): round and fix
+        runs inside the trees -- per tree the decisions of its sequential solve, `Workspace.primal_heuristic` on every
+        rf_every-th fractional node --, the candidates of ALL trees that fire in a wave as one more batch, built, solved
+        and judged on the device; a winner's value is the device's sum.  `work.lockstep['rf']` holds what `rf_stats`
+        counts, summed and per instance; the model's own `rf_stats` is not touched.  True and "refill" keep refusing the
+        heuristic, None falls to the sequential path with it.
         "refill": the trees of "device" without the wave (`lockstep.run_refill`, `OSQP.solve_trees_refill`): a column of
         the batch holds one node of one tree and counts its own iterations; after every chunk of check_termination
         iterations the decided columns are harvested and, at that same boundary, loaded again with the next leaf of a
@@ -1314,7 +1320,8 @@ class MIOSQP(object):
             if lockstep == "refill" and not ls.refill_supported(work):
                 raise ValueError('solve_many(lockstep="refill") needs the HIP engine with solve_trees_refill and the '
                                  'device digest')
-            if not ls.supported(work):
+            # (round and fix runs inside the device driver's trees; the other drivers refuse the heuristic)
+            if not (lockstep == "device" and work.rf['on'] and ls.device_rf_supported(work)) and not ls.supported(work):
                 raise ValueError('solve_many(lockstep="%s") needs branching_rule 0, primal_heuristic 0 and '
                                  'tree_explor_rule 0-3' % lockstep)
             if lockstep == "refill":

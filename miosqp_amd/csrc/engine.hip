@@ -243,12 +243,12 @@ struct CoopNode {
 #include "kernels_bstream.inc"  // the streaming batch as ONE persistent launch: iterations, test, harvest and refill per column group (kbs)
 #include "kernels_derived.inc"  // nodes derived from one parent on the device, judged after the batch solve: strong branching, round and fix
 #include "kernels_polish.inc"  // polishing of a node's solution: active set, weighted Schur rows, solves and refinement, acceptance
-#include "kernels_lockstep.inc"  // B trees in lock step on device-resident leaves: gather / heuristic rows / scatter / incumbent around slice_run
+#include "kernels_lockstep.inc"  // B trees in lock step on device-resident leaves: gather / heuristic rows / scatter / incumbent around slice_run; round and fix in those trees
 #include "host.inc"  // host side: engine object, allocation, launches, graph capture, solve loops
 #include "host_pool.inc"  // host side of the leaf pool (C ABI miosqp_qp_pool_*)
 #include "host_search.inc"  // node-at-a-time branch and bound driven from the host in C++ (C ABI miosqp_qp_search_*)
 #include "host_stream.inc"  // the host side of the streaming search in C++ (C ABI miosqp_qp_stream_*)
-#include "host_lockstep.inc"  // B trees in lock step driven from the host in C++ (C ABI miosqp_qp_solve_trees_lockstep)
+#include "host_lockstep.inc"  // B trees in lock step driven from the host in C++ (C ABI miosqp_qp_solve_trees_lockstep, miosqp_qp_solve_trees_lockstep_rf)
 #include "host_refill.inc"  // the same trees on columns refilled between chunks (C ABI miosqp_qp_solve_trees_refill)
 
 // ------------------------------------------------------------------------------------------

@@ -1,7 +1,8 @@
 // part of engine.hip (included there, not compiled alone): B branch-and-bound trees advanced in lock step, driven from the
-// host in C++ on device-resident leaves (C ABI miosqp_qp_solve_trees_lockstep).  The wave loop of miosqp_amd/lockstep.py
-// -- per wave one node of every unfinished tree, solved together as the lock-step batch with a cost per column -- with
-// the tree logic of lockstep_trees.hpp and the kernels of kernels_lockstep.inc around an unchanged slice_run.  Per wave
+// host in C++ on device-resident leaves (C ABI miosqp_qp_solve_trees_lockstep, and miosqp_qp_solve_trees_lockstep_rf with
+// round and fix between a node's verdict and its children: one more batch per wave over all trees that fire).  The
+// wave loop of miosqp_amd/lockstep.py -- per wave one node of every unfinished tree, solved together as the lock-step
+// batch with a cost per column -- with the tree logic of lockstep_trees.hpp and the kernels of kernels_lockstep.inc around an unchanged slice_run.  Per wave
 // the host sends five integers per column and reads one 64-byte record per column back; no vector crosses PCIe between
 // the upload of the roots and the download of the incumbents.
 namespace {
@@ -24,6 +25,18 @@ struct LockstepStore {
   miosqp::lockstep::Slots slots;
   std::vector<miosqp::lockstep::Tree> trees;
   void *refill = nullptr;  // RefillCols (host_refill.inc): the per-column arrays of solve_trees_refill
+  // round and fix (solve_trees_lockstep_rf): per candidate column of a heuristic batch the five integers going up, per
+  // firing tree its record coming back and, for the winners the host adopts, the tree's number going up
+  int rf_inst_cap = 0, rf_col_cap = 0, rf_trip_inst = 0;  // (rf_trip_inst: the trees the column block's second part holds)
+  double *rf_block = nullptr;  // [ rf.x | run[0] | run[1] | rec | cand ]
+  std::vector<LsRfCand> rf_cand;  // (debug: a batch's candidates on the host, when the caller asked for them)
+  int *d_rf_trip = nullptr, *d_rf_adopt = nullptr;
+  int *h_rf_trip = nullptr, *h_rf_adopt = nullptr;  // pinned (one block)
+  LsRfGroup *h_rf_rec = nullptr;                    // pinned
+  LsRfDev rf{};
+  hipEvent_t rf_ev0 = nullptr, rf_ev1 = nullptr;    // around a heuristic batch
+  std::vector<int> fire;      // the wave's columns whose tree fires
+  std::vector<char> branch;   // per column of the wave: its node branches (the verdict, kept from begin to end)
 };
 
 void refill_free(void *p);  // (host_refill.inc)
@@ -41,6 +54,12 @@ void lockstep_free(void *p) {
   if (L->d_trip) hipFree(L->d_trip);
   if (L->h_trip) hipHostFree(L->h_trip);
   if (L->h_rec) hipHostFree(L->h_rec);
+  if (L->rf_block) hipFree(L->rf_block);
+  if (L->d_rf_trip) hipFree(L->d_rf_trip);
+  if (L->h_rf_trip) hipHostFree(L->h_rf_trip);
+  if (L->h_rf_rec) hipHostFree(L->h_rf_rec);
+  if (L->rf_ev0) hipEventDestroy(L->rf_ev0);
+  if (L->rf_ev1) hipEventDestroy(L->rf_ev1);
   refill_free(L->refill);
   delete L;
 }
@@ -129,14 +148,65 @@ int lockstep_slots(miosqp_qp_engine *e, LockstepStore &L, int ncap, int keep) {
   return 0;
 }
 
-}  // namespace
+// room for the heuristic batches of B trees with K candidates each
+int lockstep_rf_reserve(miosqp_qp_engine *e, LockstepStore &L, int B, int K) {
+  const size_t n = e->n;
+  if (!L.rf_ev0) {
+    HIPCHK(hipEventCreate(&L.rf_ev0));
+    HIPCHK(hipEventCreate(&L.rf_ev1));
+  }
+  if (B > L.rf_inst_cap) {
+    HIPCHK(hipStreamSynchronize(e->stream));
+    if (L.rf_block) hipFree(L.rf_block);
+    if (L.h_rf_rec) hipHostFree(L.h_rf_rec);
+    L.rf_block = nullptr; L.h_rf_rec = nullptr;
+    L.rf_inst_cap = 0;
+    const size_t cap = (size_t)B, ox = ls_al(cap * n), og = ls_al(cap * sizeof(LsRfGroup) / sizeof(double)),
+                 oc = ls_al(cap * RF_MAX_K * sizeof(LsRfCand) / sizeof(double));
+    if (int rc = ls_malloc(&L.rf_block, ox + 3 * og + oc, "the heuristic's winners")) return rc;
+    L.rf.x = L.rf_block;
+    L.rf.run[0] = reinterpret_cast<LsRfGroup *>(L.rf_block + ox);
+    L.rf.run[1] = reinterpret_cast<LsRfGroup *>(L.rf_block + ox + og);
+    L.rf.rec = reinterpret_cast<LsRfGroup *>(L.rf_block + ox + 2 * og);
+    L.rf.cand = reinterpret_cast<LsRfCand *>(L.rf_block + ox + 3 * og);
+    HIPCHK(hipHostMalloc((void **)&L.h_rf_rec, cap * sizeof(LsRfGroup), hipHostMallocDefault));
+    L.rf_inst_cap = B;
+  }
+  const size_t cols = (size_t)B * (size_t)K;
+  if (cols > (size_t)L.rf_col_cap || L.rf_trip_inst != L.rf_inst_cap) {
+    HIPCHK(hipStreamSynchronize(e->stream));
+    if (L.d_rf_trip) hipFree(L.d_rf_trip);
+    if (L.h_rf_trip) hipHostFree(L.h_rf_trip);
+    L.d_rf_trip = nullptr; L.h_rf_trip = nullptr;
+    L.rf_col_cap = 0;
+    // one block each: [five integers per candidate column | the adopted trees], rf_inst_cap of those
+    const size_t ints = LS_TRIP * cols + (size_t)L.rf_inst_cap;
+    if (hipMalloc((void **)&L.d_rf_trip, ints * sizeof(int)) != hipSuccess) {
+      (void)hipGetLastError();
+      L.d_rf_trip = nullptr;
+      g_err = "solve_trees_lockstep_rf: no device memory for the heuristic's columns";
+      return MIOSQP_EFULL;
+    }
+    L.d_rf_adopt = L.d_rf_trip + LS_TRIP * cols;
+    HIPCHK(hipHostMalloc((void **)&L.h_rf_trip, ints * sizeof(int), hipHostMallocDefault));
+    L.h_rf_adopt = L.h_rf_trip + LS_TRIP * cols;
+    L.rf_col_cap = (int)cols;
+    L.rf_trip_inst = L.rf_inst_cap;
+  }
+  return 0;
+}
 
-extern "C" {
+// what round and fix asks of lockstep_trees_run (K = 0: the heuristic is off, nothing of it is touched)
+struct LsRfArgs {
+  int K, max_iter, every;
+  miosqp_lockstep_rf_stats *stats;
+};
 
-int miosqp_qp_solve_trees_lockstep(miosqp_qp_engine *e, int32_t B, const double *q, const double *l, const double *u,
-                                   const double *x0, const double *y0, const double *upper0, const double *x_inc0,
-                                   int32_t tree_explor_rule, int32_t max_iter_bb, int32_t capacity, double *x_out,
-                                   miosqp_tree_info *info, miosqp_lockstep_stats *stats) {
+// the body of miosqp_qp_solve_trees_lockstep and, with rf.K > 0, of miosqp_qp_solve_trees_lockstep_rf
+int lockstep_trees_run(miosqp_qp_engine *e, int32_t B, const double *q, const double *l, const double *u, const double *x0,
+                       const double *y0, const double *upper0, const double *x_inc0, int32_t tree_explor_rule,
+                       int32_t max_iter_bb, int32_t capacity, double *x_out, miosqp_tree_info *info,
+                       miosqp_lockstep_stats *stats, const LsRfArgs &rf) {
   using miosqp::lockstep::Record;
   using miosqp::lockstep::Tree;
   using miosqp::lockstep::Verdict;
@@ -166,6 +236,13 @@ int miosqp_qp_solve_trees_lockstep(miosqp_qp_engine *e, int32_t B, const double 
   if (!e->lockstep) e->lockstep = new LockstepStore();
   LockstepStore &L = *static_cast<LockstepStore *>(e->lockstep);
   if (int rc = lockstep_reserve(e, L, B)) return rc;
+  if (rf.K > 0) {
+    if (int rc = lockstep_rf_reserve(e, L, B, rf.K)) return rc;
+    miosqp_lockstep_rf_stats *rs = rf.stats;
+    rs->batches = 0;
+    rs->columns = rs->iters_slowest = 0;
+    rs->device_time = 0.0;
+  }
   {
     // `capacity` is a starting size: a store left by an earlier call is kept when the caller leaves the size to us
     const int want = capacity > 0 ? std::max(capacity, 4) : std::max(64, 4 * B);
@@ -185,6 +262,7 @@ int miosqp_qp_solve_trees_lockstep(miosqp_qp_engine *e, int32_t B, const double 
   const Dev &d = e->d;
   L.slots.reset(L.cap);
   L.trees.assign((size_t)B, Tree());
+  L.fire.clear();  // (a call that ended in an error between begin and end may have left some)
   // ---- the roots: bounds, costs and incumbents per instance; tree b's root is slot b (integer rows of l, u; x0, y0) ----
   {
     const size_t tot = (size_t)B * (2 * M + 2 * n + 2 * p + n + M);
@@ -264,6 +342,7 @@ int miosqp_qp_solve_trees_lockstep(miosqp_qp_engine *e, int32_t B, const double 
     th = wall();
     const int wave = ++stats->waves;
     int it_max = 0, npairs = 0;
+    if (rf.K > 0) L.branch.assign((size_t)W, 0);
     int64_t it_sum = 0;
     for (int c = 0; c < W; c++) {
       const LsRec &g = L.h_rec[c];
@@ -279,7 +358,10 @@ int miosqp_qp_solve_trees_lockstep(miosqp_qp_engine *e, int32_t B, const double 
       r.heur_feasible = g.hviol <= 0.0;
       r.heur_obj = g.hobj;
       if (stats->node_hviol && T.nodes < stats->node_cap) stats->node_hviol[(size_t)b * stats->node_cap + T.nodes] = g.hviol;
-      const Verdict v = T.absorb(L.slots, tr[LS_SLOT], tr[LS_CHILD0], tr[LS_CHILD1], r);
+      // (with round and fix: up to the point where the children would enter the list; they enter after the heuristic batch)
+      const miosqp::lockstep::Begun bg = T.begin(L.slots, tr[LS_SLOT], r, rf.K > 0 ? rf.every : 0);
+      const Verdict v = bg.v;
+      if (rf.K == 0) T.end(L.slots, tr[LS_SLOT], tr[LS_CHILD0], tr[LS_CHILD1], v);  // (begin + end: Tree::absorb)
       if (v.branch && g.crossed) {
         g_err = "solve_trees_lockstep: branching produced l > u (instance " + std::to_string(b) + ")";
         return MIOSQP_EBOUNDS;
@@ -290,7 +372,10 @@ int miosqp_qp_solve_trees_lockstep(miosqp_qp_engine *e, int32_t B, const double 
         pr[1] = tr[LS_SLOT];
         pr[2] = v.incumbent == 2;
       }
-      if (!T.can_continue(max_iter_bb)) T.finished_at = wave;
+      if (rf.K > 0) {
+        L.branch[(size_t)c] = v.branch;
+        if (bg.fire) L.fire.push_back(c);
+      } else if (!T.can_continue(max_iter_bb)) T.finished_at = wave;
       it_max = g.iter > it_max ? g.iter : it_max;
       it_sum += g.iter;
     }
@@ -298,6 +383,89 @@ int miosqp_qp_solve_trees_lockstep(miosqp_qp_engine *e, int32_t B, const double 
     if (npairs > 0) {  // (the pairs' pinned block is next written after the next wave's drain: this copy is done by then)
       HIPCHK(hipMemcpyAsync(L.d_pairs, L.h_pairs, sizeof(int) * 3 * (size_t)npairs, hipMemcpyHostToDevice, e->stream));
       hipLaunchKernelGGL(kls_incumbent<0>, dim3(npairs), dim3(256), 0, e->stream, d, L.dev, L.d_pairs, npairs);
+    }
+    if (rf.K > 0) {
+      // ---- round and fix: the K candidates of every tree that fires, ONE batch; then the children of the whole wave ----
+      const int K = rf.K, F = (int)L.fire.size(), C = F * K;
+      if (F > 0) {
+        th = wall();
+        for (int f = 0; f < F; f++) {
+          const int *tr = L.h_trip + LS_TRIP * L.fire[(size_t)f];
+          for (int k = 0; k < K; k++) {
+            int *ct = L.h_rf_trip + LS_TRIP * ((size_t)f * K + k);
+            ct[LS_TREE] = tr[LS_TREE];
+            ct[LS_SLOT] = ct[LS_WARM] = tr[LS_SLOT];  // the node's own x, y (it is held until its children are decided)
+            ct[LS_RF_K] = k;
+            ct[LS_RF_GROUP] = f;
+          }
+        }
+        host_s += wall() - th;
+        HIPCHK(hipEventRecord(L.rf_ev0, e->stream));
+        int slice = 0;
+        for (int s0 = 0; s0 < C; s0 += e->Bcap, slice++) {  // sliced as a wave is; a tree's candidates may straddle two slices
+          const int nb = C - s0 < e->Bcap ? C - s0 : e->Bcap;
+          const int ntiles = (nb + 63) / 64;
+          if (int rc = slice_begin(e, nb)) return rc;
+          if (s0 == 0)
+            HIPCHK(hipMemcpyAsync(L.d_rf_trip, L.h_rf_trip, sizeof(int) * LS_TRIP * (size_t)C, hipMemcpyHostToDevice, e->stream));
+          const int *trip = L.d_rf_trip + LS_TRIP * s0;
+          const int big = (int)(n > M ? n : M);
+          hipLaunchKernelGGL(kls_rf_gather<0>, dim3((big + 255) / 256, nb), dim3(256), 0, e->stream, d, L.dev, trip, nb, K);
+          const LsRoots roots{L.dev.root_l, L.dev.root_u, trip, nb};
+          if (int rc = slice_run(e, nb, rf.max_iter, &roots)) return rc;
+          hipLaunchKernelGGL(kls_rf_keep<0>, dim3((int)((n + 63) / 64) + 1, ntiles), dim3(256), 0, e->stream, d, L.rf, trip, s0, nb, K, slice);
+        }
+        HIPCHK(hipMemcpyAsync(L.h_rf_rec, L.rf.rec, sizeof(LsRfGroup) * (size_t)F, hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(hipEventRecord(L.rf_ev1, e->stream));
+        HIPCHK(hipStreamSynchronize(e->stream));
+        HIPCHK(hipGetLastError());
+        float rf_ms = 0;
+        HIPCHK(hipEventElapsedTime(&rf_ms, L.rf_ev0, L.rf_ev1));
+        rf.stats->batches++;
+        rf.stats->columns += C;
+        rf.stats->device_time += 1e-3 * rf_ms;
+        miosqp_lockstep_rf_stats *rs = rf.stats;
+        if (rs->cand_status || rs->cand_iter || rs->cand_obj || rs->cand_viol) {  // debug: the candidates of every tree's FIRST call
+          bool any = false;
+          for (int f = 0; f < F && !any; f++) any = L.trees[(size_t)L.h_trip[LS_TRIP * L.fire[(size_t)f] + LS_TREE]].rf_calls == 0;
+          if (any) {
+            L.rf_cand.resize((size_t)C);
+            HIPCHK(hipMemcpy(L.rf_cand.data(), L.rf.cand, sizeof(LsRfCand) * (size_t)C, hipMemcpyDeviceToHost));
+            for (int f = 0; f < F; f++) {
+              const size_t b = (size_t)L.h_trip[LS_TRIP * L.fire[(size_t)f] + LS_TREE];
+              if (L.trees[b].rf_calls != 0) continue;
+              for (int k = 0; k < K; k++) {
+                const LsRfCand &cd = L.rf_cand[(size_t)f * K + k];
+                if (rs->cand_status) rs->cand_status[b * K + k] = cd.status;
+                if (rs->cand_iter) rs->cand_iter[b * K + k] = cd.iter;
+                if (rs->cand_obj) rs->cand_obj[b * K + k] = cd.obj;
+                if (rs->cand_viol) rs->cand_viol[b * K + k] = cd.viol;
+              }
+            }
+          }
+        }
+      }
+      th = wall();
+      int nadopt = 0, rf_it_max = 0;
+      for (int f = 0; f < F; f++) {  // Workspace.primal_heuristic on the winner: one `< upper` test
+        const LsRfGroup &g = L.h_rf_rec[f];
+        const int b = L.h_trip[LS_TRIP * L.fire[(size_t)f] + LS_TREE];
+        if (L.trees[(size_t)b].heuristic(L.slots, K, g.chosen >= 0, g.obj, g.feasible, g.iters)) L.h_rf_adopt[nadopt++] = b;
+        rf_it_max = g.iter_max > rf_it_max ? g.iter_max : rf_it_max;
+      }
+      rf.stats->iters_slowest += rf_it_max;
+      for (int c = 0; c < W; c++) {  // branch_children, in the order of the wave
+        const int *tr = L.h_trip + LS_TRIP * c;
+        Tree &T = L.trees[(size_t)tr[LS_TREE]];
+        T.end(L.slots, tr[LS_SLOT], tr[LS_CHILD0], tr[LS_CHILD1], Verdict{L.branch[(size_t)c] != 0, 0});
+        if (!T.can_continue(max_iter_bb)) T.finished_at = wave;
+      }
+      L.fire.clear();
+      host_s += wall() - th;
+      if (nadopt > 0) {  // (behind kls_incumbent; the pinned list is next written after the next heuristic batch's drain)
+        HIPCHK(hipMemcpyAsync(L.d_rf_adopt, L.h_rf_adopt, sizeof(int) * (size_t)nadopt, hipMemcpyHostToDevice, e->stream));
+        hipLaunchKernelGGL(kls_rf_incumbent<0>, dim3(nadopt), dim3(256), 0, e->stream, d, L.dev, L.rf, L.d_rf_adopt, nadopt);
+      }
     }
     stats->nodes += W;
     stats->max_width = W > stats->max_width ? W : stats->max_width;
@@ -334,6 +502,14 @@ int miosqp_qp_solve_trees_lockstep(miosqp_qp_engine *e, int32_t B, const double 
     info[b].run_time = wall_s / B;
     if (T.found || have) memcpy(x_out + (size_t)b * n, h_inc + (size_t)b * n, sizeof(double) * n);
     if (stats->finished_at) stats->finished_at[b] = T.finished_at;
+    if (rf.K > 0) {
+      miosqp_lockstep_rf_stats *rs = rf.stats;
+      if (rs->calls) rs->calls[b] = (int32_t)T.rf_calls;
+      if (rs->candidates) rs->candidates[b] = (int32_t)T.rf_candidates;
+      if (rs->feasible) rs->feasible[b] = (int32_t)T.rf_feasible;
+      if (rs->improved) rs->improved[b] = (int32_t)T.rf_improved;
+      if (rs->iters) rs->iters[b] = T.rf_iters;
+    }
   }
   stats->device_time = 1e-3 * ms;
   stats->run_time = wall_s;
@@ -341,6 +517,40 @@ int miosqp_qp_solve_trees_lockstep(miosqp_qp_engine *e, int32_t B, const double 
   e->loop_ms += ms;
   e->loop_iters += iters_total;
   return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int miosqp_qp_solve_trees_lockstep(miosqp_qp_engine *e, int32_t B, const double *q, const double *l, const double *u,
+                                   const double *x0, const double *y0, const double *upper0, const double *x_inc0,
+                                   int32_t tree_explor_rule, int32_t max_iter_bb, int32_t capacity, double *x_out,
+                                   miosqp_tree_info *info, miosqp_lockstep_stats *stats) {
+  return lockstep_trees_run(e, B, q, l, u, x0, y0, upper0, x_inc0, tree_explor_rule, max_iter_bb, capacity, x_out, info, stats,
+                            LsRfArgs{0, 0, 0, nullptr});
+}
+
+int miosqp_qp_solve_trees_lockstep_rf(miosqp_qp_engine *e, int32_t B, const double *q, const double *l, const double *u,
+                                      const double *x0, const double *y0, const double *upper0, const double *x_inc0,
+                                      int32_t tree_explor_rule, int32_t max_iter_bb, int32_t capacity, int32_t rf_candidates,
+                                      int32_t rf_max_iter, int32_t rf_every, double *x_out, miosqp_tree_info *info,
+                                      miosqp_lockstep_stats *stats, miosqp_lockstep_rf_stats *rf_stats) {
+  if (!e || !rf_stats) return MIOSQP_EARG;
+  if (rf_candidates < 1 || rf_candidates > RF_MAX_K) {
+    g_err = "solve_trees_lockstep_rf: rf_candidates must be in 1..32";
+    return MIOSQP_EARG;
+  }
+  if (rf_max_iter <= 0 || (rf_max_iter % e->chunk != 0 && rf_max_iter != e->st.max_iter)) {
+    g_err = "solve_trees_lockstep_rf: rf_max_iter must be a positive multiple of check_termination or the engine's max_iter";
+    return MIOSQP_EARG;
+  }
+  if (rf_every < 1) {
+    g_err = "solve_trees_lockstep_rf: rf_every must be at least 1";
+    return MIOSQP_EARG;
+  }
+  return lockstep_trees_run(e, B, q, l, u, x0, y0, upper0, x_inc0, tree_explor_rule, max_iter_bb, capacity, x_out, info, stats,
+                            LsRfArgs{rf_candidates, rf_max_iter, rf_every, rf_stats});
 }
 
 }  // extern "C"

@@ -1,7 +1,7 @@
 // part of engine.hip (included there, not compiled alone): the device side of B branch-and-bound trees in lock step
-// (host_lockstep.inc, C ABI miosqp_qp_solve_trees_lockstep).  The open leaves of ALL trees are slots of one device store
-// (integer-row bounds lo / hi, solution x / y = the children's warm start); every tree has its own root bounds, raw and
-// scaled cost and incumbent.  A wave is the unchanged lock-step batch (slice_run) between kls_gather and kls_scatter.
+// (host_lockstep.inc, C ABI miosqp_qp_solve_trees_lockstep and, with round and fix, miosqp_qp_solve_trees_lockstep_rf).
+// The open leaves of ALL trees are slots of one device store (integer-row bounds lo / hi, solution x / y = the children's
+// warm start); every tree has its own root bounds, raw and scaled cost and incumbent.  A wave is the unchanged lock-step batch (slice_run) between kls_gather and kls_scatter.
 // The kernels here are copies and row sums over vector loads and stores: no spin wait, no hand-off between workgroups,
 // no whole-chip launch.
 // They are templates (one instantiation each, LS = 0; kls_heur_rows a second one for the refilled columns at the end of this
@@ -167,6 +167,171 @@ __global__ __launch_bounds__(256) void kls_incumbent(Dev d, LsDev ls, const int 
     const size_t i = (size_t)d.i_idx[j];
     ls.inc[t * n + i] = rint(ls.x[s * n + i]);
   }
+}
+
+// ------------------------------------------------------------------------------------------
+// Round and fix in the lock-step trees (host_lockstep.inc, C ABI miosqp_qp_solve_trees_lockstep_rf): the trees that fire
+// in a wave send K candidates each into ONE more batch, F K columns, sliced like a wave.  A candidate column carries a
+// wave's five integers with the tree, the node's slot and -- the warm start is the node's own solution -- that slot again;
+// the two child entries hold the candidate's number k and the number of its group (the firing tree's place in the
+// batch).  Groups are contiguous in candidate order, k ascending, and K need not divide a slice: a group may begin in one
+// slice and end in the next.  Like the kernels above: copies and a short scan over vector loads and stores, one launch
+// each, no spin wait, no hand-off between workgroups; templates instantiated from host_lockstep.inc only.
+enum { LS_RF_K = 3, LS_RF_GROUP = 4 };
+
+struct LsRfGroup {  // what the host reads back per firing tree (32 bytes)
+  int chosen;       // the candidate that counts with the lowest c_hobj (ties to the lowest k), -1 when none counts
+  int feasible;     // candidates with a status that has an x and c_hviol <= 0
+  int iters;        // ADMM iterations of the K candidates
+  int iter_max;     // ... and of the slowest one
+  double obj;       // the winner's c_hobj
+  double pad;
+};
+
+struct LsRfCand {  // a candidate as the batch epilogue leaves it, in candidate order (24 bytes)
+  int status, iter;
+  double obj, viol;  // c_hobj, c_hviol
+};
+
+struct LsRfDev {
+  double *x;          // [B][n] per tree: the rounded point of its group's running winner
+  LsRfCand *cand;     // [B * RF_MAX_K] the batch's candidates, group after group, k ascending
+  LsRfGroup *run[2];  // [B] each: a straddling group's record between its two slices, read in [slice & 1], written in [(slice + 1) & 1]
+  LsRfGroup *rec;     // [B] the groups' records as the host reads them
+};
+
+// candidate c of the slice into d.b_raw (node-major l | u | x0 | y0, as kb_prepare reads it): kls_gather with every integer
+// row fixed to the rounding k_rf_candidates gives it (the same expression on the slot's x, lo, hi; Workspace.round_and_fix,
+// rf_roundings of bnb.py) and the node's own x, y as the warm start.  grid (row chunks of 256, nb)
+template <int LS>
+__global__ __launch_bounds__(256) void kls_rf_gather(Dev d, LsDev ls, const int *__restrict__ trip, int nb, int K) {
+  const int c = blockIdx.y;
+  if (c >= nb) return;
+  const size_t n = d.n, M = d.M, m = d.m_orig, p = d.n_int;
+  const size_t t = (size_t)trip[LS_TRIP * c + LS_TREE], s = (size_t)trip[LS_TRIP * c + LS_SLOT];
+  const int k = trip[LS_TRIP * c + LS_RF_K];
+  double *rl = d.b_raw + (size_t)c * M, *ru = d.b_raw + (size_t)nb * M + (size_t)c * M;
+  double *rx = d.b_raw + 2 * (size_t)nb * M + (size_t)c * n, *ry = d.b_raw + (size_t)nb * (2 * M + n) + (size_t)c * M;
+  const size_t j = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (j < M) {
+    double lo, hi;
+    if (j < m) {
+      lo = ls.root_l[t * M + j];
+      hi = ls.root_u[t * M + j];
+    } else {
+      lo = ls.lo[s * p + (j - m)];
+      hi = ls.hi[s * p + (j - m)];
+      const double theta = (double)(k + 1) / (double)(K + 1);
+      lo = hi = fmin(fmax(floor(ls.x[s * n + (size_t)d.i_idx[j - m]] + theta), lo), hi);
+    }
+    rl[j] = lo;
+    ru[j] = hi;
+    ry[j] = ls.y[s * M + j];
+  }
+  if (j < n) {
+    rx[j] = ls.x[s * n + j];
+    d.b_qraw[(size_t)c * n + j] = ls.qraw[t * n + j];
+    d.b_qs[(size_t)c * n + j] = ls.qs[t * n + j];
+  }
+}
+
+// The record of the group candidate `v` of the slice belongs to, once this slice is counted: k_rf_pick's scan over the
+// group's candidates in the slice, in ascending k, behind what an earlier slice left (a later candidate replaces the
+// winner only when strictly lower: ties stay with the lowest k).  col_of: candidate of the slice -> column (c_node
+// inverted).  fresh: the winner is a candidate of this slice.
+__device__ __forceinline__ LsRfGroup ls_rf_judge(const Dev &d, const LsRfDev &rf, const int *__restrict__ trip, const int *col_of, int v,
+                                                 int nb, int K, int slice, bool &fresh) {
+  const int k = trip[LS_TRIP * v + LS_RF_K];
+  const int first = v - k;  // where the group's candidate 0 is (negative: in the slice before)
+  const int v_lo = first > 0 ? first : 0, v_hi = first + K < nb ? first + K : nb;
+  LsRfGroup g;
+  g.chosen = -1;
+  g.feasible = g.iters = g.iter_max = 0;
+  g.obj = g.pad = 0.0;
+  if (first < 0) g = rf.run[slice & 1][trip[LS_TRIP * v + LS_RF_GROUP]];
+  fresh = false;
+  for (int w = v_lo; w < v_hi; w++) {
+    const int b = col_of[w], st = d.c_status[b], it = d.c_iter[b];
+    g.iters += it;
+    g.iter_max = it > g.iter_max ? it : g.iter_max;
+    if ((st == MIOSQP_QP_SOLVED || st == MIOSQP_QP_MAX_ITER_REACHED) && d.c_hviol[b] <= 0.0) {
+      const double o = d.c_hobj[b];
+      g.feasible++;
+      if (g.chosen < 0 || o < g.obj) {
+        g.chosen = w - first;
+        g.obj = o;
+        fresh = true;
+      }
+    }
+  }
+  return g;
+}
+
+// After a slice of candidates (s0: the slice's first candidate in the batch): per candidate its status, iterations, c_hobj
+// and c_hviol in candidate order (rf.cand), per group with candidates in the slice its record (rf.rec, and rf.run for the slice that
+// may finish it), and the rounded point of a winner found in this slice -- its column of b_xi, unscaled, the integer
+// entries the fixed values -- into the tree's row of rf.x.  grid (tiles of 64 rows of x, then one block for the records;
+// tiles of 64 columns).  b_xi is batch-fastest and rf.x tree-major: a tile goes through LDS as in kls_scatter, so that the
+// loads and the stores are both contiguous.  Every block judges the groups of its own columns (a scan of at most K
+// candidates per column): nothing is handed from one workgroup to another.
+template <int LS>
+__global__ __launch_bounds__(256) void kls_rf_keep(Dev d, LsRfDev rf, const int *__restrict__ trip, int s0, int nb, int K, int slice) {
+  __shared__ double tile[64][65];
+  __shared__ int col_of[1024];  // (a slice has at most 1024 columns)
+  __shared__ int tree_of[64];   // the tree whose winner this column of the tile has just become, or -1
+  __shared__ int s_any;
+  const int n = d.n, nxt = (n + 63) / 64;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int b0 = blockIdx.y * 64;
+  const size_t Bs = (size_t)d.Bs;
+  for (int b = threadIdx.x; b < nb; b += 256) col_of[d.c_node[b]] = b;  // (c_node of the slice's columns: a permutation of 0 .. nb-1)
+  __syncthreads();
+  if (threadIdx.x < 64) {
+    const int b = b0 + (int)threadIdx.x;
+    int tree = -1;
+    if (b < nb) {
+      const int v = d.c_node[b], k = trip[LS_TRIP * v + LS_RF_K];
+      bool fresh;
+      const LsRfGroup g = ls_rf_judge(d, rf, trip, col_of, v, nb, K, slice, fresh);
+      if (fresh && g.chosen == k) tree = trip[LS_TRIP * v + LS_TREE];
+      if ((int)blockIdx.x == nxt) {
+        LsRfCand cd;  // (through c_node: compaction swaps columns)
+        cd.status = d.c_status[b];
+        cd.iter = d.c_iter[b];
+        cd.obj = d.c_hobj[b];
+        cd.viol = d.c_hviol[b];
+        rf.cand[s0 + v] = cd;
+        if (k == 0 || v == 0) {  // the group's first candidate in the slice writes its record
+          const int grp = trip[LS_TRIP * v + LS_RF_GROUP];
+          rf.run[(slice + 1) & 1][grp] = g;
+          rf.rec[grp] = g;
+        }
+      }
+    }
+    tree_of[threadIdx.x] = tree;
+    const unsigned long long any = __ballot(tree >= 0);
+    if (threadIdx.x == 0) s_any = any != 0ull;
+  }
+  __syncthreads();
+  if ((int)blockIdx.x >= nxt || !s_any) return;
+  const int r0 = (int)blockIdx.x * 64;
+  for (int r = wv; r < 64; r += 4)
+    if (r0 + r < n) tile[r][lane] = d.b_xi[(size_t)(r0 + r) * Bs + b0 + lane];  // (columns up to Bs exist)
+  __syncthreads();
+  for (int cc = wv; cc < 64; cc += 4) {
+    const int t = tree_of[cc];
+    if (t >= 0 && r0 + lane < n) rf.x[(size_t)t * n + r0 + lane] = tile[lane][cc];
+  }
+}
+
+// the winners the host adopted in this wave: the tree's row of rf.x becomes its incumbent (Workspace.primal_heuristic:
+// self.x = r.x).  Queued behind kls_incumbent: at a node where both heuristics improve, this one is the later.  grid (trees)
+template <int LS>
+__global__ __launch_bounds__(256) void kls_rf_incumbent(Dev d, LsDev ls, LsRfDev rf, const int *__restrict__ trees, int nt) {
+  const int k = blockIdx.x;
+  if (k >= nt) return;
+  const size_t n = d.n, t = (size_t)trees[k];
+  for (size_t i = threadIdx.x; i < n; i += 256) ls.inc[t * n + i] = rf.x[t * n + i];
 }
 
 // ------------------------------------------------------------------------------------------

@@ -4,7 +4,8 @@
 // It restates the three decisions of the Python mirror (miosqp_amd/bnb.py) with the list semantics of host_search.inc:
 // list order = creation order, choose = first extremum (workspace.py:128-149 and best bound), the prune traversal that does
 // not examine the element behind a removed one (workspace.py:274-280), and bound_and_branch on a node's digest
-// (workspace.py:282-334).  Every tree has its own open list, incumbent value and counters; the node slots -- the device
+// (workspace.py:282-334), whole (absorb) or in three steps around round and fix (begin / heuristic / end: bnb.py's
+// Workspace.primal_heuristic between the verdict and the children).  Every tree has its own open list, incumbent value and counters; the node slots -- the device
 // store's indices -- and their free list are shared by all trees.
 #ifndef MIOSQP_LOCKSTEP_TREES_HPP
 #define MIOSQP_LOCKSTEP_TREES_HPP
@@ -34,6 +35,12 @@ struct Record {
 struct Verdict {
   bool branch;    // the two children enter the list (their slots are kept)
   int incumbent;  // 0: unchanged, 1: the node's x is the new incumbent, 2: its rounded point is
+};
+
+// what the first step of a split absorb decided (Tree::begin)
+struct Begun {
+  Verdict v;
+  bool fire;  // round and fix runs at this node before its children enter the list
 };
 
 // Node slots shared by all trees.  A slot stays allocated while a child may still read its solution as a warm start: the
@@ -83,6 +90,8 @@ struct Tree {
   int64_t nodes = 0, iters = 0;
   int finished_at = 0;    // the wave after which the tree was done (0: nothing to do)
   size_t max_open = 0;
+  // round and fix: the fractional nodes that asked (Workspace.rf_nodes) and what Workspace.rf_stats counts
+  int64_t rf_nodes = 0, rf_calls = 0, rf_candidates = 0, rf_feasible = 0, rf_improved = 0, rf_iters = 0;
 
   // a root with explicit bounds and warm start in slot `s`; upper0 >= NO_UPPER: no incumbent (Workspace.set_x0)
   void start(Slots &S, int s, double upper0) {
@@ -90,6 +99,7 @@ struct Tree {
     upper = upper0 < NO_UPPER ? upper0 : std::numeric_limits<double>::infinity();
     found = false;
     nodes = iters = 0;
+    rf_nodes = rf_calls = rf_candidates = rf_feasible = rf_improved = rf_iters = 0;
     finished_at = 0;
     S.depth[(size_t)s] = 0;
     S.lower[(size_t)s] = -std::numeric_limits<double>::infinity();
@@ -145,7 +155,19 @@ struct Tree {
   // bound_and_branch (workspace.py:282-334) on the record of node `s`, whose children would sit in slots c0 and c1
   // (taken before the wave).  Without a branching the two slots go back to the free list.
   Verdict absorb(Slots &S, int s, int c0, int c1, const Record &r) {
-    Verdict v{false, 0};
+    const Verdict v = begin(S, s, r, 0).v;
+    end(S, s, c0, c1, v);
+    return v;
+  }
+
+  // absorb in three steps, for the driver that runs round and fix (Workspace.primal_heuristic / round_and_fix of
+  // miosqp_amd/bnb.py) between a node's verdict and the entry of its children:
+  // begin: bound_and_branch up to the point where the children would be pushed, and whether the heuristic fires at this
+  // node -- only a fractional node that is about to branch asks, every rf_every-th of them, the first included
+  // (rf_every < 1: the heuristic is off and nothing is counted).
+  Begun begin(Slots &S, int s, const Record &r, int rf_every) {
+    Begun g{{false, 0}, false};
+    Verdict &v = g.v;
     nodes++;
     iters += r.iter;
     if (r.ok) {
@@ -164,9 +186,35 @@ struct Tree {
             prune(S);
           }
           v.branch = true;
+          if (rf_every > 0) {
+            g.fire = rf_nodes % rf_every == 0;
+            rf_nodes++;
+          }
         }
       }
     }
+    return g;
+  }
+
+  // the outcome of the heuristic's K candidates at a node where begin said `fire`: `counted`: a candidate counts (it has
+  // an x and its rounded point keeps the root's rows), `obj` the lowest objective among those, `feasible` how many count,
+  // `it` the candidates' iterations.  The winner becomes the incumbent when it is better (primal_heuristic).  Returns
+  // whether it did.
+  bool heuristic(Slots &S, int K, bool counted, double obj, int feasible, int64_t it) {
+    rf_calls++;
+    rf_candidates += K;
+    rf_feasible += feasible;
+    rf_iters += it;
+    if (!counted || !(obj < upper)) return false;
+    upper = obj;
+    found = true;
+    rf_improved++;
+    prune(S);
+    return true;
+  }
+
+  // end: the children enter the list behind whatever the pruning left, or their slots go back
+  void end(Slots &S, int s, int c0, int c1, const Verdict &v) {
     if (v.branch) {
       for (int c : {c0, c1}) {
         S.depth[(size_t)c] = S.depth[(size_t)s] + 1;
@@ -184,7 +232,6 @@ struct Tree {
       S.kids[(size_t)s] = 0;
     }
     S.done(s);
-    return v;
   }
 
   // workspace.py:334, reported once: the smallest bound of the open leaves (the incumbent's value on a closed tree)

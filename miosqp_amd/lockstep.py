@@ -13,7 +13,9 @@ set up itself (`_Tree`).  One wave:
 
 `run_device` is the same wave loop in the library (`OSQP.solve_trees_lockstep`, miosqp_qp_solve_trees_lockstep): the
 leaves of all trees stay in device slots, the per-tree logic runs in C++ and Python sees the B results.  It is asked for
-by name: `solve_many(lockstep="device")`.
+by name: `solve_many(lockstep="device")`.  It is also the one driver that runs round and fix (primal_heuristic = 1)
+inside the trees (`OSQP.solve_trees_lockstep_rf`): the candidates of every tree that fires in a wave go out as one more
+batch.
 
 `run_refill` drops the wave (`OSQP.solve_trees_refill`, miosqp_qp_solve_trees_refill): a column of the batch holds one
 node of one tree and counts its own iterations; after every chunk of check_termination iterations the decided columns
@@ -162,6 +164,14 @@ def device_supported(work):
     return hasattr(work.solver, 'solve_trees_lockstep') and work.root_on_device and work.data.n_int > 0
 
 
+def device_rf_supported(work):
+    """round and fix inside the device driver (`OSQP.solve_trees_lockstep_rf`): the entry, the on-device digest,
+    most-fractional branching, rules 0-3"""
+    st = work.settings
+    return hasattr(work.solver, 'solve_trees_lockstep_rf') and work.root_on_device and work.data.n_int > 0 \
+        and st['branching_rule'] == 0 and st['tree_explor_rule'] in (0, 1, 2, 3)
+
+
 def run_device(model, todo, Q, L, U, up, XI, instances, out, capacity=0):
     """`run` in the library: the trees of instances `todo` advance in lock step inside ONE call of
     `OSQP.solve_trees_lockstep` -- leaves in device slots, the tree logic in C++ (csrc/lockstep_trees.hpp), per wave five
@@ -169,21 +179,39 @@ def run_device(model, todo, Q, L, U, up, XI, instances, out, capacity=0):
     work.lockstep with the same keys, driver='device', plus grown (times the slot store grew), iters_slowest,
     iters_all, device_time, run_time and host_time (the library's call and, of it, the tree logic between the waves).  The value of an incumbent found by the rounding heuristic is the device's sum
     (`run` recomputes it with numpy: ~1e-12 relative apart), as in the hosted search.  The model's q, l, u, leaves and
-    counters are not touched.  capacity: starting number of node slots (0: the engine's default)."""
+    counters are not touched.  capacity: starting number of node slots (0: the engine's default).
+    With primal_heuristic = 1 (work.rf['on']) the call is `OSQP.solve_trees_lockstep_rf`: round and fix runs inside the
+    trees, the candidates of all trees that fire in a wave as one more batch (rf_candidates, rf_max_iter, rf_every as
+    `Workspace.primal_heuristic` reads them), and work.lockstep['rf'] = dict(calls, candidates, feasible, improved,
+    osqp_iter -- the sums of what `rf_stats` counts per sequential solve --, batches, columns, iters_slowest,
+    device_time, per_instance={k: dict(calls, candidates, feasible, improved, osqp_iter)}); the dicts' osqp_iter counts
+    node relaxations only, as work.osqp_iter does."""
     work, data, st = model.work, model.work.data, model.work.settings
     todo = list(todo)
     n, M = data.n, data.m + data.n_int
     t0 = time()
     any_inc = bool(np.any(np.isfinite(up[todo])))
-    X, infos, s = work.solver.solve_trees_lockstep(
-        Q[todo], L[todo], U[todo], np.zeros((len(todo), n)), np.zeros((len(todo), M)), up[todo],
-        XI[todo] if any_inc else None, st['tree_explor_rule'], st['max_iter_bb'], capacity=capacity)
+    args = (Q[todo], L[todo], U[todo], np.zeros((len(todo), n)), np.zeros((len(todo), M)), up[todo],
+            XI[todo] if any_inc else None, st['tree_explor_rule'], st['max_iter_bb'])
+    r = None
+    if work.rf['on']:
+        X, infos, s, r = work.solver.solve_trees_lockstep_rf(*args, work.rf['K'], work.rf['max_iter'], work.rf['every'],
+                                                             capacity=capacity)
+    else:
+        X, infos, s = work.solver.solve_trees_lockstep(*args, capacity=capacity)
     dt = time() - t0
     work.lockstep = dict(instances=len(todo), waves=s.waves, nodes=int(s.nodes), batched=True, max_width=s.max_width,
                          iters_max=s.iters_max, iters_mean=s.iters_mean,
                          finished_at={k: int(s.finished_at[j]) for j, k in enumerate(todo)}, driver='device',
                          grown=s.grown, iters_slowest=int(s.iters_slowest), iters_all=int(s.iters_all),
                          device_time=s.device_time, run_time=s.run_time, host_time=s.host_time)
+    if r is not None:
+        per = {k: dict(calls=r.calls[j], candidates=r.candidates[j], feasible=r.feasible[j], improved=r.improved[j],
+                       osqp_iter=r.iters[j]) for j, k in enumerate(todo)}
+        work.lockstep['rf'] = dict(calls=sum(r.calls), candidates=sum(r.candidates), feasible=sum(r.feasible),
+                                   improved=sum(r.improved), osqp_iter=sum(r.iters), batches=r.batches,
+                                   columns=int(r.columns), iters_slowest=int(r.iters_slowest),
+                                   device_time=r.device_time, per_instance=per)
     for j, k in enumerate(todo):
         info = infos[j]
         upper = info.upper_glob

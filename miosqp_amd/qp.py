@@ -437,13 +437,32 @@ class OSQP(object):
         Returns (x B x n, [TreeInfo], stats): stats has waves, nodes, max_width, grown, iters_slowest, iters_all,
         device_time, run_time, host_time (the tree logic between the waves), the per-wave lists width, iters_max, iters_mean (the first 65536 waves), finished_at
         (per instance) and node_hviol (B x node_hviol, NaN where there was no node; None when not asked for)."""
+        return self._trees_lockstep(q, l, u, x0, y0, upper0, x_inc0, tree_explor_rule, max_iter_bb, capacity, node_hviol, None)
+
+    def solve_trees_lockstep_rf(self, q, l, u, x0, y0, upper0, x_inc0, tree_explor_rule, max_iter_bb, rf_candidates,
+                                rf_max_iter, rf_every, capacity=0, first_call=False):
+        """solve_trees_lockstep with round and fix inside the trees (miosqp_qp_solve_trees_lockstep_rf): on every
+        rf_every-th fractional node a tree is about to branch (the first included) rf_candidates rounded-and-fixed copies
+        of the node, at most rf_max_iter iterations each; the candidates of all trees that fire in a wave are ONE more
+        batch, built, solved and judged on the device.  rf_candidates in 1..32, rf_max_iter a positive multiple of
+        check_termination or max_iter, rf_every >= 1 (ValueError otherwise).
+        Returns (x, [TreeInfo], stats, rf): stats as solve_trees_lockstep's (TreeInfo.osqp_iter and the iteration counts
+        there are the node relaxations'), rf has batches, columns, iters_slowest, device_time and per instance calls,
+        candidates, feasible, improved, iters (lists).  first_call: debug, rf.first_call is then a namespace of
+        B x rf_candidates arrays status, iter, obj, viol -- the candidates of every tree's first call as
+        `round_and_fix` reports them (status -1 and NaN for a tree that never fired); None otherwise."""
+        return self._trees_lockstep(q, l, u, x0, y0, upper0, x_inc0, tree_explor_rule, max_iter_bb, capacity, 0,
+                                    (int(rf_candidates), int(rf_max_iter), int(rf_every), bool(first_call)))
+
+    def _trees_lockstep(self, q, l, u, x0, y0, upper0, x_inc0, tree_explor_rule, max_iter_bb, capacity, node_hviol, rf):
+        who = "solve_trees_lockstep" if rf is None else "solve_trees_lockstep_rf"
         q = np.ascontiguousarray(q, dtype=np.float64)
         B = q.shape[0]
         l, u = np.ascontiguousarray(l, dtype=np.float64), np.ascontiguousarray(u, dtype=np.float64)
         x0, y0 = np.ascontiguousarray(x0, dtype=np.float64), np.ascontiguousarray(y0, dtype=np.float64)
         if B < 1 or q.shape != (B, self.n) or x0.shape != (B, self.n) or l.shape != (B, self.m) or u.shape != (B, self.m) \
                 or y0.shape != (B, self.m):
-            raise ValueError("solve_trees_lockstep: instance-major arrays (B x n, B x M)")
+            raise ValueError(who + ": instance-major arrays (B x n, B x M)")
         up = np.minimum(np.ascontiguousarray(upper0, dtype=np.float64).reshape(B), 1.7e308)
         xin = None if x_inc0 is None else np.ascontiguousarray(x_inc0, dtype=np.float64).reshape(B, self.n)
         x = np.zeros((B, self.n))
@@ -459,11 +478,31 @@ class OSQP(object):
         st.finished_at = _lib.as_i(fin)
         if hv is not None:
             st.node_hviol, st.node_cap = _lib.as_d(hv), int(node_hviol)
-        rc = self._lib.miosqp_qp_solve_trees_lockstep(
-            self._h, B, _lib.as_d(q), _lib.as_d(l), _lib.as_d(u), _lib.as_d(x0), _lib.as_d(y0), _lib.as_d(up),
-            None if xin is None else _lib.as_d(xin), int(tree_explor_rule), max_iter_bb, int(capacity), _lib.as_d(x), infos,
-            C.byref(st))
-        _check(rc, "solve_trees_lockstep")
+        if rf is None:
+            rc = self._lib.miosqp_qp_solve_trees_lockstep(
+                self._h, B, _lib.as_d(q), _lib.as_d(l), _lib.as_d(u), _lib.as_d(x0), _lib.as_d(y0), _lib.as_d(up),
+                None if xin is None else _lib.as_d(xin), int(tree_explor_rule), max_iter_bb, int(capacity), _lib.as_d(x), infos,
+                C.byref(st))
+        else:
+            cnt = [np.zeros(B, dtype=np.int32) for _ in range(4)]
+            rf_it = np.zeros(B, dtype=np.int64)
+            rs = _lib.LockstepRfStats()
+            rs.calls, rs.candidates, rs.feasible, rs.improved = (_lib.as_i(a) for a in cnt)
+            rs.iters = rf_it.ctypes.data_as(_lib.i64p)
+            first = None
+            if rf[3]:
+                Kc = max(rf[0], 1)
+                first = types.SimpleNamespace(status=np.full((B, Kc), -1, dtype=np.int32), iter=np.zeros((B, Kc), dtype=np.int32),
+                                              obj=np.full((B, Kc), np.nan), viol=np.full((B, Kc), np.nan))
+                rs.cand_status, rs.cand_iter = _lib.as_i(first.status), _lib.as_i(first.iter)
+                rs.cand_obj, rs.cand_viol = _lib.as_d(first.obj), _lib.as_d(first.viol)
+            rc = self._lib.miosqp_qp_solve_trees_lockstep_rf(
+                self._h, B, _lib.as_d(q), _lib.as_d(l), _lib.as_d(u), _lib.as_d(x0), _lib.as_d(y0), _lib.as_d(up),
+                None if xin is None else _lib.as_d(xin), int(tree_explor_rule), max_iter_bb, int(capacity), rf[0], rf[1], rf[2],
+                _lib.as_d(x), infos, C.byref(st), C.byref(rs))
+            if rc == -1 and "solve_trees_lockstep_rf: rf_" in _lib.last_error():
+                raise ValueError(_lib.last_error())
+        _check(rc, who)
         if rc == 1:
             msg = _lib.last_error()
             if "branching" in msg:
@@ -474,6 +513,12 @@ class OSQP(object):
             waves=st.waves, nodes=st.nodes, max_width=st.max_width, grown=st.grown, iters_slowest=st.iters_slowest,
             iters_all=st.iters_all, device_time=st.device_time, run_time=st.run_time, host_time=st.host_time, width=width[:k].tolist(),
             iters_max=imax[:k].tolist(), iters_mean=imean[:k].tolist(), finished_at=fin.tolist(), node_hviol=hv)
+        if rf is not None:
+            rfs = types.SimpleNamespace(
+                batches=rs.batches, columns=rs.columns, iters_slowest=rs.iters_slowest, device_time=rs.device_time,
+                calls=cnt[0].tolist(), candidates=cnt[1].tolist(), feasible=cnt[2].tolist(), improved=cnt[3].tolist(),
+                iters=rf_it.tolist(), first_call=first)
+            return x, list(infos), stats, rfs
         return x, list(infos), stats
 
     def solve_trees_refill(self, q, l, u, x0, y0, upper0, x_inc0, tree_explor_rule, max_iter_bb, capacity=0):
