@@ -539,6 +539,53 @@ int miosqp_qp_solve_trees_refill(miosqp_qp_engine *e, int32_t B, const double *q
                                  int32_t tree_explor_rule, int32_t max_iter_bb, int32_t capacity,
                                  double *x_out, miosqp_tree_info *info, miosqp_refill_stats *stats);
 
+/* ---- the lock-step trees with spare columns solving open leaves early -----------------------------------
+ * miosqp_qp_solve_trees_lockstep launches whole tiles of 64 columns per wave; with L live trees the columns behind the L
+ * chosen leaves iterate on padding.  Here a tree may hold up to `ahead` columns of a wave: its chosen leaf (the MANDATORY
+ * column) and, in the free columns of the tiles the wave launches anyway, other open leaves and children of nodes it has
+ * already solved ahead.  The record of a node solved ahead waits with the node -- which stays in the open list with its
+ * inherited bound, counted as a leaf -- until the tree's exploration rule chooses it: then it is absorbed without a
+ * wave (a HIT), as are further records the rule reaches.  A record whose node is pruned, or that is left when the call
+ * ends, is discarded with everything solved below it.  A node is a pure function of (q, l, u, x0, y0): every tree makes
+ * the decisions of its sequential solve, node for node, and info[b], x_out are those of miosqp_qp_solve_trees_lockstep
+ * bit for bit; only the number of waves changes.  nodes, osqp_iter, incumbents and prunings happen at absorb time only.
+ * The wave ends with its mandatory columns: behind every chunk one small launch counts the mandatory columns the test
+ * has not decided, the count comes down with the chunk's control block, and an ahead column that is undecided when the
+ * loop ends is called off -- nothing of it is kept and its node is solved again when it is next chosen.
+ * Free columns: the mandatory columns are sliced at max_batch as miosqp_qp_solve_trees_lockstep slices them; the last
+ * slice holds nbl of them and min(64 ceil(nbl / 64), max_batch) - nbl free columns (64 ceil(L / 64) - L when max_batch is
+ * a multiple of 64).  They are dealt round-robin over the live trees in tree order, one candidate per tree per round,
+ * until a tree holds `ahead` columns, its candidates run out or the free columns run out; a tree's candidates are taken
+ * in the order its own rule would choose them (csrc/lockstep_ahead.hpp states it in full).  The order influences speed
+ * only.  No tile is launched that miosqp_qp_solve_trees_lockstep would not launch for the same L; ahead = 1 runs its
+ * launches exactly. */
+typedef struct miosqp_lockstep_ahead_stats {
+  int32_t waves;             /* waves run (miosqp_lockstep_stats.waves) */
+  int32_t wave_cap;          /* IN: entries the three per-wave arrays below can take; later waves are not recorded */
+  int64_t columns;           /* columns solved: mandatory and ahead */
+  int64_t sent;              /* ahead columns sent = hits + discarded + called_off */
+  int64_t hits;              /* ... whose record was absorbed when the tree's rule reached the node */
+  int64_t discarded;         /* ... whose record was dropped (pruned, below a node that did not branch, left at the end) */
+  int64_t called_off;        /* ... the wave did not wait for */
+  int64_t hit_iters;         /* ADMM iterations of the hits (they are part of info[b].osqp_iter) ... */
+  int64_t discarded_iters;   /* ... of the discarded records and ... */
+  int64_t called_off_iters;  /* ... of the columns called off: these two appear here only */
+  int32_t free_slots;        /* node slots free when the call ended ... */
+  int32_t slot_cap;          /* ... of this many: the difference is the open leaves and the parents their warm starts need */
+  int32_t *wave_width;           /* IN, optional (NULL: not wanted): columns per wave, ahead columns included */
+  int32_t *wave_iter_mandatory;  /* IN, optional: the mandatory columns' largest iteration count per wave */
+  int32_t *wave_chunks;          /* IN, optional: chunks the wave's slowest slice ran (a tail at max_iter counts as one) */
+} miosqp_lockstep_ahead_stats;
+
+/* Arguments, layouts, info[b], stats, capacity and errors as for miosqp_qp_solve_trees_lockstep (stats: max_width and
+ * wave_width count all columns, the iteration figures the mandatory columns per wave and iters_all the absorbed nodes;
+ * node_hviol is not written).  ahead >= 1: MIOSQP_EARG with a last_error text otherwise, nothing queued. */
+int miosqp_qp_solve_trees_lockstep_ahead(miosqp_qp_engine *e, int32_t B, const double *q, const double *l, const double *u,
+                                         const double *x0, const double *y0, const double *upper0, const double *x_inc0,
+                                         int32_t tree_explor_rule, int32_t max_iter_bb, int32_t capacity, int32_t ahead,
+                                         double *x_out, miosqp_tree_info *info, miosqp_lockstep_stats *stats,
+                                         miosqp_lockstep_ahead_stats *ahead_stats);
+
 /* ---- node-at-a-time branch and bound, driven from the host in C++ -------------------------------------
  * The loop of /root/reference/miosqp/solver.py:65-172 (choose_leaf -> Node.solve -> bound_and_branch, workspace.py:
  * 113-155, 274-334) for problems of any size, one relaxation at a time in whatever form the engine uses for single

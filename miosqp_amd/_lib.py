@@ -49,6 +49,13 @@ class LockstepRfStats(C.Structure):
                 ("iters", i64p), ("cand_status", ip), ("cand_iter", ip), ("cand_obj", dp), ("cand_viol", dp)]
 
 
+class LockstepAheadStats(C.Structure):
+    _fields_ = [("waves", C.c_int32), ("wave_cap", C.c_int32), ("columns", C.c_int64), ("sent", C.c_int64),
+                ("hits", C.c_int64), ("discarded", C.c_int64), ("called_off", C.c_int64), ("hit_iters", C.c_int64),
+                ("discarded_iters", C.c_int64), ("called_off_iters", C.c_int64), ("free_slots", C.c_int32),
+                ("slot_cap", C.c_int32), ("wave_width", ip), ("wave_iter_mandatory", ip), ("wave_chunks", ip)]
+
+
 class RefillStats(C.Structure):
     _fields_ = [("chunks", C.c_int32), ("columns", C.c_int32), ("grown", C.c_int32), ("chunk_cap", C.c_int32),
                 ("nodes", C.c_int64), ("iters_all", C.c_int64), ("col_chunks_busy", C.c_int64),
@@ -131,6 +138,9 @@ SYMBOLS = {
     "miosqp_qp_solve_trees_lockstep_rf": (C.c_int, [C.c_void_p, C.c_int32, dp, dp, dp, dp, dp, dp, dp, C.c_int32, C.c_int32,
                                                     C.c_int32, C.c_int32, C.c_int32, C.c_int32, dp, C.POINTER(TreeInfo),
                                                     C.POINTER(LockstepStats), C.POINTER(LockstepRfStats)]),
+    "miosqp_qp_solve_trees_lockstep_ahead": (C.c_int, [C.c_void_p, C.c_int32, dp, dp, dp, dp, dp, dp, dp, C.c_int32,
+                                                       C.c_int32, C.c_int32, C.c_int32, dp, C.POINTER(TreeInfo),
+                                                       C.POINTER(LockstepStats), C.POINTER(LockstepAheadStats)]),
     "miosqp_qp_solve_trees_refill": (C.c_int, [C.c_void_p, C.c_int32, dp, dp, dp, dp, dp, dp, dp, C.c_int32, C.c_int32,
                                                C.c_int32, dp, C.POINTER(TreeInfo), C.POINTER(RefillStats)]),
     "miosqp_qp_search_create": (C.c_int, [C.c_void_p, C.c_int32]),

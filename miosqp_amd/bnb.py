@@ -1192,7 +1192,7 @@ class MIOSQP(object):
                 res['polished'] = True
         return results
 
-    def solve_many(self, instances, polish=False, lockstep=None):
+    def solve_many(self, instances, polish=False, lockstep=None, ahead=8):
         """B MIQPs on this model's factorisation, solved TOGETHER: instance k is what
         `update_vectors(q=, l=, u=)` [+ `set_x0(x0)`] + `solve()` would solve (the reference's MPC pattern,
         /root/reference/miosqp/solver.py:174-212, examples/power_converter/power_converter.py:467-476), for a list of
@@ -1238,6 +1238,15 @@ class MIOSQP(object):
         slowest of a wave and B trees need only min(B, max_batch) columns.  Status, nodes and iterations are those of
         False, upper_glob and x those of "device" bit for bit.  Needs what "device" needs and max_iter a multiple of
         check_termination (ValueError otherwise).  Asked for by name only (DESIGN 3k has the measurements).
+        "ahead": the waves of "device" with their spare columns put to use (`lockstep.run_ahead`,
+        `OSQP.solve_trees_lockstep_ahead`): a wave launches whole tiles of 64 columns, and in the columns behind the
+        chosen leaves a tree may solve other open leaves and children of nodes it has already solved ahead -- up to
+        `ahead` columns per tree and wave (an int >= 1; 1 is "device" exactly).  A record waits with its node until the
+        tree's rule reaches it and goes when a pruning removes the node; the wave ends with its chosen leaves, whatever
+        the other columns are doing.  Every field is that of "device" bit for bit, only the number of waves changes;
+        `work.lockstep['ahead']` counts the ahead columns sent, hit, discarded and called off.  Needs what "device"
+        needs; primal_heuristic 1, another branching_rule and ahead < 1 are refused (ValueError).  Asked for by name
+        only (DESIGN 3k has the measurements).  `ahead` is read by this driver alone.
 
         polish=True: the incumbents are then polished together by `polish_many` (one more launch on the HIP engine) and
         every dict gains polished, polish_rounds, pri_after, dua_after.  Polishing many instances is asked for per call:
@@ -1312,14 +1321,21 @@ class MIOSQP(object):
         if isinstance(lockstep, str):
             # the driver in the library, asked for by name (the default is not this one)
             from miosqp_amd import lockstep as ls
-            if lockstep not in ("device", "refill"):
-                raise ValueError('solve_many: lockstep must be None, True, False, "device" or "refill"')
+            if lockstep not in ("device", "refill", "ahead"):
+                raise ValueError('solve_many: lockstep must be None, True, False, "ahead", "device" or "refill"')
             if lockstep == "device" and not ls.device_supported(work):
                 raise ValueError('solve_many(lockstep="device") needs the HIP engine with solve_trees_lockstep and the '
                                  'device digest')
             if lockstep == "refill" and not ls.refill_supported(work):
                 raise ValueError('solve_many(lockstep="refill") needs the HIP engine with solve_trees_refill and the '
                                  'device digest')
+            if lockstep == "ahead":
+                if not ls.ahead_supported(work):
+                    raise ValueError('solve_many(lockstep="ahead") needs the HIP engine with solve_trees_lockstep_ahead '
+                                     'and the device digest')
+                if isinstance(ahead, bool) or not isinstance(ahead, (int, np.integer)) or ahead < 1:
+                    raise ValueError('solve_many(lockstep="ahead") needs ahead to be an int >= 1 (the most columns one '
+                                     'tree may hold in a wave): ahead %r' % (ahead,))
             # (round and fix runs inside the device driver's trees; the other drivers refuse the heuristic)
             if not (lockstep == "device" and work.rf['on'] and ls.device_rf_supported(work)) and not ls.supported(work):
                 raise ValueError('solve_many(lockstep="%s") needs branching_rule 0, primal_heuristic 0 and '
@@ -1331,7 +1347,10 @@ class MIOSQP(object):
                     raise ValueError('solve_many(lockstep="refill") needs max_iter to be a multiple of check_termination '
                                      '(a column counts whole chunks): max_iter %d, check_termination %d' % (mi, ct))
             if redo:
-                (ls.run_refill if lockstep == "refill" else ls.run_device)(self, redo, Q, L, U, up, XI, instances, out)
+                if lockstep == "ahead":
+                    ls.run_ahead(self, redo, Q, L, U, up, XI, instances, out, ahead=int(ahead))
+                else:
+                    (ls.run_refill if lockstep == "refill" else ls.run_device)(self, redo, Q, L, U, up, XI, instances, out)
                 redo = []
         if redo and lockstep is not False:
             from miosqp_amd import lockstep as ls

@@ -1521,13 +1521,25 @@ int slice_begin(miosqp_qp_engine *e, int B) {
 
 void launch_ls_heur_rows(miosqp_qp_engine *e, const LsRoots &roots, int ntiles);  // (host_lockstep.inc)
 
+// what slice_run needs to end a wave with its mandatory columns (host_lockstep_ahead.inc): behind every chunk one more
+// small launch counts the mandatory columns the test has not decided yet, and the count comes down with the Ctrl copy
+struct LsNeed {
+  const int *mand;       // device, per node of the slice: the wave waits for this column
+  int *d_left, *h_left;  // the count on the device / pinned
+  int chunks;            // OUT: chunks run (a tail counts as one)
+  bool cut;              // OUT: the loop ended on the count with iterations still to run -- columns with c_done == 0 are unfinished
+};
+void launch_ls_need(miosqp_qp_engine *e, const LsNeed &need, int B);  // (host_lockstep_ahead.inc)
+
 // The lock-step solve of the B nodes staged in d.b_raw (node-major l | u | x0 | y0), up to `max_iter` iterations:
 // full chunks of check_termination iterations, then the tail graph for the rest only when max_iter is the engine's own
 // (a strong-branching cap is a multiple of check_termination: no tail).  Ends with the per-column epilogue
 // (unscale, clamp, digest, objective) in c_status / c_iter / c_lower / b_xfin / b_yfin, node order through c_node.
 // roots: the columns belong to trees with root bounds of their own (kernels_lockstep.inc) -- the rounded points are
 // judged against those; nullptr (every other caller): against the engine's root, today's launches.
-int slice_run(miosqp_qp_engine *e, int B, int max_iter, const LsRoots *roots = nullptr) {
+// need: the chunk loop also ends when no mandatory column is undecided (above); nullptr (every other caller): today's
+// launches and today's loop.
+int slice_run(miosqp_qp_engine *e, int B, int max_iter, const LsRoots *roots = nullptr, LsNeed *need = nullptr) {
   const Dev &d = e->d;
   const size_t n = e->n, M = e->M;
   const int ntiles = (B + 63) / 64;
@@ -1538,17 +1550,23 @@ int slice_run(miosqp_qp_engine *e, int B, int max_iter, const LsRoots *roots = n
   hipLaunchKernelGGL(kb_warm_z, dim3((d.M + 3) / 4, ntiles), dim3(256), 0, e->stream, d);
   const int nfull = max_iter / e->chunk;
   const bool tail = max_iter == e->st.max_iter && e->tail_iters > 0;
-  bool done = false;
+  bool done = false, stop = false;  // (stop: only with `need`)
   int decided = 0;
   int cur = ntiles;  // tiles still launched; shrinks as the wave is compacted
-  for (int k = 0; k < nfull && !done; k++) {
+  if (need) {
+    need->chunks = 0;
+    need->cut = false;
+  }
+  for (int k = 0; k < nfull && !done && !stop; k++) {
     HIPCHK(hipEventRecord(e->evc0, e->stream));
     {
       ChipGuard turn(e);  // (the captured chunk may hold a whole-chip launch)
       HIPCHK(hipGraphLaunch(e->xb_full[e->pq][cur - 1], e->stream));
     }
     HIPCHK(hipEventRecord(e->evc1, e->stream));
+    if (need) launch_ls_need(e, *need, B);
     HIPCHK(hipMemcpyAsync(e->h_ctrl, d.ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost, e->stream));
+    if (need) HIPCHK(hipMemcpyAsync(need->h_left, need->d_left, sizeof(int), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     float ms = 0;
     HIPCHK(hipEventElapsedTime(&ms, e->evc0, e->evc1));
@@ -1572,8 +1590,15 @@ int slice_run(miosqp_qp_engine *e, int B, int max_iter, const LsRoots *roots = n
     }
     decided = e->h_ctrl->ndone;
     done = e->h_ctrl->done != 0;
+    if (need) {
+      need->chunks++;
+      if (!done && *need->h_left == 0) {
+        stop = true;
+        need->cut = k + 1 < nfull || tail;
+      }
+    }
     const int active = B - decided, want = (active + 63) / 64;
-    if (!done && e->compact && want < cur) {
+    if (!done && !stop && e->compact && want < cur) {
       // move the still-iterating columns into the first `want` tiles
       const int cols = cur * 64;
       int *flags = e->hb_int;  // scratch: the info arrays are only filled at the end
@@ -1607,7 +1632,7 @@ int slice_run(miosqp_qp_engine *e, int B, int max_iter, const LsRoots *roots = n
       e->compactions++;
     }
   }
-  while (!done && tail) {
+  while (!done && !stop && tail) {
     // the last max_iter % check_termination iterations: the same call-off handling as a full chunk -- a persistent
     // launch that was called off iterated nothing and its test decided nothing, so the tail is redone as launches
     {
@@ -1616,7 +1641,10 @@ int slice_run(miosqp_qp_engine *e, int B, int max_iter, const LsRoots *roots = n
     }
     HIPCHK(hipMemcpyAsync(e->h_ctrl, d.ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
-    if (!e->h_ctrl->pad) break;
+    if (!e->h_ctrl->pad) {
+      if (need) need->chunks++;
+      break;
+    }
     if (e->h_ctrl->pad != 1) {
       g_err = "batched persistent sweeps: a group barrier timed out, stage " + std::to_string(e->h_ctrl->pad);
       return MIOSQP_EHIP;

@@ -23,6 +23,11 @@ are harvested and, at that same boundary, loaded again with the next leaf of a t
 still has at most one node in flight, so its decisions are those of the wave drivers.  Asked for by name as well:
 `solve_many(lockstep="refill")`.
 
+`run_ahead` keeps the wave and fills its spare columns (`OSQP.solve_trees_lockstep_ahead`,
+miosqp_qp_solve_trees_lockstep_ahead): a wave launches whole tiles of 64 columns, and behind the chosen leaves a tree
+solves other open leaves and children of nodes it has solved ahead; such a record waits with its node until the tree's
+rule reaches it.  Asked for by name: `solve_many(lockstep="ahead", ahead=8)`.
+
 A node is a pure function of (q, l, u, x0, y0), so every tree makes exactly the decisions of its sequential solve
 (`update_vectors` + `set_x0` + `solve`), node for node.  The wave waits for its slowest column; trees finish at
 different waves and later waves are narrower.
@@ -258,6 +263,59 @@ def run_refill(model, todo, Q, L, U, up, XI, instances, out, capacity=0):
                          finished_at={k: int(s.finished_at[j]) for j, k in enumerate(todo)}, driver='refill',
                          grown=s.grown, iters_all=int(s.iters_all), device_time=s.device_time, run_time=s.run_time,
                          host_time=s.host_time, chunk_time=s.chunk_time)
+    for j, k in enumerate(todo):
+        info = infos[j]
+        upper = info.upper_glob
+        # workspace.py:352-373 decides on the loop counter (iter_num = nodes + 1), as run_device does
+        finished = int(info.nodes) + 1 < st['max_iter_bb']
+        if upper != np.inf:
+            status = bnb.MI_SOLVED if finished else bnb.MI_MAX_ITER_FEASIBLE
+        elif upper >= 0:
+            status = bnb.MI_PRIMAL_INFEASIBLE if finished else bnb.MI_MAX_ITER_UNSOLVED
+        else:
+            status = bnb.MI_DUAL_INFEASIBLE
+        x = X[j].copy() if (info.found or np.isfinite(up[k])) else np.empty(n)
+        if status in (bnb.MI_SOLVED, bnb.MI_MAX_ITER_FEASIBLE):
+            x[data.i_idx] = np.round(x[data.i_idx])
+        out[k] = dict(x=x, upper_glob=upper, status=status, nodes=int(info.nodes), osqp_iter=int(info.osqp_iter),
+                      run_time=dt / len(todo))
+
+
+def ahead_supported(work):
+    """the ahead driver needs the HIP engine's entry and the on-device digest (set_root)"""
+    return hasattr(work.solver, 'solve_trees_lockstep_ahead') and work.root_on_device and work.data.n_int > 0
+
+
+def run_ahead(model, todo, Q, L, U, up, XI, instances, out, ahead=8, capacity=0):
+    """`run_device` with the spare columns of every wave put to use: the trees of instances `todo` inside ONE call of
+    `OSQP.solve_trees_lockstep_ahead` -- a tree may hold up to `ahead` columns of a wave, its chosen leaf and, in the free
+    columns of the tiles the wave launches anyway, other open leaves and children of nodes solved ahead; a record waits
+    with its node until the tree's rule reaches it (csrc/lockstep_ahead.hpp, csrc/host_lockstep_ahead.inc).  Fills
+    out[k] with the dicts `run_device` forms, equal to them bit for bit, and leaves work.lockstep with `run_device`'s
+    keys, driver='ahead' (nodes: the absorbed nodes over all trees; max_width counts all columns; iters_max and
+    iters_mean the mandatory columns of each wave), plus work.lockstep['ahead'] = dict(ahead, columns, sent, hits,
+    discarded, called_off, hit_iters, discarded_iters, called_off_iters, free_slots, slot_cap, width, iter_mandatory,
+    chunks -- the last three per wave).  The model's q, l, u, leaves and counters are not touched.  capacity: starting
+    number of node slots (0: the engine's default)."""
+    work, data, st = model.work, model.work.data, model.work.settings
+    todo = list(todo)
+    n, M = data.n, data.m + data.n_int
+    t0 = time()
+    any_inc = bool(np.any(np.isfinite(up[todo])))
+    X, infos, s, a = work.solver.solve_trees_lockstep_ahead(
+        Q[todo], L[todo], U[todo], np.zeros((len(todo), n)), np.zeros((len(todo), M)), up[todo],
+        XI[todo] if any_inc else None, st['tree_explor_rule'], st['max_iter_bb'], ahead, capacity=capacity)
+    dt = time() - t0
+    work.lockstep = dict(instances=len(todo), waves=s.waves, nodes=int(s.nodes), batched=True, max_width=s.max_width,
+                         iters_max=s.iters_max, iters_mean=s.iters_mean,
+                         finished_at={k: int(s.finished_at[j]) for j, k in enumerate(todo)}, driver='ahead',
+                         grown=s.grown, iters_slowest=int(s.iters_slowest), iters_all=int(s.iters_all),
+                         device_time=s.device_time, run_time=s.run_time, host_time=s.host_time,
+                         ahead=dict(ahead=int(ahead), columns=int(a.columns), sent=int(a.sent), hits=int(a.hits),
+                                    discarded=int(a.discarded), called_off=int(a.called_off), hit_iters=int(a.hit_iters),
+                                    discarded_iters=int(a.discarded_iters), called_off_iters=int(a.called_off_iters),
+                                    free_slots=int(a.free_slots), slot_cap=int(a.slot_cap), width=a.width,
+                                    iter_mandatory=a.iter_mandatory, chunks=a.chunks))
     for j, k in enumerate(todo):
         info = infos[j]
         upper = info.upper_glob

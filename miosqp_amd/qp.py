@@ -521,6 +521,65 @@ class OSQP(object):
             return x, list(infos), stats, rfs
         return x, list(infos), stats
 
+    def solve_trees_lockstep_ahead(self, q, l, u, x0, y0, upper0, x_inc0, tree_explor_rule, max_iter_bb, ahead, capacity=0):
+        """solve_trees_lockstep (same arrays) with the spare columns of every wave solving open leaves early
+        (miosqp_qp_solve_trees_lockstep_ahead): a tree may hold up to `ahead` columns of a wave -- its chosen leaf and,
+        in the free columns of the tiles the wave launches anyway, other open leaves and children of nodes solved
+        ahead --, keeps those records until its exploration rule reaches the node and drops them when a pruning removes
+        it.  Results are solve_trees_lockstep's bit for bit; ahead = 1 runs its launches.  ahead >= 1 (ValueError
+        otherwise).
+        Returns (x B x n, [TreeInfo], stats, ahead): stats as solve_trees_lockstep's (width counts all columns, the
+        iteration figures the mandatory columns; node_hviol None), ahead has waves, columns, sent, hits, discarded,
+        called_off, hit_iters, discarded_iters, called_off_iters, free_slots, slot_cap and per wave (the first 65536)
+        width, iter_mandatory, chunks."""
+        who = "solve_trees_lockstep_ahead"
+        if int(ahead) != ahead or int(ahead) < 1:
+            raise ValueError(who + ": ahead must be at least 1")
+        q = np.ascontiguousarray(q, dtype=np.float64)
+        B = q.shape[0]
+        l, u = np.ascontiguousarray(l, dtype=np.float64), np.ascontiguousarray(u, dtype=np.float64)
+        x0, y0 = np.ascontiguousarray(x0, dtype=np.float64), np.ascontiguousarray(y0, dtype=np.float64)
+        if B < 1 or q.shape != (B, self.n) or x0.shape != (B, self.n) or l.shape != (B, self.m) or u.shape != (B, self.m) \
+                or y0.shape != (B, self.m):
+            raise ValueError(who + ": instance-major arrays (B x n, B x M)")
+        up = np.minimum(np.ascontiguousarray(upper0, dtype=np.float64).reshape(B), 1.7e308)
+        xin = None if x_inc0 is None else np.ascontiguousarray(x_inc0, dtype=np.float64).reshape(B, self.n)
+        x = np.zeros((B, self.n))
+        infos = (_lib.TreeInfo * B)()
+        max_iter_bb = 2 ** 31 - 1 if not np.isfinite(max_iter_bb) else int(min(int(max_iter_bb), 2 ** 31 - 1))
+        wcap = max(1, min(max_iter_bb, 65536))
+        width, imax = np.zeros(wcap, dtype=np.int32), np.zeros(wcap, dtype=np.int32)
+        imean, fin = np.zeros(wcap), np.zeros(B, dtype=np.int32)
+        awidth, amand, achunks = (np.zeros(wcap, dtype=np.int32) for _ in range(3))
+        st = _lib.LockstepStats()
+        st.wave_cap = wcap
+        st.wave_width, st.wave_iter_max, st.wave_iter_mean = _lib.as_i(width), _lib.as_i(imax), _lib.as_d(imean)
+        st.finished_at = _lib.as_i(fin)
+        ah = _lib.LockstepAheadStats()
+        ah.wave_cap = wcap
+        ah.wave_width, ah.wave_iter_mandatory, ah.wave_chunks = _lib.as_i(awidth), _lib.as_i(amand), _lib.as_i(achunks)
+        rc = self._lib.miosqp_qp_solve_trees_lockstep_ahead(
+            self._h, B, _lib.as_d(q), _lib.as_d(l), _lib.as_d(u), _lib.as_d(x0), _lib.as_d(y0), _lib.as_d(up),
+            None if xin is None else _lib.as_d(xin), int(tree_explor_rule), max_iter_bb, int(capacity), int(ahead),
+            _lib.as_d(x), infos, C.byref(st), C.byref(ah))
+        _check(rc, who)
+        if rc == 1:
+            msg = _lib.last_error()
+            if "branching" in msg:
+                raise RuntimeError("branching produced l > u")
+            raise ValueError("Lower bound must be lower than or equal to upper bound")
+        k = min(st.waves, wcap)
+        stats = types.SimpleNamespace(
+            waves=st.waves, nodes=st.nodes, max_width=st.max_width, grown=st.grown, iters_slowest=st.iters_slowest,
+            iters_all=st.iters_all, device_time=st.device_time, run_time=st.run_time, host_time=st.host_time, width=width[:k].tolist(),
+            iters_max=imax[:k].tolist(), iters_mean=imean[:k].tolist(), finished_at=fin.tolist(), node_hviol=None)
+        ahs = types.SimpleNamespace(
+            waves=ah.waves, columns=ah.columns, sent=ah.sent, hits=ah.hits, discarded=ah.discarded, called_off=ah.called_off,
+            hit_iters=ah.hit_iters, discarded_iters=ah.discarded_iters, called_off_iters=ah.called_off_iters,
+            free_slots=ah.free_slots, slot_cap=ah.slot_cap, width=awidth[:k].tolist(), iter_mandatory=amand[:k].tolist(),
+            chunks=achunks[:k].tolist())
+        return x, list(infos), stats, ahs
+
     def solve_trees_refill(self, q, l, u, x0, y0, upper0, x_inc0, tree_explor_rule, max_iter_bb, capacity=0):
         """The trees of solve_trees_lockstep (same arrays) on columns that are refilled between chunks
         (miosqp_qp_solve_trees_refill): a column holds one node of one tree, every tree has at most one node in flight, and
