@@ -493,6 +493,57 @@ int miosqp_qp_solve_trees_lockstep_rf(miosqp_qp_engine *e, int32_t B, const doub
                                       miosqp_tree_info *info, miosqp_lockstep_stats *stats,
                                       miosqp_lockstep_rf_stats *rf_stats);
 
+/* ---- the lock-step trees with strong and reliability branching --------------------------------------------
+ * miosqp_qp_solve_trees_lockstep with the branching position chosen as the sequential solve with branching_rule 1 or 2
+ * chooses it (miosqp_amd/bnb.py: Workspace.bound_and_branch -> Workspace.select_branching -> Workspace.strong_branch,
+ * the bookkeeping of Workspace.record_gain / pseudo_costs and the scores of sb_scores; the reference has rule 0 only,
+ * workspace.py:205-230).  On a solved fractional node that is not cut off, after the rounding heuristic of the digest:
+ *   rule 1: with one fractional position (|x - round(x)| > eps_int_feas of miosqp_qp_set_root) that position; otherwise
+ *     the candidates are the sb_candidates most fractional positions (ties to the lower position), ascending;
+ *   rule 2: the candidates are the fractional positions with min(observations down, up) < sb_reliability, cut to the
+ *     sb_candidates most fractional; without one, nothing is solved.
+ * The nodes that have candidates in a wave send their 2K children (K down: u = floor x on the candidate's integer row,
+ * then K up: l = ceil x; the tree's cost, the node's OWN x, y as the warm start, at most sb_max_iter iterations) into
+ * ONE more batch, sliced at max_batch like a wave; a node's children may straddle two slices.  A child's gain is
+ * max(L_child - L_node, 0), 1e30 without an x (status neither SOLVED nor MAX_ITER_REACHED); a candidate's score
+ * max(gain_down, sb_eps) * max(gain_up, sb_eps); rule 1 takes the first maximum.  Rule 2 records the children with an
+ * x as observations (gain per unit distance to floor / ceil, candidate order, down then up), scores every fractional
+ * position -- by pseudo-costs where it has no strong-branching score: mean gain per unit, for a position without
+ * observations in a direction the mean of those means in numpy's summation order, or 1.0 -- and takes the first
+ * maximum in ascending position order; each child of the branching is one more observation when its own solve has an
+ * x.  The tables are per tree and start at zero.  Per wave the host reads the asking nodes' x at the integer
+ * positions (one download) and a 16-byte record per child (one download), and writes the children of the chosen
+ * positions with one launch.  A wave in which no node asks queues nothing more than miosqp_qp_solve_trees_lockstep
+ * does. */
+typedef struct miosqp_lockstep_sb_stats {
+  int32_t batches;        /* strong-branching batches run (waves in which at least one node had candidates) */
+  int32_t reserved;
+  int64_t columns;        /* their columns: 2K per node with K candidates */
+  int64_t iters_slowest;  /* sum over the batches of the slowest child's ADMM iterations */
+  double device_time;     /* seconds between the events around the branching step of the waves that ran a batch, its two
+                             downloads included (part of miosqp_lockstep_stats.device_time) */
+  int32_t *calls;         /* IN, optional (NULL: not wanted), B entries each: strong_branch calls of tree b ... */
+  int32_t *children;      /* ... their children ... */
+  int64_t *iters;         /* ... and the children's ADMM iterations (info[b].osqp_iter counts node relaxations only) */
+  int32_t *first_k;       /* IN, optional debug, B entries: candidates K of tree b's FIRST call (0: it never called) */
+  int32_t *first_chosen;  /* B entries: the argmax of its scores (index into the candidates) */
+  int32_t *first_cand;    /* B x sb_candidates: its candidate positions, ascending (the first K of a row) */
+  int32_t *first_status;  /* B x 2 sb_candidates each: its children as the batch epilogue left them, K down then K up */
+  int32_t *first_iter;    /* (the first 2K of a row): status, iterations, objective at the clamped x -- what */
+  double *first_lower;    /* miosqp_qp_strong_branch returns per child */
+} miosqp_lockstep_sb_stats;
+
+/* Arguments, layouts, info[b], stats, capacity and errors as for miosqp_qp_solve_trees_lockstep.  branching_rule 1 or 2;
+ * sb_candidates in 1 .. 32; sb_max_iter a positive multiple of settings.check_termination (the rule of
+ * miosqp_qp_strong_branch); sb_reliability >= 0; sb_eps > 0: MIOSQP_EARG with a last_error text otherwise, nothing
+ * queued.  MIOSQP_EBOUNDS also when a candidate's child would have l > u. */
+int miosqp_qp_solve_trees_lockstep_sb(miosqp_qp_engine *e, int32_t B, const double *q, const double *l, const double *u,
+                                      const double *x0, const double *y0, const double *upper0, const double *x_inc0,
+                                      int32_t tree_explor_rule, int32_t max_iter_bb, int32_t capacity,
+                                      int32_t branching_rule, int32_t sb_candidates, int32_t sb_max_iter,
+                                      int32_t sb_reliability, double sb_eps, double *x_out, miosqp_tree_info *info,
+                                      miosqp_lockstep_stats *stats, miosqp_lockstep_sb_stats *sb_stats);
+
 /* ---- the same B trees on columns that are refilled between chunks ---------------------------------------
  * miosqp_qp_solve_trees_lockstep without the wave.  The engine's batch runs in chunks of check_termination iterations
  * with one termination test each; here a column holds one node of one tree, counts its own iterations from the chunk it

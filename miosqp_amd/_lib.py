@@ -49,6 +49,12 @@ class LockstepRfStats(C.Structure):
                 ("iters", i64p), ("cand_status", ip), ("cand_iter", ip), ("cand_obj", dp), ("cand_viol", dp)]
 
 
+class LockstepSbStats(C.Structure):
+    _fields_ = [("batches", C.c_int32), ("reserved", C.c_int32), ("columns", C.c_int64), ("iters_slowest", C.c_int64),
+                ("device_time", C.c_double), ("calls", ip), ("children", ip), ("iters", i64p), ("first_k", ip),
+                ("first_chosen", ip), ("first_cand", ip), ("first_status", ip), ("first_iter", ip), ("first_lower", dp)]
+
+
 class LockstepAheadStats(C.Structure):
     _fields_ = [("waves", C.c_int32), ("wave_cap", C.c_int32), ("columns", C.c_int64), ("sent", C.c_int64),
                 ("hits", C.c_int64), ("discarded", C.c_int64), ("called_off", C.c_int64), ("hit_iters", C.c_int64),
@@ -138,6 +144,10 @@ SYMBOLS = {
     "miosqp_qp_solve_trees_lockstep_rf": (C.c_int, [C.c_void_p, C.c_int32, dp, dp, dp, dp, dp, dp, dp, C.c_int32, C.c_int32,
                                                     C.c_int32, C.c_int32, C.c_int32, C.c_int32, dp, C.POINTER(TreeInfo),
                                                     C.POINTER(LockstepStats), C.POINTER(LockstepRfStats)]),
+    "miosqp_qp_solve_trees_lockstep_sb": (C.c_int, [C.c_void_p, C.c_int32, dp, dp, dp, dp, dp, dp, dp, C.c_int32, C.c_int32,
+                                                    C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, dp,
+                                                    C.POINTER(TreeInfo), C.POINTER(LockstepStats),
+                                                    C.POINTER(LockstepSbStats)]),
     "miosqp_qp_solve_trees_lockstep_ahead": (C.c_int, [C.c_void_p, C.c_int32, dp, dp, dp, dp, dp, dp, dp, C.c_int32,
                                                        C.c_int32, C.c_int32, C.c_int32, dp, C.POINTER(TreeInfo),
                                                        C.POINTER(LockstepStats), C.POINTER(LockstepAheadStats)]),

@@ -1231,6 +1231,14 @@ class MIOSQP(object):
         and judged on the device; a winner's value is the device's sum.  `work.lockstep['rf']` holds what `rf_stats`
         counts, summed and per instance; the model's own `rf_stats` is not touched.  True and "refill" keep refusing the
         heuristic, None falls to the sequential path with it.
+        "device" also takes branching_rule 1 and 2 (`OSQP.solve_trees_lockstep_sb`): every node that branches chooses its
+        position as `Workspace.select_branching` does -- per tree the decisions of its sequential solve with that rule,
+        pseudo-costs per tree included --, the strong-branching children of ALL nodes with candidates in a wave as one
+        more batch (sb_candidates, sb_max_iter, sb_reliability, sb_eps as `solve` reads them).  `work.lockstep['sb']`
+        holds what `sb_stats` counts, summed and per instance; the model's own `sb_stats` and pseudo-costs are not
+        touched.  Rule 1 or 2 together with primal_heuristic 1 is refused there, True, "refill" and "ahead" refuse rules
+        1 and 2 (ValueError naming the rule), None falls to the sequential path with them (DESIGN 3k has the
+        measurements).
         "refill": the trees of "device" without the wave (`lockstep.run_refill`, `OSQP.solve_trees_refill`): a column of
         the batch holds one node of one tree and counts its own iterations; after every chunk of check_termination
         iterations the decided columns are harvested and, at that same boundary, loaded again with the next leaf of a
@@ -1337,7 +1345,20 @@ class MIOSQP(object):
                     raise ValueError('solve_many(lockstep="ahead") needs ahead to be an int >= 1 (the most columns one '
                                      'tree may hold in a wave): ahead %r' % (ahead,))
             # (round and fix runs inside the device driver's trees; the other drivers refuse the heuristic)
-            if not (lockstep == "device" and work.rf['on'] and ls.device_rf_supported(work)) and not ls.supported(work):
+            # (... and so do strong and reliability branching, without the heuristic)
+            br = st['branching_rule']
+            if br in (1, 2) and lockstep == "device":
+                if work.rf['on']:
+                    raise ValueError('solve_many(lockstep="device") takes branching_rule %d or primal_heuristic 1, not both '
+                                     'together' % br)
+                if not ls.device_sb_supported(work):
+                    raise ValueError('solve_many(lockstep="device") with branching_rule %d needs the HIP engine with '
+                                     'solve_trees_lockstep_sb, the device digest and tree_explor_rule 0-3' % br)
+            elif br in (1, 2):
+                raise ValueError('solve_many(lockstep="%s") needs branching_rule 0, primal_heuristic 0 and '
+                                 'tree_explor_rule 0-3: branching_rule %d runs inside lockstep="device" and on the '
+                                 'sequential path only' % (lockstep, br))
+            elif not (lockstep == "device" and work.rf['on'] and ls.device_rf_supported(work)) and not ls.supported(work):
                 raise ValueError('solve_many(lockstep="%s") needs branching_rule 0, primal_heuristic 0 and '
                                  'tree_explor_rule 0-3' % lockstep)
             if lockstep == "refill":
@@ -1357,7 +1378,9 @@ class MIOSQP(object):
             batched = hasattr(work.solver, 'solve_batch_q')
             if lockstep and not ls.supported(work):
                 raise ValueError('solve_many(lockstep=True) needs branching_rule 0, primal_heuristic 0 and '
-                                 'tree_explor_rule 0-3')
+                                 'tree_explor_rule 0-3' + (': branching_rule %d runs inside lockstep="device" and on the '
+                                                           'sequential path only' % st['branching_rule']
+                                                           if st['branching_rule'] in (1, 2) else ''))
             if lockstep or (declined and batched and ls.supported(work)):
                 ls.run(self, redo, Q, L, U, up, XI, instances, out, batched)
                 redo = []

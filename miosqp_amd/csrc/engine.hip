@@ -41,6 +41,7 @@
 #include "polish_many_large.hpp"  // ... and of larger ones, S in a slab of device scratch per workgroup (polish_many_large.hip)
 #include "lockstep_trees.hpp"  // the tree logic of B trees in lock step (plain C++; host_lockstep.inc drives it)
 #include "lockstep_ahead.hpp"  // ahead records, shadow leaves and the choice of ahead columns (plain C++; host_lockstep_ahead.inc drives it)
+#include "lockstep_sb.hpp"  // strong and reliability branching in the lock-step trees (plain C++; host_lockstep_sb.inc drives it)
 #include "lockstep_refill.hpp"  // which tree goes into which free column when the columns are refilled between chunks (plain C++; host_refill.inc drives it)
 
 #define QP_INFTY 1e30
@@ -252,6 +253,8 @@ struct CoopNode {
 #include "host_lockstep.inc"  // B trees in lock step driven from the host in C++ (C ABI miosqp_qp_solve_trees_lockstep, miosqp_qp_solve_trees_lockstep_rf)
 #include "host_refill.inc"  // the same trees on columns refilled between chunks (C ABI miosqp_qp_solve_trees_refill)
 #include "host_lockstep_ahead.inc"  // the lock-step trees with spare columns solving open leaves early (C ABI miosqp_qp_solve_trees_lockstep_ahead); its two kernels
+#include "kernels_lockstep_sb.inc"  // strong and reliability branching in the lock-step trees: x at the integer positions, the children's gather, judge and bounds
+#include "host_lockstep_sb.inc"  // ... and its driver (C ABI miosqp_qp_solve_trees_lockstep_sb)
 
 // ------------------------------------------------------------------------------------------
 // C ABI

@@ -26,6 +26,7 @@ struct LockstepStore {
   std::vector<miosqp::lockstep::Tree> trees;
   void *refill = nullptr;  // RefillCols (host_refill.inc): the per-column arrays of solve_trees_refill
   void *ahead = nullptr;   // AheadCols (host_lockstep_ahead.inc): the mandatory flags and records of solve_trees_lockstep_ahead
+  void *sb = nullptr;      // SbStore (host_lockstep_sb.inc): the branching step of solve_trees_lockstep_sb
   // round and fix (solve_trees_lockstep_rf): per candidate column of a heuristic batch the five integers going up, per
   // firing tree its record coming back and, for the winners the host adopts, the tree's number going up
   int rf_inst_cap = 0, rf_col_cap = 0, rf_trip_inst = 0;  // (rf_trip_inst: the trees the column block's second part holds)
@@ -42,6 +43,7 @@ struct LockstepStore {
 
 void refill_free(void *p);  // (host_refill.inc)
 void ahead_free(void *p);   // (host_lockstep_ahead.inc)
+void sb_free(void *p);      // (host_lockstep_sb.inc)
 
 // kls_heur_rows in place of kb_heur_rows at the end of slice_run (declared in host.inc; the kernel is used here, see kernels_lockstep.inc)
 void launch_ls_heur_rows(miosqp_qp_engine *e, const LsRoots &roots, int ntiles) {
@@ -64,6 +66,7 @@ void lockstep_free(void *p) {
   if (L->rf_ev1) hipEventDestroy(L->rf_ev1);
   refill_free(L->refill);
   ahead_free(L->ahead);
+  sb_free(L->sb);
   delete L;
 }
 

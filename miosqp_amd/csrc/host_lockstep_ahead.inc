@@ -1,4 +1,4 @@
-// part of engine.hip (included there, not compiled alone; the LAST file of the translation unit): the lock-step trees of
+// part of engine.hip (included there, not compiled alone; behind every file of the translation unit but host_lockstep_sb.inc and its kernels): the lock-step trees of
 // host_lockstep.inc with the spare columns of every wave put to use (C ABI miosqp_qp_solve_trees_lockstep_ahead).  A wave
 // launches whole tiles of 64 columns; behind the L mandatory columns -- one chosen leaf per live tree, what
 // miosqp_qp_solve_trees_lockstep sends -- the rest of the last tile carries other open leaves of the same trees and children

@@ -15,7 +15,9 @@ set up itself (`_Tree`).  One wave:
 leaves of all trees stay in device slots, the per-tree logic runs in C++ and Python sees the B results.  It is asked for
 by name: `solve_many(lockstep="device")`.  It is also the one driver that runs round and fix (primal_heuristic = 1)
 inside the trees (`OSQP.solve_trees_lockstep_rf`): the candidates of every tree that fires in a wave go out as one more
-batch.
+batch.  And the one that runs branching_rule 1 and 2 (`OSQP.solve_trees_lockstep_sb`): the strong-branching children of
+every node with candidates in a wave go out as one more batch, and the position is chosen per tree as
+`Workspace.select_branching` chooses it.
 
 `run_refill` drops the wave (`OSQP.solve_trees_refill`, miosqp_qp_solve_trees_refill): a column of the batch holds one
 node of one tree and counts its own iterations; after every chunk of check_termination iterations the decided columns
@@ -177,6 +179,14 @@ def device_rf_supported(work):
         and st['branching_rule'] == 0 and st['tree_explor_rule'] in (0, 1, 2, 3)
 
 
+def device_sb_supported(work):
+    """strong and reliability branching inside the device driver (`OSQP.solve_trees_lockstep_sb`): the entry, the
+    on-device digest, branching_rule 1 or 2, no round and fix, rules 0-3"""
+    st = work.settings
+    return hasattr(work.solver, 'solve_trees_lockstep_sb') and work.root_on_device and work.data.n_int > 0 \
+        and st['branching_rule'] in (1, 2) and not work.rf['on'] and st['tree_explor_rule'] in (0, 1, 2, 3)
+
+
 def run_device(model, todo, Q, L, U, up, XI, instances, out, capacity=0):
     """`run` in the library: the trees of instances `todo` advance in lock step inside ONE call of
     `OSQP.solve_trees_lockstep` -- leaves in device slots, the tree logic in C++ (csrc/lockstep_trees.hpp), per wave five
@@ -190,7 +200,13 @@ def run_device(model, todo, Q, L, U, up, XI, instances, out, capacity=0):
     `Workspace.primal_heuristic` reads them), and work.lockstep['rf'] = dict(calls, candidates, feasible, improved,
     osqp_iter -- the sums of what `rf_stats` counts per sequential solve --, batches, columns, iters_slowest,
     device_time, per_instance={k: dict(calls, candidates, feasible, improved, osqp_iter)}); the dicts' osqp_iter counts
-    node relaxations only, as work.osqp_iter does."""
+    node relaxations only, as work.osqp_iter does.
+    With branching_rule 1 or 2 (work.sb['rule']) the call is `OSQP.solve_trees_lockstep_sb`: every node that branches
+    chooses its position as `Workspace.select_branching` does, the strong-branching children of all nodes with
+    candidates in a wave as one more batch (sb_candidates, sb_max_iter, sb_reliability, sb_eps as the workspace reads
+    them), and work.lockstep['sb'] = dict(calls, children, osqp_iter -- the sums of what `sb_stats` counts per
+    sequential solve --, batches, columns, iters_slowest, device_time, per_instance={k: dict(calls, children,
+    osqp_iter)}).  The model's own sb_stats and pseudo-costs are not touched."""
     work, data, st = model.work, model.work.data, model.work.settings
     todo = list(todo)
     n, M = data.n, data.m + data.n_int
@@ -198,8 +214,12 @@ def run_device(model, todo, Q, L, U, up, XI, instances, out, capacity=0):
     any_inc = bool(np.any(np.isfinite(up[todo])))
     args = (Q[todo], L[todo], U[todo], np.zeros((len(todo), n)), np.zeros((len(todo), M)), up[todo],
             XI[todo] if any_inc else None, st['tree_explor_rule'], st['max_iter_bb'])
-    r = None
-    if work.rf['on']:
+    r = b = None
+    if work.sb['rule'] in (1, 2):
+        sb = work.sb
+        X, infos, s, b = work.solver.solve_trees_lockstep_sb(*args, sb['rule'], sb['K'], sb['max_iter'], sb['reliability'],
+                                                             sb['eps'], capacity=capacity)
+    elif work.rf['on']:
         X, infos, s, r = work.solver.solve_trees_lockstep_rf(*args, work.rf['K'], work.rf['max_iter'], work.rf['every'],
                                                              capacity=capacity)
     else:
@@ -217,6 +237,11 @@ def run_device(model, todo, Q, L, U, up, XI, instances, out, capacity=0):
                                    improved=sum(r.improved), osqp_iter=sum(r.iters), batches=r.batches,
                                    columns=int(r.columns), iters_slowest=int(r.iters_slowest),
                                    device_time=r.device_time, per_instance=per)
+    if b is not None:
+        per = {k: dict(calls=b.calls[j], children=b.children[j], osqp_iter=b.iters[j]) for j, k in enumerate(todo)}
+        work.lockstep['sb'] = dict(calls=sum(b.calls), children=sum(b.children), osqp_iter=sum(b.iters), batches=b.batches,
+                                   columns=int(b.columns), iters_slowest=int(b.iters_slowest), device_time=b.device_time,
+                                   per_instance=per)
     for j, k in enumerate(todo):
         info = infos[j]
         upper = info.upper_glob

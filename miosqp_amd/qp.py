@@ -454,8 +454,27 @@ class OSQP(object):
         return self._trees_lockstep(q, l, u, x0, y0, upper0, x_inc0, tree_explor_rule, max_iter_bb, capacity, 0,
                                     (int(rf_candidates), int(rf_max_iter), int(rf_every), bool(first_call)))
 
-    def _trees_lockstep(self, q, l, u, x0, y0, upper0, x_inc0, tree_explor_rule, max_iter_bb, capacity, node_hviol, rf):
+    def solve_trees_lockstep_sb(self, q, l, u, x0, y0, upper0, x_inc0, tree_explor_rule, max_iter_bb, branching_rule,
+                                sb_candidates, sb_max_iter, sb_reliability, sb_eps, capacity=0, first_call=False):
+        """solve_trees_lockstep with strong (branching_rule 1) or reliability branching (2) inside the trees
+        (miosqp_qp_solve_trees_lockstep_sb): every node that branches chooses its position as
+        `Workspace.select_branching` does; the 2K children of all nodes with candidates in a wave are ONE more batch,
+        built, solved (at most sb_max_iter iterations each) and read off on the device.  sb_candidates in 1..32,
+        sb_max_iter a positive multiple of check_termination, sb_reliability >= 0, sb_eps > 0 (ValueError otherwise).
+        Returns (x, [TreeInfo], stats, sb): stats as solve_trees_lockstep's (TreeInfo.osqp_iter and the iteration counts
+        there are the node relaxations'), sb has batches, columns, iters_slowest, device_time and per instance calls,
+        children, iters (lists).  first_call: debug, sb.first_call is then a namespace of k, chosen (B), cand
+        (B x sb_candidates), status, iter, lower (B x 2 sb_candidates: K down then K up in the first 2K entries) --
+        every tree's first call as `strong_branch` reports it (k = 0 for a tree that never called); None otherwise."""
+        return self._trees_lockstep(q, l, u, x0, y0, upper0, x_inc0, tree_explor_rule, max_iter_bb, capacity, 0, None,
+                                    (int(branching_rule), int(sb_candidates), int(sb_max_iter), int(sb_reliability),
+                                     float(sb_eps), bool(first_call)))
+
+    def _trees_lockstep(self, q, l, u, x0, y0, upper0, x_inc0, tree_explor_rule, max_iter_bb, capacity, node_hviol, rf,
+                        sb=None):
         who = "solve_trees_lockstep" if rf is None else "solve_trees_lockstep_rf"
+        if sb is not None:
+            who = "solve_trees_lockstep_sb"
         q = np.ascontiguousarray(q, dtype=np.float64)
         B = q.shape[0]
         l, u = np.ascontiguousarray(l, dtype=np.float64), np.ascontiguousarray(u, dtype=np.float64)
@@ -478,7 +497,30 @@ class OSQP(object):
         st.finished_at = _lib.as_i(fin)
         if hv is not None:
             st.node_hviol, st.node_cap = _lib.as_d(hv), int(node_hviol)
-        if rf is None:
+        if sb is not None:
+            cnt = [np.zeros(B, dtype=np.int32) for _ in range(2)]
+            sb_it = np.zeros(B, dtype=np.int64)
+            bs = _lib.LockstepSbStats()
+            bs.calls, bs.children = (_lib.as_i(a) for a in cnt)
+            bs.iters = sb_it.ctypes.data_as(_lib.i64p)
+            first = None
+            if sb[5]:
+                Kc = max(sb[1], 1)
+                first = types.SimpleNamespace(k=np.zeros(B, dtype=np.int32), chosen=np.full(B, -1, dtype=np.int32),
+                                              cand=np.full((B, Kc), -1, dtype=np.int32),
+                                              status=np.full((B, 2 * Kc), -1, dtype=np.int32),
+                                              iter=np.zeros((B, 2 * Kc), dtype=np.int32), lower=np.full((B, 2 * Kc), np.nan))
+                bs.first_k, bs.first_chosen, bs.first_cand = _lib.as_i(first.k), _lib.as_i(first.chosen), _lib.as_i(first.cand)
+                bs.first_status, bs.first_iter, bs.first_lower = _lib.as_i(first.status), _lib.as_i(first.iter), \
+                    _lib.as_d(first.lower)
+            rc = self._lib.miosqp_qp_solve_trees_lockstep_sb(
+                self._h, B, _lib.as_d(q), _lib.as_d(l), _lib.as_d(u), _lib.as_d(x0), _lib.as_d(y0), _lib.as_d(up),
+                None if xin is None else _lib.as_d(xin), int(tree_explor_rule), max_iter_bb, int(capacity), sb[0], sb[1], sb[2],
+                sb[3], sb[4], _lib.as_d(x), infos, C.byref(st), C.byref(bs))
+            if rc == -1 and "solve_trees_lockstep_sb: " in _lib.last_error() and \
+                    any(w in _lib.last_error() for w in ("branching_rule", "sb_")):
+                raise ValueError(_lib.last_error())
+        elif rf is None:
             rc = self._lib.miosqp_qp_solve_trees_lockstep(
                 self._h, B, _lib.as_d(q), _lib.as_d(l), _lib.as_d(u), _lib.as_d(x0), _lib.as_d(y0), _lib.as_d(up),
                 None if xin is None else _lib.as_d(xin), int(tree_explor_rule), max_iter_bb, int(capacity), _lib.as_d(x), infos,
@@ -513,6 +555,11 @@ class OSQP(object):
             waves=st.waves, nodes=st.nodes, max_width=st.max_width, grown=st.grown, iters_slowest=st.iters_slowest,
             iters_all=st.iters_all, device_time=st.device_time, run_time=st.run_time, host_time=st.host_time, width=width[:k].tolist(),
             iters_max=imax[:k].tolist(), iters_mean=imean[:k].tolist(), finished_at=fin.tolist(), node_hviol=hv)
+        if sb is not None:
+            sbs = types.SimpleNamespace(
+                batches=bs.batches, columns=bs.columns, iters_slowest=bs.iters_slowest, device_time=bs.device_time,
+                calls=cnt[0].tolist(), children=cnt[1].tolist(), iters=sb_it.tolist(), first_call=first)
+            return x, list(infos), stats, sbs
         if rf is not None:
             rfs = types.SimpleNamespace(
                 batches=rs.batches, columns=rs.columns, iters_slowest=rs.iters_slowest, device_time=rs.device_time,
