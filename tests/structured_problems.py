@@ -1,4 +1,6 @@
-"""Structured (non-random-dense) MIQP instances for the parity tests of the register-resident solvers.
+"""Structured (non-random-dense) MIQP instances for the parity tests of the register-resident solvers and, at reduced
+size through tests/batch_structured_inputs.py, of the lock-step batch path (solve_batch / solve_batch_q and the lock-step
+trees of solve_many).
 
 Every GPU parity instance of n + M in 193 .. 2048 used to be `problems.random_miqp` (positive definite P = Pt Pt',
 finite two-sided rows, density >= 0.7).  These generators produce what a relaxation engine meets in practice and the
