@@ -405,6 +405,50 @@ int miosqp_qp_solve_trees(miosqp_qp_engine *e, int32_t B, const double *q, const
                           const double *x0, const double *y0, const double *upper0, const double *x_inc0,
                           int32_t tree_explor_rule, int32_t max_iter_bb, double *x_out, miosqp_tree_info *info);
 
+/* ---- trees of DIFFERENT models in one launch ----------------------------------------------------------
+ * Which of the one-launch tree kernels takes this engine as it stands: 0 none (what miosqp_qp_solve_trees answers with
+ * MIOSQP_EUNSUPPORTED or MIOSQP_EARG: no product-form factor, no integer rows or root, no integer variable, more than
+ * 160 KB of LDS; also a NULL engine or a failed runtime call), 1 the one-wavefront kernel (n + M <= 64, the explicit
+ * inverse passed its guard, MIOSQP_TREE_WAVE not 0), 2 the one-workgroup kernel.  The call performs what the first tree
+ * launch of such an engine performs: for n + M <= 64 the explicit inverse and Kc are built if they are missing and the
+ * inverse is checked (a tripped guard turns the engine to form 2 for good). */
+int miosqp_qp_tree_form(miosqp_qp_engine *e);
+
+typedef struct miosqp_models_stats {
+  int32_t launches;         /* tree launches of the call: 0, 1 or 2 (the cost scaling before them is not counted) */
+  int32_t models_wave;      /* models run by the one-wavefront kernel (form 1) */
+  int32_t models_group;     /* models run by the one-workgroup kernel (form 2) */
+  int32_t pad;
+  int64_t lds_bytes;        /* dynamic LDS of the workgroup launch: the largest need among its models (0: no such launch) */
+  double device_time;       /* seconds between the events around upload, launches and download */
+  double run_time;          /* wall seconds of the call */
+} miosqp_models_stats;
+
+/* B MIQPs on B DIFFERENT engines -- each with its own P, A, shapes, factor, scalings and settings -- every tree in one
+ * launch per kernel form: workgroup (or wavefront) b runs model b exactly as miosqp_qp_solve_trees(engines[b], 1, q[b], ...)
+ * would, bit for bit.  It replaces B calls of miosqp_qp_solve_trees with B = 1, i.e. the reference's pattern
+ * MIOSQP.update_vectors + set_x0 + solve (/root/reference/miosqp/solver.py:174-212) repeated on B different models, by one
+ * upload, at most two tree launches (form 1 models, form 2 models; a form without a model launches nothing), one download
+ * and one synchronisation.  One pointer per model, because shapes differ: q[b], x0[b], x_out[b] n_b doubles; l[b], u[b],
+ * y0[b] M_b; upper0 B (>= 1.7e308: no incumbent); x_inc0[b] n_b doubles or NULL; tree_explor_rule[b] 0..3 and
+ * max_iter_bb[b] >= 1 per model; the ADMM settings are each engine's own.  info[b] as miosqp_qp_solve_trees fills it
+ * (device_time: the call's divided by B); x_out[b]: the incumbent found, else the one handed in.  No engine's own linear
+ * cost or bounds are touched.
+ * Refused before anything is queued, with a last_error text naming the model: B < 1 or a NULL argument, an engine listed
+ * twice, a tree_explor_rule outside 0..3, max_iter_bb < 1 (MIOSQP_EARG); l > u in a root (MIOSQP_EBOUNDS); engines on
+ * different devices, an engine with streaming chunks in flight (MIOSQP_EARG); an engine whose miosqp_qp_tree_form is 0
+ * (MIOSQP_EUNSUPPORTED: the caller runs that model on its own).
+ * Memory: the leaf stores, staging blocks and the table of per-workgroup arguments are one arena taken from the device
+ * pool of engines[0], with a pinned host mirror of its staged part; both then BELONG TO THAT ENGINE: they are reused by
+ * later calls that have this engine first, grow when such a call needs more, and are released by its miosqp_qp_cleanup.
+ * Nothing of a call outlives it in any other engine, so the engines may be cleaned up in any order between calls.
+ * The launches run on engines[0]'s stream; work queued on the other engines' streams is waited for first. */
+int miosqp_qp_solve_trees_models(int32_t B, miosqp_qp_engine *const *engines, const double *const *q, const double *const *l,
+                                 const double *const *u, const double *const *x0, const double *const *y0,
+                                 const double *upper0, const double *const *x_inc0, const int32_t *tree_explor_rule,
+                                 const int32_t *max_iter_bb, double *const *x_out, miosqp_tree_info *info,
+                                 miosqp_models_stats *stats);
+
 /* ---- B trees in lock step, driven from the host in C++ on device-resident leaves -----------------------
  * miosqp_qp_solve_trees for problems of any size: the B instances of the reference's MPC pattern
  * (MIOSQP.update_vectors + set_x0 + solve per instance, /root/reference/miosqp/solver.py:174-212, each solve the loop of

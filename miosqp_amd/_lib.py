@@ -10,6 +10,7 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG, "libmiosqp_hip.so")
 
 dp = C.POINTER(C.c_double)
+dpp = C.POINTER(dp)
 ip = C.POINTER(C.c_int32)
 i64p = C.POINTER(C.c_int64)
 
@@ -34,6 +35,11 @@ class TreeInfo(C.Structure):
     _fields_ = [("nodes", C.c_int32), ("osqp_iter", C.c_int32), ("leaves_left", C.c_int32), ("overflow", C.c_int32),
                 ("max_leaves", C.c_int32), ("found", C.c_int32), ("upper_glob", C.c_double), ("lower_glob", C.c_double),
                 ("device_time", C.c_double), ("run_time", C.c_double)]
+
+
+class ModelsStats(C.Structure):
+    _fields_ = [("launches", C.c_int32), ("models_wave", C.c_int32), ("models_group", C.c_int32), ("pad", C.c_int32),
+                ("lds_bytes", C.c_int64), ("device_time", C.c_double), ("run_time", C.c_double)]
 
 
 class LockstepStats(C.Structure):
@@ -139,6 +145,9 @@ SYMBOLS = {
     "miosqp_qp_get_polish_many_large_classes": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int8)]),
     "miosqp_qp_solve_trees": (C.c_int, [C.c_void_p, C.c_int32, dp, dp, dp, dp, dp, dp, dp, C.c_int32, C.c_int32, dp,
                                         C.POINTER(TreeInfo)]),
+    "miosqp_qp_tree_form": (C.c_int, [C.c_void_p]),
+    "miosqp_qp_solve_trees_models": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), dpp, dpp, dpp, dpp, dpp, dp, dpp, ip, ip, dpp,
+                                               C.POINTER(TreeInfo), C.POINTER(ModelsStats)]),
     "miosqp_qp_solve_trees_lockstep": (C.c_int, [C.c_void_p, C.c_int32, dp, dp, dp, dp, dp, dp, dp, C.c_int32, C.c_int32,
                                                  C.c_int32, dp, C.POINTER(TreeInfo), C.POINTER(LockstepStats)]),
     "miosqp_qp_solve_trees_lockstep_rf": (C.c_int, [C.c_void_p, C.c_int32, dp, dp, dp, dp, dp, dp, dp, C.c_int32, C.c_int32,

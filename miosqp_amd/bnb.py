@@ -124,6 +124,16 @@ def polish_repair_setting(settings):
     return int(it)
 
 
+def one_launch_trees_ok(work):
+    """would `solve_many` (and `solve_models`) try the one-launch trees for this workspace: the entry point is there, the
+    settings are the plain search's, and the engine has not declined before"""
+    st, data = work.settings, work.data
+    return hasattr(work.solver, 'solve_trees') and st.get('device_tree', True) and st['branching_rule'] == 0 \
+        and not work.rf['on'] \
+        and st['tree_explor_rule'] in (0, 1, 2, 3) and data.n_int > 0 and 'eps_abs' in work.qp_settings \
+        and st.get('device_digest', True) and not getattr(work, '_no_trees', False)
+
+
 def exploration_setting(settings):
     """The exploration rule, checked (MIOSQP.setup calls this before anything is built).  0: depth first; 1: the
     reference's default (depth first, then the largest bound); 2: best bound; 3: depth first until the first incumbent,
@@ -1130,6 +1140,43 @@ class MIOSQP(object):
                 U[k, :m] = inst['u']
         return Q, L, U
 
+    def _instance_incumbent(self, inst, q, l, u):
+        """Workspace.set_x0 (workspace.py:94-111) on one instance's data (q: n, l, u: M): (value, x0) when the instance
+        brings an x0 that is feasible for its rows and integral, None when it brings none or an invalid one (printed)"""
+        work, data, st = self.work, self.work.data, self.work.settings
+        x0 = inst.get('x0')
+        if x0 is None:
+            return None
+        x0 = np.asarray(x0, dtype=float)
+        z = data.A.dot(x0)
+        tol = work.qp_settings['eps_abs']
+        xi = x0[data.i_idx]
+        if not (np.any(z < l - tol) or np.any(z > u + tol)) and \
+                not np.any(abs(xi - np.round(xi)) > st['eps_int_feas']):
+            return .5 * np.dot(x0, data.P.dot(x0)) + np.dot(q, x0), x0
+        print('Invalid initial solution!\n')
+        return None
+
+    def _tree_result(self, info, x_tree, upper0, run_time):
+        """solve_many's dict from the record of a one-launch tree (info: TreeInfo, x_tree: the incumbent the launch
+        returned, upper0: the value of the incumbent that went in, inf for none)"""
+        data, st = self.work.data, self.work.settings
+        upper = info.upper_glob
+        # workspace.py:352-373 decides on the loop counter, not on the leaf list: a tree that closes with its
+        # last permitted node reports the MAX_ITER family, exactly as solve() does (iter_num = nodes + 1)
+        finished = int(info.nodes) + 1 < st['max_iter_bb']
+        if upper != np.inf:
+            status = MI_SOLVED if finished else MI_MAX_ITER_FEASIBLE
+        elif upper >= 0:
+            status = MI_PRIMAL_INFEASIBLE if finished else MI_MAX_ITER_UNSOLVED
+        else:
+            status = MI_DUAL_INFEASIBLE
+        x = x_tree.copy() if (info.found or np.isfinite(upper0)) else np.empty(data.n)
+        if status in (MI_SOLVED, MI_MAX_ITER_FEASIBLE):
+            x[data.i_idx] = np.round(x[data.i_idx])
+        return dict(x=x, upper_glob=upper, status=status, nodes=int(info.nodes),
+                    osqp_iter=int(info.osqp_iter), run_time=run_time)
+
     def polish_many(self, instances, results, tau=None, repair_iter=20, large=False):
         """Polishes the answers of `solve_many(instances)` in place, all in ONE device call.  For every result with status
         MI_SOLVED / MI_MAX_ITER_FEASIBLE: its x with the integers rounded, the instance's l, u with the integer rows fixed
@@ -1270,27 +1317,14 @@ class MIOSQP(object):
         if B == 0:
             return []
         n, m, M = data.n, data.m, data.m + data.n_int
-        ok_engine = hasattr(work.solver, 'solve_trees') and st.get('device_tree', True) and st['branching_rule'] == 0 \
-            and not work.rf['on'] \
-            and st['tree_explor_rule'] in (0, 1, 2, 3) and data.n_int > 0 and 'eps_abs' in work.qp_settings \
-            and st.get('device_digest', True) and not getattr(work, '_no_trees', False)
+        ok_engine = one_launch_trees_ok(work)
         Q, L, U = self._instance_vectors(instances)
         up = np.full(B, np.inf); XI = np.zeros((B, n)); any_inc = False
         for k, inst in enumerate(instances):
-            x0 = inst.get('x0')
+            x0 = self._instance_incumbent(inst, Q[k], L[k], U[k])
             if x0 is not None:
-                # Workspace.set_x0 (workspace.py:94-111) on this instance's data
-                x0 = np.asarray(x0, dtype=float)
-                z = data.A.dot(x0)
-                tol = work.qp_settings['eps_abs']
-                xi = x0[data.i_idx]
-                if not (np.any(z < L[k] - tol) or np.any(z > U[k] + tol)) and \
-                        not np.any(abs(xi - np.round(xi)) > st['eps_int_feas']):
-                    up[k] = .5 * np.dot(x0, data.P.dot(x0)) + np.dot(Q[k], x0)
-                    XI[k] = x0
-                    any_inc = True
-                else:
-                    print('Invalid initial solution!\n')
+                up[k], XI[k] = x0
+                any_inc = True
         out = [None] * B
         redo = list(range(B))
         declined = True  # the one-launch path: absent, switched off, or it returned None
@@ -1311,21 +1345,7 @@ class MIOSQP(object):
                     if info.overflow:
                         redo.append(k)
                         continue
-                    upper = info.upper_glob
-                    # workspace.py:352-373 decides on the loop counter, not on the leaf list: a tree that closes with its
-                    # last permitted node reports the MAX_ITER family, exactly as solve() does (iter_num = nodes + 1)
-                    finished = int(info.nodes) + 1 < st['max_iter_bb']
-                    if upper != np.inf:
-                        status = MI_SOLVED if finished else MI_MAX_ITER_FEASIBLE
-                    elif upper >= 0:
-                        status = MI_PRIMAL_INFEASIBLE if finished else MI_MAX_ITER_UNSOLVED
-                    else:
-                        status = MI_DUAL_INFEASIBLE
-                    x = X[k].copy() if (info.found or np.isfinite(up[k])) else np.empty(n)
-                    if status in (MI_SOLVED, MI_MAX_ITER_FEASIBLE):
-                        x[data.i_idx] = np.round(x[data.i_idx])
-                    out[k] = dict(x=x, upper_glob=upper, status=status, nodes=int(info.nodes),
-                                  osqp_iter=int(info.osqp_iter), run_time=dt / B)
+                    out[k] = self._tree_result(info, X[k], up[k], dt / B)
         if isinstance(lockstep, str):
             # the driver in the library, asked for by name (the default is not this one)
             from miosqp_amd import lockstep as ls
@@ -1426,3 +1446,123 @@ class MIOSQP(object):
 
     def set_x0(self, x0):
         self.work.set_x0(x0)
+
+
+def _models_own_reason(work):
+    """why `solve_models` leaves a model to its own `solve_many` (None: it goes into the launch)"""
+    st = work.settings
+    if not hasattr(work.solver, 'solve_trees') or not hasattr(work.solver, 'tree_form'):
+        return 'backend without the one-launch trees'
+    if not st.get('device_tree', True):
+        return 'device_tree off'
+    if st['branching_rule'] != 0:
+        return 'branching_rule %d' % st['branching_rule']
+    if work.rf['on']:
+        return 'primal_heuristic on'
+    if work.data.n_int == 0:
+        return 'n_int == 0'
+    if getattr(work, '_no_trees', False):
+        return 'the one-launch trees declined this model before'
+    if not one_launch_trees_ok(work):
+        return 'settings beyond the one-launch trees'
+    try:
+        require_plain_search(st, "solve_models", rule=False, heuristic=False)
+    except ValueError:
+        return 'settings solve_many refuses'
+    if work.solver.tree_form() == 0:
+        return 'tree_form 0: beyond the one-launch trees'
+    return None
+
+
+def solve_models(models, instances=None, info=None):
+    """One MIQP on each of several DIFFERENT set-up models -- each with its own P, A, shapes and settings --, the trees
+    of all of them in ONE call of the library (`qp.solve_trees_models`, miosqp_qp_solve_trees_models: at most two
+    launches, workgroup or wavefront b runs model b).  It replaces the loop `models[k].solve_many([instances[k]])`: one
+    upload, one synchronisation and one interpreter round trip for the whole list instead of one per model (the
+    reference's benchmark draws a new P and A for every MIQP; so does a sweep over plants).
+
+    models: a list of set-up MIOSQP objects, each at most once.  instances: None, or one dict per model with the keys of
+    `solve_many` (q, l, u, x0, each optional).  Returns one dict per model with the keys `solve_many` returns; result k
+    is what `models[k].solve_many([instances[k]])[0]` returns -- status, nodes, osqp_iter equal, x and upper_glob bit
+    for bit (run_time: the call's time divided by the number of launched models).
+
+    A model goes into the launch when `solve_many` would try its one-launch path for it and its engine's `tree_form()`
+    is not 0; every other model (the CPU oracle backend, branching_rule / primal_heuristic not 0, device_tree off, no
+    integer variable, an engine beyond one workgroup) and every model whose tree overflowed is solved by its own
+    `solve_many([instance])`, and that result stands in its place.  The models are left as they were (q, l, u, the leaf
+    list, the statistics); `work.trees_info` of a launched model gets its own TreeInfo as a one-element list.
+
+    ValueError before any launch: an empty list, len(instances) != len(models), a model listed twice (both positions
+    named), a model that was not set up, l > u in an instance (its position named).
+
+    info: a dict that is filled with launched (positions), own ({position: why}), forms ({'wave': .., 'group': ..}),
+    launches, device_time (seconds) and overflow (positions)."""
+    models = list(models)
+    B = len(models)
+    if B == 0:
+        raise ValueError('solve_models: an empty list of models')
+    if instances is None:
+        instances = [{} for _ in range(B)]
+    instances = list(instances)
+    if len(instances) != B:
+        raise ValueError('solve_models: %d instances for %d models (one dict per model)' % (len(instances), B))
+    for k, mdl in enumerate(models):
+        for j in range(k):
+            if models[j] is mdl:
+                raise ValueError('solve_models: the model at position %d is listed again at position %d' % (j, k))
+    for k, mdl in enumerate(models):
+        if getattr(mdl, 'work', None) is None:
+            raise ValueError('solve_models: the model at position %d was not set up' % k)
+    vec = []
+    for k, mdl in enumerate(models):
+        Q, L, U = mdl._instance_vectors([instances[k]])
+        if np.any(L[0] > U[0]):
+            raise ValueError('solve_models: instance %d: Lower bound must be lower than or equal to upper bound' % k)
+        vec.append((Q[0], L[0], U[0]))
+    own = {}
+    launched = []
+    for k, mdl in enumerate(models):
+        why = _models_own_reason(mdl.work)
+        if why is None:
+            launched.append(k)
+        else:
+            own[k] = why
+    out = [None] * B
+    overflow = []
+    forms = dict(wave=0, group=0)
+    launches, device_time = 0, 0.0
+    if launched:
+        from miosqp_amd import qp
+        inc = {}
+        for k in launched:
+            inc[k] = models[k]._instance_incumbent(instances[k], *vec[k])
+        t0 = time()
+        r = qp.solve_trees_models(
+            [models[k].work.solver for k in launched], [vec[k][0] for k in launched], [vec[k][1] for k in launched],
+            [vec[k][2] for k in launched], [np.zeros(models[k].work.data.n) for k in launched],
+            [np.zeros(len(vec[k][1])) for k in launched], [np.inf if inc[k] is None else inc[k][0] for k in launched],
+            [None if inc[k] is None else inc[k][1] for k in launched],
+            [models[k].work.settings['tree_explor_rule'] for k in launched],
+            [models[k].work.settings['max_iter_bb'] for k in launched])
+        dt = time() - t0
+        if r is None:  # (an engine declined after all: every model on its own)
+            for k in launched:
+                own[k] = 'the library declined the call'
+            launched = []
+        else:
+            X, infos, stats = r
+            forms = dict(wave=int(stats.models_wave), group=int(stats.models_group))
+            launches, device_time = int(stats.launches), float(stats.device_time)
+            for j, k in enumerate(launched):
+                models[k].work.trees_info = [infos[j]]
+                if infos[j].overflow:
+                    overflow.append(k)
+                    continue
+                out[k] = models[k]._tree_result(infos[j], X[j], np.inf if inc[k] is None else inc[k][0], dt / len(launched))
+    for k in range(B):
+        if out[k] is None:
+            out[k] = models[k].solve_many([instances[k]])[0]
+    if info is not None:
+        info.update(launched=list(launched), own=dict(own), forms=forms, launches=launches, device_time=device_time,
+                    overflow=list(overflow))
+    return out

@@ -42,6 +42,7 @@
 #include "lockstep_trees.hpp"  // the tree logic of B trees in lock step (plain C++; host_lockstep.inc drives it)
 #include "lockstep_ahead.hpp"  // ahead records, shadow leaves and the choice of ahead columns (plain C++; host_lockstep_ahead.inc drives it)
 #include "lockstep_sb.hpp"  // strong and reliability branching in the lock-step trees (plain C++; host_lockstep_sb.inc drives it)
+#include "models_plan.hpp"  // trees of different models in one launch: argument checks and arena layout (plain C++; host_models.inc drives it)
 #include "lockstep_refill.hpp"  // which tree goes into which free column when the columns are refilled between chunks (plain C++; host_refill.inc drives it)
 
 #define QP_INFTY 1e30
@@ -255,6 +256,7 @@ struct CoopNode {
 #include "host_lockstep_ahead.inc"  // the lock-step trees with spare columns solving open leaves early (C ABI miosqp_qp_solve_trees_lockstep_ahead); its two kernels
 #include "kernels_lockstep_sb.inc"  // strong and reliability branching in the lock-step trees: x at the integer positions, the children's gather, judge and bounds
 #include "host_lockstep_sb.inc"  // ... and its driver (C ABI miosqp_qp_solve_trees_lockstep_sb)
+#include "host_models.inc"  // what the one-launch tree entries share; trees of different models in one launch (C ABI miosqp_qp_tree_form, miosqp_qp_solve_trees_models)
 
 // ------------------------------------------------------------------------------------------
 // C ABI
@@ -664,6 +666,7 @@ int miosqp_qp_cleanup(miosqp_qp_engine *e) {
   if (e->hb_dbl) hipHostFree(e->hb_dbl);
   if (e->hb_q) hipHostFree(e->hb_q);
   if (e->h_der) hipHostFree(e->h_der);
+  if (e->mm_host) hipHostFree(e->mm_host);
   polish_free(e);
   polish_many_free(e->polm);
   polish_many_free(e->polml);
@@ -1924,19 +1927,8 @@ int miosqp_qp_solve_tree(miosqp_qp_engine *e, const double *l, const double *u, 
     return MIOSQP_EARG;
   }
   const int n = e->n, M = e->M, p = e->d.n_int;
-  // (the tree kernels decide the same way on the device: explicit inverse there and n + M small enough -> no product
-  //  form in LDS; an engine without W yet gets it below when n + M <= 64, which only shrinks what the kernel uses)
-  const bool tree_w = e->d.W != nullptr && n + M <= RES_W_MAX;
-  size_t lds = tree_lds_doubles(n, M, tree_w) * sizeof(double);
   int tree_sp_off = -1;
-  {
-    const size_t sp_bytes = res_sp_doubles(e->sp_nnzA, e->sp_nnzP, n, M) * sizeof(double);
-    if (tree_w && e->sp_nnzA > 0 && lds + sp_bytes <= 160 * 1024 &&
-        !(getenv("MIOSQP_RES_SP") && atoi(getenv("MIOSQP_RES_SP")) == 0)) {
-      tree_sp_off = (int)(lds / sizeof(double));
-      lds += sp_bytes;
-    }
-  }
+  const size_t lds = tree_lds_bytes(e, &tree_sp_off);
   if (!e->fold || lds > 160 * 1024 || p < 1) {  // whatever form single nodes use: the product-form rows must exist and fit
     g_err = "solve_tree: only for problems whose product-form factor, iterates and leaf list fit 160 KB of LDS";
     return MIOSQP_EUNSUPPORTED;
@@ -1944,30 +1936,8 @@ int miosqp_qp_solve_tree(miosqp_qp_engine *e, const double *l, const double *u, 
   for (int i = 0; i < M; i++)
     if (l[i] > u[i]) return MIOSQP_EBOUNDS;
   const double t0 = wall();
-  // n + M <= 64: the whole search in ONE wavefront on the explicit KKT inverse (k_tree_w); MIOSQP_TREE_WAVE=0 keeps k_tree
-  bool wave = n + M <= TW && !e->guard_tripped && !(getenv("MIOSQP_TREE_WAVE") && atoi(getenv("MIOSQP_TREE_WAVE")) == 0);
-  if (wave && !e->d.Kc) {  // an engine in the LDS-resident form has not built Kc (and perhaps W) yet
-    Dev &d = e->d;
-    const int N = n + M;
-    d.ldw = (N + 7) & ~7;
-    double *Wd = const_cast<double *>(d.W), *Kc = nullptr;
-    int rcw = 0;
-    if (!Wd) {
-      rcw = dalloc(e, &Wd, (size_t)N * d.ldw + 64);
-      if (!rcw) rcw = miosqp_device_kkt_inverse(d.f_rows, d.ldf, d.d2inv, n, M, Wd, d.ldw, e->stream);
-    }
-    if (!rcw) rcw = dalloc(e, &Kc, (size_t)N * d.ldw + 64);
-    if (rcw) return rcw;
-    d.W = Wd;
-    d.Kc = Kc;
-    hipLaunchKernelGGL(k_build_kc, dim3((N + 255) / 256, N), dim3(256), 0, e->stream, d, Kc);
-    if (int rcg = inverse_guard(e)) return rcg;
-    if (e->guard_tripped) {  // (kernels_guard.inc) the explicit inverse failed its check: the workgroup kernel with the sweeps
-      d.W = nullptr;
-      d.Kc = nullptr;
-      wave = false;
-    }
-  }
+  bool wave = false;  // the one-wavefront kernel (host_models.inc: the lazy build of W / Kc and its guard)
+  if (int rcw = tree_wave_prepare(e, &wave)) return rcw;
   if (!e->tree_ready) {
     HIPCHK(lds_limit_once((const void *)k_tree, 1));
     int rc = dalloc(e, &e->ta.lf_lo, (size_t)TREE_CAP * p);
@@ -1991,11 +1961,7 @@ int miosqp_qp_solve_tree(miosqp_qp_engine *e, const double *l, const double *u, 
   ta.max_nodes = max_iter_bb;
   ta.max_iter = e->st.max_iter;
   ta.check_every = e->st.check_termination;
-  {  // lanes per row of the two sweeps, as the LDS-resident solver picks them
-    auto pow2_floor = [](int v) { int q = 1; while (2 * q <= v) q *= 2; return q; };
-    ta.TG1 = std::min(64, std::max(1, pow2_floor(RES_THREADS / n)));
-    ta.TG2 = std::min(64, std::max(1, pow2_floor(RES_THREADS / (n + M))));
-  }
+  tree_lane_groups(n, M, ta);
   ta.upper0 = have_inc ? upper0 : 1.0 / 0.0;
   ta.done = nullptr;
   ta.sp_off = tree_sp_off;
@@ -2131,17 +2097,8 @@ int miosqp_qp_solve_trees(miosqp_qp_engine *e, int32_t B, const double *q, const
   }
   const int n = e->n, M = e->M, p = e->d.n_int;
   const size_t blk = 3 * (size_t)M + n;
-  const bool tree_w = e->d.W != nullptr && n + M <= RES_W_MAX;
-  size_t lds = tree_lds_doubles(n, M, tree_w) * sizeof(double);
   int tree_sp_off = -1;
-  {
-    const size_t sp_bytes = res_sp_doubles(e->sp_nnzA, e->sp_nnzP, n, M) * sizeof(double);
-    if (tree_w && e->sp_nnzA > 0 && lds + sp_bytes <= 160 * 1024 &&
-        !(getenv("MIOSQP_RES_SP") && atoi(getenv("MIOSQP_RES_SP")) == 0)) {
-      tree_sp_off = (int)(lds / sizeof(double));
-      lds += sp_bytes;
-    }
-  }
+  const size_t lds = tree_lds_bytes(e, &tree_sp_off);
   if (!e->fold || lds > 160 * 1024 || p < 1) {
     g_err = "solve_trees: only for problems whose product-form factor, iterates and leaf list fit 160 KB of LDS";
     return MIOSQP_EUNSUPPORTED;
@@ -2149,29 +2106,8 @@ int miosqp_qp_solve_trees(miosqp_qp_engine *e, int32_t B, const double *q, const
   for (size_t k = 0; k < (size_t)B * M; k++)
     if (l[k] > u[k]) return MIOSQP_EBOUNDS;
   const double t0 = wall();
-  bool wave = n + M <= TW && !e->guard_tripped && !(getenv("MIOSQP_TREE_WAVE") && atoi(getenv("MIOSQP_TREE_WAVE")) == 0);
-  if (wave && !e->d.Kc) {  // as miosqp_qp_solve_tree: an engine in the LDS-resident form has not built Kc (and perhaps W) yet
-    Dev &d = e->d;
-    const int N = n + M;
-    d.ldw = (N + 7) & ~7;
-    double *Wd = const_cast<double *>(d.W), *Kc = nullptr;
-    int rcw = 0;
-    if (!Wd) {
-      rcw = dalloc(e, &Wd, (size_t)N * d.ldw + 64);
-      if (!rcw) rcw = miosqp_device_kkt_inverse(d.f_rows, d.ldf, d.d2inv, n, M, Wd, d.ldw, e->stream);
-    }
-    if (!rcw) rcw = dalloc(e, &Kc, (size_t)N * d.ldw + 64);
-    if (rcw) return rcw;
-    d.W = Wd;
-    d.Kc = Kc;
-    hipLaunchKernelGGL(k_build_kc, dim3((N + 255) / 256, N), dim3(256), 0, e->stream, d, Kc);
-    if (int rcg = inverse_guard(e)) return rcg;
-    if (e->guard_tripped) {  // (kernels_guard.inc) the explicit inverse failed its check: the workgroup kernel with the sweeps
-      d.W = nullptr;
-      d.Kc = nullptr;
-      wave = false;
-    }
-  }
+  bool wave = false;  // as miosqp_qp_solve_tree
+  if (int rcw = tree_wave_prepare(e, &wave)) return rcw;
   if (!wave) HIPCHK(lds_limit_once((const void *)k_tree, 1));
   if (B > e->tb_cap) {  // (a larger batch takes new arrays; the old ones stay with the pool until cleanup)
     const size_t cap = (size_t)std::max(B, 2 * e->tb_cap);
@@ -2219,11 +2155,7 @@ int miosqp_qp_solve_trees(miosqp_qp_engine *e, int32_t B, const double *q, const
   ta.max_nodes = max_iter_bb;
   ta.max_iter = e->st.max_iter;
   ta.check_every = e->st.check_termination;
-  {
-    auto pow2_floor = [](int v) { int q2 = 1; while (2 * q2 <= v) q2 *= 2; return q2; };
-    ta.TG1 = std::min(64, std::max(1, pow2_floor(RES_THREADS / n)));
-    ta.TG2 = std::min(64, std::max(1, pow2_floor(RES_THREADS / (n + M))));
-  }
+  tree_lane_groups(n, M, ta);
   ta.upper0 = 1.0 / 0.0;
   ta.lf_lo = e->tb_lo; ta.lf_hi = e->tb_hi; ta.lf_x = e->tb_x; ta.lf_y = e->tb_y;
   ta.inc_x = e->tb_inc;
@@ -2271,6 +2203,21 @@ int miosqp_qp_solve_trees(miosqp_qp_engine *e, int32_t B, const double *q, const
   e->loop_ms += ms;
   e->loop_iters += iters;
   return 0;
+}
+
+int miosqp_qp_tree_form(miosqp_qp_engine *e) {
+  if (!e) return 0;
+  if (e->device >= 0 && hipSetDevice(e->device) != hipSuccess) return 0;
+  const int form = tree_form_of(e);
+  return form < 0 ? 0 : form;
+}
+
+int miosqp_qp_solve_trees_models(int32_t B, miosqp_qp_engine *const *engines, const double *const *q, const double *const *l,
+                                 const double *const *u, const double *const *x0, const double *const *y0,
+                                 const double *upper0, const double *const *x_inc0, const int32_t *tree_explor_rule,
+                                 const int32_t *max_iter_bb, double *const *x_out, miosqp_tree_info *info,
+                                 miosqp_models_stats *stats) {
+  return models_run(B, engines, q, l, u, x0, y0, upper0, x_inc0, tree_explor_rule, max_iter_bb, x_out, info, stats);
 }
 
 int miosqp_qp_debug_iterate(miosqp_qp_engine *e, int32_t k, double *x, double *z, double *y) {

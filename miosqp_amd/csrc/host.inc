@@ -67,6 +67,10 @@ struct miosqp_qp_engine {
   TreeOut *tb_out = nullptr;
   std::vector<double> tb_host;   // staging: [raw block | inc | upper] in, [inc] out
   std::vector<TreeOut> tb_hout;
+  // miosqp_qp_solve_trees_models with this engine first: the call's arena (from this engine's pool) and the pinned mirror
+  // of its staged part, capacities in doubles
+  double *mm_dev = nullptr, *mm_host = nullptr;
+  size_t mm_cap = 0, mm_host_cap = 0;
   void *search = nullptr;  // NodeSearch (host_search.inc)
   void *sdriver = nullptr;  // StreamDriver (host_stream.inc)
   void *lockstep = nullptr;  // LockstepStore (host_lockstep.inc)

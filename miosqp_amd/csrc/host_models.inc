@@ -1,0 +1,245 @@
+// part of engine.hip (included there, not compiled alone): what the one-launch tree entries share, and the trees of
+// DIFFERENT models in one launch (C ABI miosqp_qp_tree_form, miosqp_qp_solve_trees_models; kernels k_tree_m / k_tree_w_m /
+// k_scale_q_models in kernels_tree.inc; argument checks and arena layout in models_plan.hpp).
+extern "C" {
+static int stage_wait(miosqp_qp_engine *e, int k);
+}
+
+namespace {
+
+// dynamic LDS of k_tree for this engine as it stands, and where the LDS copy of the sparse rows starts inside it (or -1)
+size_t tree_lds_bytes(const miosqp_qp_engine *e, int *sp_off) {
+  const int n = e->n, M = e->M;
+  // (the tree kernels decide the same way on the device: explicit inverse there and n + M small enough -> no product
+  //  form in LDS; an engine without W yet gets it in tree_wave_prepare when n + M <= 64, which only shrinks what the kernel uses)
+  const bool tree_w = e->d.W != nullptr && n + M <= RES_W_MAX;
+  size_t lds = tree_lds_doubles(n, M, tree_w) * sizeof(double);
+  *sp_off = -1;
+  const size_t sp_bytes = res_sp_doubles(e->sp_nnzA, e->sp_nnzP, n, M) * sizeof(double);
+  if (tree_w && e->sp_nnzA > 0 && lds + sp_bytes <= 160 * 1024 && !(getenv("MIOSQP_RES_SP") && atoi(getenv("MIOSQP_RES_SP")) == 0)) {
+    *sp_off = (int)(lds / sizeof(double));
+    lds += sp_bytes;
+  }
+  return lds;
+}
+
+// n + M <= 64: the whole search in ONE wavefront on the explicit KKT inverse (k_tree_w); MIOSQP_TREE_WAVE=0 keeps k_tree.
+// An engine in the LDS-resident form has not built Kc (and perhaps W) yet: built here, once, and the inverse is checked.
+int tree_wave_prepare(miosqp_qp_engine *e, bool *wave_out) {
+  const int n = e->n, M = e->M;
+  bool wave = n + M <= TW && !e->guard_tripped && !(getenv("MIOSQP_TREE_WAVE") && atoi(getenv("MIOSQP_TREE_WAVE")) == 0);
+  if (wave && !e->d.Kc) {
+    Dev &d = e->d;
+    const int N = n + M;
+    d.ldw = (N + 7) & ~7;
+    double *Wd = const_cast<double *>(d.W), *Kc = nullptr;
+    int rcw = 0;
+    if (!Wd) {
+      rcw = dalloc(e, &Wd, (size_t)N * d.ldw + 64);
+      if (!rcw) rcw = miosqp_device_kkt_inverse(d.f_rows, d.ldf, d.d2inv, n, M, Wd, d.ldw, e->stream);
+    }
+    if (!rcw) rcw = dalloc(e, &Kc, (size_t)N * d.ldw + 64);
+    if (rcw) return rcw;
+    d.W = Wd;
+    d.Kc = Kc;
+    hipLaunchKernelGGL(k_build_kc, dim3((N + 255) / 256, N), dim3(256), 0, e->stream, d, Kc);
+    if (int rcg = inverse_guard(e)) return rcg;
+    if (e->guard_tripped) {  // (kernels_guard.inc) the explicit inverse failed its check: the workgroup kernel with the sweeps
+      d.W = nullptr;
+      d.Kc = nullptr;
+      wave = false;
+    }
+  }
+  *wave_out = wave;
+  return 0;
+}
+
+// lanes per row of the two sweeps, as the LDS-resident solver picks them
+void tree_lane_groups(int n, int M, TreeArgs &ta) {
+  auto pow2_floor = [](int v) { int q = 1; while (2 * q <= v) q *= 2; return q; };
+  ta.TG1 = std::min(64, std::max(1, pow2_floor(RES_THREADS / n)));
+  ta.TG2 = std::min(64, std::max(1, pow2_floor(RES_THREADS / (n + M))));
+}
+
+// miosqp_qp_tree_form without the entry's own checks: 0, 1, 2, or a negative error code of the lazy build
+int tree_form_of(miosqp_qp_engine *e) {
+  if (!e->have_int || !e->d.digest) return 0;
+  int sp_off = -1;
+  if (!e->fold || e->d.n_int < 1 || tree_lds_bytes(e, &sp_off) > 160 * 1024) return 0;
+  bool wave = false;
+  if (int rc = tree_wave_prepare(e, &wave)) return rc < 0 ? rc : MIOSQP_EHIP;
+  return wave ? 1 : 2;
+}
+
+// the arena of miosqp_qp_solve_trees_models and its pinned mirror: they belong to the engine that was first in the call
+int models_reserve(miosqp_qp_engine *e, size_t total_doubles, size_t up_doubles) {
+  if (total_doubles > e->mm_cap) {  // (a larger call takes a new arena; the old one stays with the pool until cleanup)
+    const size_t cap = std::max(total_doubles, 2 * e->mm_cap);
+    int rc = pool_reserve(e, cap * sizeof(double) + 4096);
+    if (!rc) rc = dalloc(e, &e->mm_dev, cap);
+    if (rc) return rc;
+    e->mm_cap = cap;
+  }
+  if (up_doubles > e->mm_host_cap) {
+    const size_t cap = std::max(up_doubles, 2 * e->mm_host_cap);
+    HIPCHK(hipStreamSynchronize(e->stream));
+    if (e->mm_host) hipHostFree(e->mm_host);
+    e->mm_host = nullptr;
+    e->mm_host_cap = 0;
+    HIPCHK(hipHostMalloc((void **)&e->mm_host, cap * sizeof(double), hipHostMallocDefault));
+    e->mm_host_cap = cap;
+  }
+  return 0;
+}
+
+int models_run(int32_t B, miosqp_qp_engine *const *engines, const double *const *q, const double *const *l,
+               const double *const *u, const double *const *x0, const double *const *y0, const double *upper0,
+               const double *const *x_inc0, const int32_t *rule, const int32_t *max_iter_bb, double *const *x_out,
+               miosqp_tree_info *info, miosqp_models_stats *stats) {
+  namespace mm = miosqp::models;
+  // ---- refused before anything is queued ----
+  {
+    std::vector<int> Mv;
+    if (B >= 1 && engines)
+      for (int b = 0; b < B; b++) Mv.push_back(engines[b] ? engines[b]->M : 0);
+    std::string err;
+    if (int rc = mm::check_args(B, (const void *const *)engines, Mv.data(), q, l, u, x0, y0, upper0, x_inc0, rule, max_iter_bb,
+                                (const void *const *)x_out, info, stats, err)) {
+      g_err = err;
+      return rc;
+    }
+  }
+  miosqp_qp_engine *e0 = engines[0];
+  for (int b = 0; b < B; b++) {
+    miosqp_qp_engine *e = engines[b];
+    if (e->device != e0->device) {
+      g_err = "solve_trees_models: model " + std::to_string(b) + " lives on device " + std::to_string(e->device) + ", model 0 on device " +
+              std::to_string(e0->device);
+      return MIOSQP_EARG;
+    }
+    if (e->pool_pending) {
+      g_err = "solve_trees_models: streaming chunks are still in flight (pool_collect first), model " + std::to_string(b);
+      return MIOSQP_EARG;
+    }
+  }
+  ENTER(e0);
+  const double t0 = wall();
+  std::vector<mm::Shape> sh((size_t)B);
+  for (int b = 0; b < B; b++) {
+    miosqp_qp_engine *e = engines[b];
+    const int form = tree_form_of(e);  // (the lazy build of W / Kc and its guard: the engine's own state, on its own stream)
+    if (form < 0) return form;
+    if (form == 0) {
+      g_err = "solve_trees_models: the one-launch trees do not take model " + std::to_string(b) +
+              " (integer rows and root set? product-form factor, iterates and leaf list within 160 KB of LDS?)";
+      return MIOSQP_EUNSUPPORTED;
+    }
+    sh[(size_t)b] = mm::Shape{e->n, e->M, e->d.n_int, form};
+  }
+  const mm::Plan P = mm::plan(sh, sizeof(TreeModel), (size_t)TREE_CAP);
+  if (int rc = models_reserve(e0, P.total_doubles, P.up_doubles)) return rc;
+  if (P.n2) HIPCHK(lds_limit_once((const void *)k_tree_m, 13));
+  // every other engine's stream in front of the launches: an update or a lazy build queued there has finished
+  for (int b = 1; b < B; b++) {
+    if (int rc = stage_wait(engines[b], 0)) return rc;
+    if (int rc = stage_wait(engines[b], 1)) return rc;
+    if (engines[b]->stream != e0->stream) HIPCHK(hipStreamSynchronize(engines[b]->stream));
+  }
+  // ---- the staged part: table, roots and costs, incumbents (the table is rebuilt every call: Dev changes under
+  //      update_lin_cost, a lazy build of W or a tripped guard) ----
+  double *hs = e0->mm_host, *dv = e0->mm_dev;
+  TreeModel *tab_h = reinterpret_cast<TreeModel *>(hs), *tab_d = reinterpret_cast<TreeModel *>(dv);
+  size_t lds_max = 0;
+  for (int b = 0; b < B; b++) {
+    miosqp_qp_engine *e = engines[b];
+    const mm::Slot &s = P.slot[(size_t)b];
+    const size_t n = (size_t)e->n, M = (size_t)e->M;
+    double *r = hs + s.raw;
+    memcpy(r, l[b], sizeof(double) * M);
+    memcpy(r + M, u[b], sizeof(double) * M);
+    memcpy(r + 2 * M, x0[b], sizeof(double) * n);
+    memcpy(r + 2 * M + n, y0[b], sizeof(double) * M);
+    memcpy(hs + s.qraw, q[b], sizeof(double) * n);
+    const bool have = x_inc0[b] != nullptr && upper0[b] < 1.7e308;
+    if (have) memcpy(hs + s.inc, x_inc0[b], sizeof(double) * n);
+    else memset(hs + s.inc, 0, sizeof(double) * n);
+    memset(hs + s.out, 0, sizeof(double) * mm::OUT_DOUBLES);
+    TreeModel &t = tab_h[s.entry];
+    t.d = e->d;
+    t.d.q = dv + s.q;
+    t.d.qraw = dv + s.qraw;
+    t.d.raw_l = dv + s.raw;
+    t.d.raw_u = dv + s.raw + M;
+    t.d.raw_x = dv + s.raw + 2 * M;
+    t.d.raw_y = dv + s.raw + 2 * M + n;
+    t.d.root_l = t.d.raw_l;  // the rounded point is tested against the instance's own root rows
+    t.d.root_u = t.d.raw_u;
+    t.d.prof = nullptr;
+    TreeArgs ta{};
+    ta.rule = rule[b];
+    ta.max_nodes = max_iter_bb[b];
+    ta.max_iter = e->st.max_iter;
+    ta.check_every = e->st.check_termination;
+    tree_lane_groups(e->n, e->M, ta);
+    ta.upper0 = have ? upper0[b] : 1.0 / 0.0;
+    ta.lf_lo = dv + s.lf_lo;
+    ta.lf_hi = dv + s.lf_hi;
+    ta.lf_x = dv + s.lf_x;
+    ta.lf_y = dv + s.lf_y;
+    ta.inc_x = dv + s.inc;
+    ta.out = reinterpret_cast<TreeOut *>(dv + s.out);
+    ta.done = nullptr;
+    ta.sp_off = -1;
+    ta.batch = 0;
+    ta.upper_b = nullptr;
+    if (sh[(size_t)b].form == 2) {  // (after the form is settled: W may have come or gone in tree_form_of)
+      const size_t lds = tree_lds_bytes(e, &ta.sp_off);
+      lds_max = std::max(lds_max, lds);
+    }
+    t.ta = ta;
+  }
+  static_assert(sizeof(TreeOut) <= mm::OUT_DOUBLES * sizeof(double), "TreeOut fits its place in the arena");
+  // ---- one upload, the costs scaled, at most two tree launches, one download, one synchronisation ----
+  HIPCHK(hipEventRecord(e0->ev0, e0->stream));
+  HIPCHK(hipMemcpyAsync(dv, hs, sizeof(double) * P.up_doubles, hipMemcpyHostToDevice, e0->stream));
+  hipLaunchKernelGGL(k_scale_q_models, dim3((unsigned)B), dim3(64), 0, e0->stream, tab_d);
+  if (P.n1) hipLaunchKernelGGL(k_tree_w_m, dim3((unsigned)P.n1), dim3(TW), 0, e0->stream, tab_d);
+  if (P.n2) hipLaunchKernelGGL(k_tree_m, dim3((unsigned)P.n2), dim3(RES_THREADS), lds_max, e0->stream, tab_d + P.n1);
+  HIPCHK(hipMemcpyAsync(hs + P.down_off, dv + P.down_off, sizeof(double) * P.down_doubles, hipMemcpyDeviceToHost, e0->stream));
+  HIPCHK(hipEventRecord(e0->ev1, e0->stream));
+  HIPCHK(hipStreamSynchronize(e0->stream));
+  float ms = 0;
+  HIPCHK(hipEventElapsedTime(&ms, e0->ev0, e0->ev1));
+  const double wall_s = wall() - t0;
+  for (int b = 0; b < B; b++) {
+    miosqp_qp_engine *e = engines[b];
+    const mm::Slot &s = P.slot[(size_t)b];
+    TreeOut o;
+    memcpy(&o, hs + s.out, sizeof o);
+    info[b].nodes = o.nodes;
+    info[b].osqp_iter = o.osqp_iter;
+    info[b].leaves_left = o.leaves_left;
+    info[b].overflow = o.overflow;
+    info[b].max_leaves = o.max_leaves;
+    info[b].found = o.found;
+    info[b].upper_glob = o.upper;
+    info[b].lower_glob = o.lower_glob;
+    info[b].device_time = 1e-3 * ms / B;  // the call's device time, shared equally
+    info[b].run_time = wall_s / B;
+    const bool have = x_inc0[b] != nullptr && upper0[b] < 1.7e308;
+    if (o.found) memcpy(x_out[b], hs + s.inc, sizeof(double) * (size_t)e->n);
+    else if (have) memcpy(x_out[b], x_inc0[b], sizeof(double) * (size_t)e->n);
+    e->loop_ms += ms / B;
+    e->loop_iters += o.osqp_iter;
+  }
+  stats->launches = (P.n1 ? 1 : 0) + (P.n2 ? 1 : 0);
+  stats->models_wave = P.n1;
+  stats->models_group = P.n2;
+  stats->pad = 0;
+  stats->lds_bytes = (int64_t)lds_max;
+  stats->device_time = 1e-3 * ms;
+  stats->run_time = wall_s;
+  return 0;
+}
+
+}  // namespace

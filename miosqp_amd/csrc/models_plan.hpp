@@ -1,0 +1,136 @@
+// Trees of different models in one launch (miosqp_qp_solve_trees_models): the host logic that needs neither an engine nor
+// the device -- the argument checks that refuse a call before anything is queued, and the layout of the call's arena.
+// Plain C++ (no HIP): engine.hip includes it, and so does the stand-alone sanitized program under tests/.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+namespace miosqp {
+namespace models {
+
+constexpr int ERR_ARG = -1;     // MIOSQP_EARG
+constexpr int ERR_BOUNDS = 1;   // MIOSQP_EBOUNDS
+constexpr size_t OUT_DOUBLES = 8;  // room of one outcome record (TreeOut: 48 bytes)
+
+// The checks that read only the caller's arrays, in the order the entry point documents.  M[b]: rows of model b (general
+// rows and integer rows), known once engines[b] is known to be non-NULL.  0, or the error code with `err` naming the model.
+inline int check_args(int32_t B, const void *const *engines, const int *M, const double *const *q, const double *const *l,
+                      const double *const *u, const double *const *x0, const double *const *y0, const double *upper0,
+                      const double *const *x_inc0, const int32_t *rule, const int32_t *max_iter_bb, const void *const *x_out,
+                      const void *info, const void *stats, std::string &err) {
+  const std::string who = "solve_trees_models: ";
+  if (B < 1) {
+    err = who + "B must be at least 1";
+    return ERR_ARG;
+  }
+  if (!engines || !M || !q || !l || !u || !x0 || !y0 || !upper0 || !x_inc0 || !rule || !max_iter_bb || !x_out || !info || !stats) {
+    err = who + "a NULL argument";
+    return ERR_ARG;
+  }
+  for (int b = 0; b < B; b++) {
+    if (!engines[b] || !q[b] || !l[b] || !u[b] || !x0[b] || !y0[b] || !x_out[b]) {  // (x_inc0[b] may be NULL: no incumbent)
+      err = who + "a NULL pointer for model " + std::to_string(b);
+      return ERR_ARG;
+    }
+  }
+  for (int b = 1; b < B; b++)
+    for (int a = 0; a < b; a++)
+      if (engines[a] == engines[b]) {
+        err = who + "the engine of model " + std::to_string(a) + " is listed again as model " + std::to_string(b);
+        return ERR_ARG;
+      }
+  for (int b = 0; b < B; b++) {
+    if (rule[b] < 0 || rule[b] > 3) {
+      err = who + "tree_explor_rule " + std::to_string(rule[b]) + " of model " + std::to_string(b) + " is outside 0..3";
+      return ERR_ARG;
+    }
+    if (max_iter_bb[b] < 1) {
+      err = who + "max_iter_bb of model " + std::to_string(b) + " must be at least 1";
+      return ERR_ARG;
+    }
+  }
+  for (int b = 0; b < B; b++)
+    for (int i = 0; i < M[b]; i++)
+      if (l[b][i] > u[b][i]) {
+        err = who + "l > u in the root of model " + std::to_string(b);
+        return ERR_BOUNDS;
+      }
+  return 0;
+}
+
+struct Shape {
+  int n, M, p;  // variables, rows (general + integer), integer variables
+  int form;     // 1: one wavefront, 2: one workgroup
+};
+
+// where model b's arrays lie in the arena (offsets in doubles from its base) and which table entry is its own
+struct Slot {
+  int entry;
+  size_t raw, qraw;  // l | u | x0 | y0 (3 M + n), the raw cost (n): uploaded
+  size_t inc, out;   // incumbent (n), outcome (OUT_DOUBLES): uploaded and downloaded
+  size_t q;          // the scaled cost (n)
+  size_t lf_lo, lf_hi, lf_x, lf_y;  // the leaf store: cap x p, cap x p, cap x n, cap x M
+};
+
+// [ table | raw, qraw of every model | inc, out of every model | q and leaf store of every model ]: the first three parts
+// go up in ONE copy, the third comes back in ONE copy.  The table holds the one-wavefront models first (the launch over
+// them reads entries [0, n1)), then the workgroup models (entries [n1, n1 + n2)), each group in the caller's order.
+struct Plan {
+  std::vector<Slot> slot;
+  int n1 = 0, n2 = 0;
+  size_t table_doubles = 0;
+  size_t up_doubles = 0;               // what the host stages and uploads: [0, up_doubles)
+  size_t down_off = 0, down_doubles = 0;  // what comes back
+  size_t total_doubles = 0;
+};
+
+inline size_t round_up(size_t v, size_t to) { return (v + to - 1) / to * to; }
+
+inline Plan plan(const std::vector<Shape> &sh, size_t entry_bytes, size_t tree_cap) {
+  Plan P;
+  const size_t B = sh.size();
+  P.slot.resize(B);
+  for (const Shape &s : sh) (s.form == 1 ? P.n1 : P.n2)++;
+  int k1 = 0, k2 = P.n1;
+  for (size_t b = 0; b < B; b++) P.slot[b].entry = sh[b].form == 1 ? k1++ : k2++;
+  P.table_doubles = round_up((B * entry_bytes + 7) / 8, 32);
+  size_t at = P.table_doubles;
+  for (size_t b = 0; b < B; b++) {
+    const size_t n = (size_t)sh[b].n, M = (size_t)sh[b].M;
+    P.slot[b].raw = at;
+    at += 3 * M + n;
+    P.slot[b].qraw = at;
+    at += n;
+  }
+  at = round_up(at, 2);  // (16-byte alignment of the part that comes back)
+  P.down_off = at;
+  for (size_t b = 0; b < B; b++) {
+    P.slot[b].inc = at;
+    at += (size_t)sh[b].n;
+    P.slot[b].out = at;
+    at += OUT_DOUBLES;
+  }
+  P.down_doubles = at - P.down_off;
+  P.up_doubles = at;
+  at = round_up(at, 32);
+  for (size_t b = 0; b < B; b++) {
+    const size_t n = (size_t)sh[b].n, M = (size_t)sh[b].M, p = (size_t)sh[b].p;
+    P.slot[b].q = at;
+    at += round_up(n, 2);
+    P.slot[b].lf_lo = at;
+    at += tree_cap * p;
+    P.slot[b].lf_hi = at;
+    at += tree_cap * p;
+    P.slot[b].lf_x = at;
+    at += tree_cap * n;
+    P.slot[b].lf_y = at;
+    at += tree_cap * M;
+  }
+  P.total_doubles = at;
+  return P;
+}
+
+}  // namespace models
+}  // namespace miosqp

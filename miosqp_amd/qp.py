@@ -78,6 +78,48 @@ def _f64(a, size, name):
     return a
 
 
+def solve_trees_models(solvers, q, l, u, x0, y0, upper0, x_inc0, rules, max_iter_bb):
+    """One MIQP on each of B DIFFERENT engines, every tree in one launch per kernel form (miosqp_qp_solve_trees_models):
+    model b is what `solvers[b].solve_trees(q[b][None], ...)` solves, bit for bit.  Lists of per-model arrays (q, x0: n_b;
+    l, u, y0: M_b), upper0: B incumbent values (inf: none), x_inc0: per model an array or None, rules / max_iter_bb: per
+    model.  Returns ([x_b], [TreeInfo], stats) -- stats: launches, models_wave, models_group, lds_bytes, device_time,
+    run_time -- or None when the library declines (MIOSQP_EUNSUPPORTED: some engine's tree_form() is 0).  ValueError for
+    l > u in a root, RuntimeError (with the library's text, which names the model) for every other refusal."""
+    B = len(solvers)
+    if not (len(q) == len(l) == len(u) == len(x0) == len(y0) == len(upper0) == len(x_inc0) == len(rules) == len(max_iter_bb) == B):
+        raise ValueError("solve_trees_models: one entry per model in every list")
+    lib = _lib.load()
+
+    def ptrs(arrs):
+        return (_lib.dp * max(B, 1))(*[None if a is None else _lib.as_d(a) for a in arrs])
+
+    for s in solvers:
+        if s._h is None:
+            raise ValueError("solve_trees_models: an engine that was not set up (or was closed)")
+    q = [_f64(a, s.n, "q") for a, s in zip(q, solvers)]
+    l = [_f64(a, s.m, "l") for a, s in zip(l, solvers)]
+    u = [_f64(a, s.m, "u") for a, s in zip(u, solvers)]
+    x0 = [_f64(a, s.n, "x0") for a, s in zip(x0, solvers)]
+    y0 = [_f64(a, s.m, "y0") for a, s in zip(y0, solvers)]
+    up = np.minimum(np.ascontiguousarray(upper0, dtype=np.float64).reshape(B), 1.7e308)
+    xin = [None if (a is None or not up[b] < 1.7e308) else _f64(a, solvers[b].n, "x_inc0") for b, a in enumerate(x_inc0)]
+    x = [np.zeros(s.n) for s in solvers]
+    rl = np.ascontiguousarray(rules, dtype=np.int32).reshape(B)
+    mi = np.array([2 ** 31 - 1 if not np.isfinite(v) else int(min(int(v), 2 ** 31 - 1)) for v in max_iter_bb],
+                  dtype=np.int32).reshape(B)
+    infos = (_lib.TreeInfo * max(B, 1))()
+    stats = _lib.ModelsStats()
+    hs = (C.c_void_p * max(B, 1))(*[s._h.value for s in solvers])
+    rc = lib.miosqp_qp_solve_trees_models(B, hs, ptrs(q), ptrs(l), ptrs(u), ptrs(x0), ptrs(y0), _lib.as_d(up), ptrs(xin),
+                                          _lib.as_i(rl), _lib.as_i(mi), ptrs(x), infos, C.byref(stats))
+    if rc == -5:
+        return None
+    _check(rc, "solve_trees_models")
+    if rc == 1:
+        raise ValueError("Lower bound must be lower than or equal to upper bound (%s)" % _lib.last_error())
+    return x, list(infos)[:B], stats
+
+
 class DevicePtr(object):
     """`count` doubles at address `addr` of DEVICE memory (a slice of a torch tensor, say): accepted wherever a leaf's
     vectors go in or come out (search_add_leaf / search_take_leaf, stream_*, pool_write_node / pool_read_node) -- the
@@ -427,6 +469,13 @@ class OSQP(object):
         if rc == 1:
             raise ValueError("Lower bound must be lower than or equal to upper bound")
         return x, list(infos)
+
+    def tree_form(self):
+        """Which one-launch tree kernel takes this engine (miosqp_qp_tree_form): 0 none -- `solve_trees` would return
+        None --, 1 one wavefront (n + M <= 64), 2 one workgroup.  Builds what the first tree launch would build."""
+        if self._h is None:
+            return 0
+        return int(self._lib.miosqp_qp_tree_form(self._h))
 
     def solve_trees_lockstep(self, q, l, u, x0, y0, upper0, x_inc0, tree_explor_rule, max_iter_bb, capacity=0,
                              node_hviol=0):
