@@ -449,6 +449,73 @@ int miosqp_qp_solve_trees_models(int32_t B, miosqp_qp_engine *const *engines, co
                                  const int32_t *max_iter_bb, double *const *x_out, miosqp_tree_info *info,
                                  miosqp_models_stats *stats);
 
+/* ---- set-up of many small models in ONE launch -----------------------------------------------------------
+ * What the reference does once per MIQP with osqp.OSQP().setup() (/root/reference/miosqp/workspace.py:63-68), for B
+ * models with their own P and A at once: the equilibration and the row packing stay on the host, per model, exactly as
+ * miosqp_qp_setup does them; the whole dense part -- S = Pbar + sigma I + rho Abar^T Abar, its LDL^T, Linv / LinvT /
+ * d2inv, the product form (f_rows, f_GmT, f_Ad, f_Atd, f_Pd), the explicit inverse W, Kc, the guard residual, the scaled
+ * bounds and the control block -- is ONE launch, one workgroup per model (k_setup_models).  One upload, one launch, one
+ * download, one synchronisation per call.
+ * The engines of one call form a GROUP: they share one stream, one device arena (zero-filled once on that stream, ahead
+ * of the upload) and one pinned slab, carved into each engine's staging buffers; each engine keeps events of its own.
+ * miosqp_qp_cleanup of such an engine releases what is its own and drops one reference; the last one frees the group
+ * (its stream, arena and slab, when none is above 32 MB, wait for the next call of the process instead of being destroyed:
+ * one set at most, in a cache of their own; MIOSQP_NO_CACHE switches that off like the other caches).
+ * The engines may be cleaned up in any order and at any time.  What an engine allocates later beyond the room its slice
+ * of the arena keeps (the arrays of miosqp_qp_set_integer_rows fit) comes from a chunk of its own, as for every engine.
+ * The returned engines are ready for every entry of this header and behave as engines of miosqp_qp_setup in the
+ * LDS-resident form with the explicit inverse; the products agree with that set-up to rounding (not bit for bit: the order
+ * of the sums in the factorisation differs), the scalings, the scaled cost and bounds, f_Ad, f_Atd, f_Pd and Kc bit for bit.
+ * A model whose inverse fails the guard stays on the product form, as in miosqp_qp_setup. */
+typedef struct miosqp_setup_model {
+  int32_t n, M;                  /* variables, rows */
+  const int32_t *Pp, *Pi;        /* P, CSC, upper triangle read; row indices strictly ascending within a column */
+  const double *Px;
+  const int32_t *Ap, *Ai;        /* A, CSC; row indices strictly ascending within a column (no entry twice) */
+  const double *Ax;
+  const double *q, *l, *u;       /* n, M, M */
+  const miosqp_qp_settings *settings;
+  int32_t n_int, m_orig;         /* n_int >= 0: miosqp_qp_set_integer_rows(e, n_int, i_idx, m_orig) is applied; < 0: not */
+  const int32_t *i_idx;
+  const double *l_root, *u_root; /* non-NULL (with integer rows): miosqp_qp_set_root(e, l_root, u_root, eps_int_feas, eps_lin) */
+  double eps_int_feas, eps_lin;
+} miosqp_setup_model;
+
+typedef struct miosqp_setup_models_stats {
+  int32_t models;           /* B */
+  int32_t launches;         /* kernel launches of the dense set-up: 1 */
+  int32_t device_mallocs;   /* hipMalloc calls of the call: 1 (the arena), whatever B is; 0 when the objects of a freed */
+  int32_t host_mallocs;     /* hipHostMalloc calls: 1 (the slab)      group of this process were large enough and are */
+  int32_t streams;          /* streams created: 1                     used again (at most one set waits, <= 32 MB each) */
+  int32_t reserved;
+  int64_t arena_bytes, pinned_bytes;
+  int64_t lds_bytes;        /* dynamic LDS of the launch: the largest model's */
+  double device_time;       /* seconds between the events around upload, launch and download */
+  double run_time;          /* wall seconds of the call */
+} miosqp_setup_models_stats;
+
+/* out: B engine handles, in the order of `models` (all NULL after an error).  Refused before anything is queued, with a
+ * last_error text naming the model's position: B < 1, a NULL argument, n or M < 1, settings out of range, integer rows that
+ * do not add up, l > u, models that ask for different devices (MIOSQP_EARG); a model the launch does not take
+ * (MIOSQP_EUNSUPPORTED: see miosqp_qp_setup_models_eligible; also a P or an A with an entry twice or unsorted row indices in
+ * a column -- the launch copies entries where miosqp_qp_setup sums duplicates, so such a model goes to miosqp_qp_setup).  A pivot of the LDL^T that is not positive or not finite:
+ * MIOSQP_EFACTOR, the text names the model and the pivot.  After any error everything of the call has been released. */
+int miosqp_qp_setup_models(int32_t B, const miosqp_setup_model *models, miosqp_qp_engine **out, miosqp_setup_models_stats *stats);
+/* 1 when the launch takes a model of this shape under these settings and this environment, else 0: n + M <= 192 with the
+ * kernel's LDS within 160 KB, and everything under which miosqp_qp_setup would choose the LDS-resident form with the product
+ * form and the explicit inverse at a fixed rho -- not rho_auto, coop = 1, resident = 0, fold = 0, setup_on_device = 1,
+ * MIOSQP_COOP=1 or MIOSQP_RES_W=0. */
+int miosqp_qp_setup_models_eligible(int32_t n, int32_t M, const miosqp_qp_settings *settings);
+/* groups of miosqp_qp_setup_models that are alive in this process (engines of theirs not yet cleaned up) */
+int miosqp_qp_setup_groups_live(void);
+/* the group this engine belongs to (a positive number, the same for the engines of one call), 0 for an engine of miosqp_qp_setup */
+int64_t miosqp_qp_setup_group(miosqp_qp_engine *e);
+/* debug, beside miosqp_qp_debug_factor and with its conventions: one array of the product form as it lies in device
+ * memory.  which: 0 f_rows (n x ldf: [ -G | strict lower of Linv ])   1 f_GmT (M x ldn)   2 f_Ad (M x ldn)
+ * 3 f_Atd (n x ldm)   4 f_Pd (n x ldn); and the scaled vectors of the problem as the solvers read them: 5 q (n x 1)
+ * 6 l (M x 1)   7 u (M x 1).  MIOSQP_EUNSUPPORTED for 0..4 on an engine without the product form. */
+int miosqp_qp_debug_product_form(miosqp_qp_engine *e, int32_t which, double *out, int64_t capacity, int32_t *rows, int32_t *ld);
+
 /* ---- B trees in lock step, driven from the host in C++ on device-resident leaves -----------------------
  * miosqp_qp_solve_trees for problems of any size: the B instances of the reference's MPC pattern
  * (MIOSQP.update_vectors + set_x0 + solve per instance, /root/reference/miosqp/solver.py:174-212, each solve the loop of

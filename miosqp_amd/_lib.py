@@ -42,6 +42,18 @@ class ModelsStats(C.Structure):
                 ("lds_bytes", C.c_int64), ("device_time", C.c_double), ("run_time", C.c_double)]
 
 
+class SetupModel(C.Structure):
+    _fields_ = [("n", C.c_int32), ("M", C.c_int32), ("Pp", ip), ("Pi", ip), ("Px", dp), ("Ap", ip), ("Ai", ip), ("Ax", dp),
+                ("q", dp), ("l", dp), ("u", dp), ("settings", C.POINTER(Settings)), ("n_int", C.c_int32), ("m_orig", C.c_int32),
+                ("i_idx", ip), ("l_root", dp), ("u_root", dp), ("eps_int_feas", C.c_double), ("eps_lin", C.c_double)]
+
+
+class SetupModelsStats(C.Structure):
+    _fields_ = [("models", C.c_int32), ("launches", C.c_int32), ("device_mallocs", C.c_int32), ("host_mallocs", C.c_int32),
+                ("streams", C.c_int32), ("reserved", C.c_int32), ("arena_bytes", C.c_int64), ("pinned_bytes", C.c_int64),
+                ("lds_bytes", C.c_int64), ("device_time", C.c_double), ("run_time", C.c_double)]
+
+
 class LockstepStats(C.Structure):
     _fields_ = [("waves", C.c_int32), ("max_width", C.c_int32), ("grown", C.c_int32), ("wave_cap", C.c_int32),
                 ("nodes", C.c_int64), ("iters_slowest", C.c_int64), ("iters_all", C.c_int64), ("device_time", C.c_double),
@@ -148,6 +160,11 @@ SYMBOLS = {
     "miosqp_qp_tree_form": (C.c_int, [C.c_void_p]),
     "miosqp_qp_solve_trees_models": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), dpp, dpp, dpp, dpp, dpp, dp, dpp, ip, ip, dpp,
                                                C.POINTER(TreeInfo), C.POINTER(ModelsStats)]),
+    "miosqp_qp_setup_models": (C.c_int, [C.c_int32, C.POINTER(SetupModel), C.POINTER(C.c_void_p), C.POINTER(SetupModelsStats)]),
+    "miosqp_qp_setup_models_eligible": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(Settings)]),
+    "miosqp_qp_setup_groups_live": (C.c_int, []),
+    "miosqp_qp_setup_group": (C.c_int64, [C.c_void_p]),
+    "miosqp_qp_debug_product_form": (C.c_int, [C.c_void_p, C.c_int32, dp, C.c_int64, ip, ip]),
     "miosqp_qp_solve_trees_lockstep": (C.c_int, [C.c_void_p, C.c_int32, dp, dp, dp, dp, dp, dp, dp, C.c_int32, C.c_int32,
                                                  C.c_int32, dp, C.POINTER(TreeInfo), C.POINTER(LockstepStats)]),
     "miosqp_qp_solve_trees_lockstep_rf": (C.c_int, [C.c_void_p, C.c_int32, dp, dp, dp, dp, dp, dp, dp, C.c_int32, C.c_int32,

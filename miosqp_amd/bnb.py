@@ -465,7 +465,7 @@ class Results(object):
 class Workspace(object):
     """Tree state + the single shared relaxation solver (workspace.py:58-92)."""
 
-    def __init__(self, data, settings, qp_settings=None, backend=None):
+    def __init__(self, data, settings, qp_settings=None, backend=None, solver=None):
         self.data = data
         self.settings = settings
         exploration_setting(settings)
@@ -477,13 +477,19 @@ class Workspace(object):
         self.backend = backend if backend is not None else _default_backend()
         self.constant = self.backend.constant
         self.ok = (self.constant('OSQP_SOLVED'), self.constant('OSQP_MAX_ITER_REACHED'))  # the statuses with an x
-        self.solver = self.backend.OSQP()
         self.qp_settings = {} if qp_settings is None else qp_settings
-        # workspace.py:67-68 expands the *argument*: qp_settings=None is a TypeError there too
-        self.solver.setup(data.P, data.q, data.A, data.l, data.u, **qp_settings)
-        if hasattr(self.solver, 'set_integer_rows'):
-            self.solver.set_integer_rows(data.i_idx, data.m)
-        self.push_root()
+        if solver is not None:
+            # a solver that is already set up on this data with these qp_settings, integer rows and root included
+            # (setup_models builds many in one launch): adopted as it is
+            self.solver = solver
+            self.root_on_device = self._root_goes_to_device()
+        else:
+            self.solver = self.backend.OSQP()
+            # workspace.py:67-68 expands the *argument*: qp_settings=None is a TypeError there too
+            self.solver.setup(data.P, data.q, data.A, data.l, data.u, **qp_settings)
+            if hasattr(self.solver, 'set_integer_rows'):
+                self.solver.set_integer_rows(data.i_idx, data.m)
+            self.push_root()
         self._reset_counters()
         self.first_run = 1
         self.leaves = [self._make_root()]
@@ -493,13 +499,16 @@ class Workspace(object):
         self.solve_time = 0.
         self.run_time = 0.
 
+    def _root_goes_to_device(self):
+        return bool(hasattr(self.solver, 'set_root') and self.settings.get('device_digest', True)
+                    and 'eps_abs' in self.qp_settings and self.data.n_int > 0)
+
     def push_root(self):
         """Hands the root bounds and the two tolerances to the engine so that the x-only part of
         bound_and_branch (integrality test, branching variable, rounding heuristic) is evaluated on
         the device at the end of each node (settings['device_digest'] = False keeps it on the host)."""
         self.root_on_device = False
-        if hasattr(self.solver, 'set_root') and self.settings.get('device_digest', True) \
-                and 'eps_abs' in self.qp_settings and self.data.n_int > 0:
+        if self._root_goes_to_device():
             self.root_on_device = True
             self.solver.set_root(self.data.l, self.data.u, self.settings['eps_int_feas'],
                                  self.qp_settings['eps_abs'])
@@ -1565,4 +1574,130 @@ def solve_models(models, instances=None, info=None):
     if info is not None:
         info.update(launched=list(launched), own=dict(own), forms=forms, launches=launches, device_time=device_time,
                     overflow=list(overflow))
+    return out
+
+
+def _setup_models_own_reason(be, data, qp_settings):
+    """why `setup_models` leaves a model to `MIOSQP.setup` (None: it goes into the launch)"""
+    if not hasattr(be, 'setup_models') or not hasattr(be, 'setup_models_eligible'):
+        return 'backend without the one-launch set-up'
+    if data.n_int == 0:
+        return 'n_int == 0'
+    if isinstance(qp_settings.get('rho'), str):
+        return 'rho="auto"'
+    n, M = data.n, data.A.shape[0]
+    if not be.setup_models_eligible(n, M, {}):  # (the library's size rule, asked with default settings)
+        return 'n + M = %d: beyond one workgroup of the launch' % (n + M)
+    if not data.P.has_canonical_format or not spa.csc_matrix(data.A).has_canonical_format:
+        return 'duplicate entries in P or A'
+    if not be.setup_models_eligible(n, M, qp_settings):
+        return 'settings or environment that lead to another engine form'
+    return None
+
+
+def setup_models(problems, settings, qp_settings, info=None, backend=None):
+    """Set up several DIFFERENT MIQP models -- each with its own P and A -- with ONE launch for the dense set-up of all of
+    them (`qp.setup_models`, miosqp_qp_setup_models: one workgroup per model builds the Schur complement, its LDL^T, the
+    triangular inverse, the product form, the explicit inverse and its guard; the engines share one stream, one device
+    arena and one pinned slab).  It replaces the loop `MIOSQP().setup(...)` over the list: the reference draws a new P and
+    A for every MIQP of its benchmark, and that loop is where such a run spends its time.
+
+    problems: a list of dicts with the keys `problems.random_miqp` returns (P, q, A, l, u, i_idx, i_l, i_u).  settings,
+    qp_settings: one dict for all models (every model gets its own copy of `settings`), or a list with one per model.
+    Returns set-up MIOSQP objects in the order given, ready for `solve_models` and every other method.
+
+    A model goes into the launch when it fits one workgroup (the library's rule: n + M <= 192), rho is a number, it has an integer variable and the settings lead to
+    the engine form the launch builds (LDS-resident, product form, explicit inverse); every other model (the CPU oracle
+    backend among them) is set up in its place by `MIOSQP.setup`.
+
+    ValueError before anything is queued, with the positions named: an empty list, a wrong number of settings, l > u, a P
+    of the wrong shape.  A pivot that is not positive raises what `MIOSQP.setup` raises, with the position added; nothing
+    of the call is left behind.
+
+    info: a dict that is filled with batched (positions), own ({position: why}), launches, device_time, arena_bytes and
+    host_time (seconds of the call outside the library's one)."""
+    t_call = time()
+    problems = list(problems)
+    B = len(problems)
+    if B == 0:
+        raise ValueError('setup_models: an empty list of problems')
+
+    def per_model(v, name, copy):
+        if isinstance(v, dict):
+            return [dict(v) if copy else v for _ in range(B)]
+        v = list(v)
+        if len(v) != B:
+            raise ValueError('setup_models: %d %s for %d problems (one dict, or one per problem)' % (len(v), name, B))
+        return v
+
+    settings = per_model(settings, 'settings', True)
+    qp_settings = per_model(qp_settings, 'qp_settings', False)
+    bad_shape, crossed = [], []
+    datas = []
+    for k, pr in enumerate(problems):
+        A, P = spa.csc_matrix(pr['A']), spa.csc_matrix(pr['P'])
+        n = A.shape[1]
+        i_idx = pr['i_idx']
+        i_l = -np.inf * np.ones(len(i_idx)) if pr.get('i_l') is None else pr['i_l']
+        i_u = np.inf * np.ones(len(i_idx)) if pr.get('i_u') is None else pr['i_u']
+        if P.shape != (n, n):
+            bad_shape.append(k)
+            datas.append(None)
+            continue
+        if np.any(np.asarray(pr['l']) > np.asarray(pr['u'])) or np.any(np.asarray(i_l) > np.asarray(i_u)):
+            crossed.append(k)
+        datas.append(Data(P, pr['q'], A, pr['l'], pr['u'], i_idx, i_l, i_u))
+    if bad_shape:
+        raise ValueError('setup_models: P must be n x n with n the columns of A, at position(s) %s' % bad_shape)
+    if crossed:
+        raise ValueError('setup_models: Lower bound must be lower than or equal to upper bound, at position(s) %s' % crossed)
+    be = backend if backend is not None else _default_backend()
+    own, batched = {}, []
+    for k in range(B):
+        why = _setup_models_own_reason(be, datas[k], qp_settings[k])
+        if why is None:
+            batched.append(k)
+        else:
+            own[k] = why
+    out = [None] * B
+    solvers = []
+    launches, device_time, arena_bytes, lib_time = 0, 0.0, 0, 0.0
+    try:
+        if batched:
+            desc = []
+            for k in batched:
+                d, st, qs = datas[k], settings[k], qp_settings[k]
+                md = dict(P=d.P, q=d.q, A=d.A, l=d.l, u=d.u, settings=qs, i_idx=d.i_idx, m_orig=d.m)
+                if st.get('device_digest', True) and 'eps_abs' in qs:
+                    md['root'] = (d.l, d.u, st['eps_int_feas'], qs['eps_abs'])
+                desc.append(md)
+            t0 = time()
+            try:
+                solvers, stats = be.setup_models(desc)
+            except RuntimeError as ex:
+                import re
+                hit = re.search(r'\(model (\d+)', str(ex))
+                if hit:
+                    raise RuntimeError('%s [setup_models: position %d]' % (ex, batched[int(hit.group(1))]))
+                raise
+            lib_time = time() - t0
+            launches, device_time, arena_bytes = int(stats.launches), float(stats.device_time), int(stats.arena_bytes)
+            for j, k in enumerate(batched):
+                t1 = time()
+                out[k] = MIOSQP(backend=backend)
+                out[k].work = Workspace(datas[k], settings[k], qp_settings[k], backend=backend, solver=solvers[j])
+                out[k].work.setup_time = lib_time / len(batched) + (time() - t1)
+        for k in sorted(own):
+            pr, d = problems[k], datas[k]
+            mdl = MIOSQP(backend=backend)
+            mdl.setup(d.P, pr['q'], spa.csc_matrix(pr['A']), pr['l'], pr['u'], d.i_idx, d.i_l, d.i_u, settings[k], qp_settings[k])
+            out[k] = mdl
+    except Exception:
+        for s in solvers + [out[k].work.solver for k in own if out[k] is not None]:  # nothing of the call is left behind
+            if hasattr(s, 'close'):
+                s.close()
+        raise
+    if info is not None:
+        info.update(batched=list(batched), own=dict(own), launches=launches, device_time=device_time, arena_bytes=arena_bytes,
+                    host_time=(time() - t_call) - lib_time)
     return out

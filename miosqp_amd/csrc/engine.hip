@@ -42,6 +42,7 @@
 #include "lockstep_trees.hpp"  // the tree logic of B trees in lock step (plain C++; host_lockstep.inc drives it)
 #include "lockstep_ahead.hpp"  // ahead records, shadow leaves and the choice of ahead columns (plain C++; host_lockstep_ahead.inc drives it)
 #include "lockstep_sb.hpp"  // strong and reliability branching in the lock-step trees (plain C++; host_lockstep_sb.inc drives it)
+#include "setup_plan.hpp"  // set-up of many models in one launch: argument checks, eligibility, arena layout (plain C++; host_setup_models.inc drives it); with guard_probe.hpp and setup_models_body.hpp, the kernel's arithmetic
 #include "models_plan.hpp"  // trees of different models in one launch: argument checks and arena layout (plain C++; host_models.inc drives it)
 #include "lockstep_refill.hpp"  // which tree goes into which free column when the columns are refilled between chunks (plain C++; host_refill.inc drives it)
 
@@ -256,6 +257,8 @@ struct CoopNode {
 #include "host_lockstep_ahead.inc"  // the lock-step trees with spare columns solving open leaves early (C ABI miosqp_qp_solve_trees_lockstep_ahead); its two kernels
 #include "kernels_lockstep_sb.inc"  // strong and reliability branching in the lock-step trees: x at the integer positions, the children's gather, judge and bounds
 #include "host_lockstep_sb.inc"  // ... and its driver (C ABI miosqp_qp_solve_trees_lockstep_sb)
+#include "kernels_setup_models.inc"  // the dense set-up of many small models in one launch (k_setup_models)
+#include "host_setup_models.inc"  // ... and its host side: the group, the arena, the engines (C ABI miosqp_qp_setup_models)
 #include "host_models.inc"  // what the one-launch tree entries share; trees of different models in one launch (C ABI miosqp_qp_tree_form, miosqp_qp_solve_trees_models)
 
 // ------------------------------------------------------------------------------------------
@@ -265,7 +268,7 @@ namespace {
 // the dynamic-LDS ceiling of a kernel is a property of (process, device, kernel): raised to the chip's 160 KB once instead of
 // at every set-up (the call costs ~40 us, a fifth of a small problem's set-up)
 hipError_t lds_limit_once(const void *fn, int which) {
-  static bool done[14][64] = {};
+  static bool done[15][64] = {};  // (one row per kernel: 0 .. 13 as before, 14: k_setup_models)
   int dev = 0;
   hipError_t rc = hipGetDevice(&dev);
   if (rc != hipSuccess) return rc;
@@ -671,7 +674,8 @@ int miosqp_qp_cleanup(miosqp_qp_engine *e) {
   polish_many_free(e->polm);
   polish_many_free(e->polml);
   drop_chunk_graphs(e);
-  rt_release(e->rt);  // stream, events and pinned staging go back to the per-process cache
+  if (e->group) group_engine_release(e);  // (miosqp_qp_setup_models: its own events go, one reference to the group is dropped)
+  else rt_release(e->rt);  // stream, events and pinned staging go back to the per-process cache
   delete e;
   return 0;
 }
@@ -1080,14 +1084,7 @@ int miosqp_qp_setup(miosqp_qp_engine **out, int32_t n, int32_t M, const int32_t 
           }
           if (e->resident) {
             HIPCHK(lds_limit_once((const void *)k_resident, 0));
-            // lanes per row: as many as keep every row of a sweep in flight at once
-            auto pow2_floor = [](int v) { int p = 1; while (2 * p <= v) p *= 2; return p; };
-            e->res_tg1 = std::min(64, std::max(1, pow2_floor(RES_THREADS / n)));
-            e->res_tg2 = std::min(64, std::max(1, pow2_floor(RES_THREADS / (n + M))));
-            if (const char *ev = getenv("MIOSQP_RES_TG")) {
-              int a1 = 0, b1 = 0;
-              if (sscanf(ev, "%d,%d", &a1, &b1) == 2) { e->res_tg1 = a1; e->res_tg2 = b1; }
-            }
+            resident_lane_groups(e);
           }
         }
       }
@@ -1164,19 +1161,7 @@ int miosqp_qp_setup(miosqp_qp_engine **out, int32_t n, int32_t M, const int32_t 
           }
         }
       }
-      if (const char *ev = getenv("MIOSQP_BD_CFG")) e->bd_cfg = atoi(ev);
-      if (const char *ev = getenv("MIOSQP_BM_VAR")) e->bm_var = atoi(ev);
-      if (const char *ev = getenv("MIOSQP_SPIN_WAIT")) e->spin_wait = atoi(ev) != 0;
-      if (const char *ev = getenv("MIOSQP_COMPACT")) e->compact = atoi(ev) != 0;
-      if (const char *ev = getenv("MIOSQP_BM_ABLATE")) d.bm_ablate = atoi(ev);
-      if (const char *ev = getenv("MIOSQP_FOLD_TPR")) {  // tuning hook: "fwd,x,c"
-        int a = 0, b = 0, c = 0;
-        if (sscanf(ev, "%d,%d,%d", &a, &b, &c) == 3) {
-          e->tpr_ff = a;
-          e->tpr_fx = b;
-          e->tpr_fc = c;
-        }
-      }
+      tuning_from_env(e);
       std::vector<double>().swap(e->fo.rows);
       std::vector<double>().swap(e->fo.GmT);
       std::vector<double>().swap(e->fo.Ad);
@@ -2256,6 +2241,60 @@ int miosqp_qp_debug_iterate(miosqp_qp_engine *e, int32_t k, double *x, double *z
   if (x) HIPCHK(hipMemcpy(x, e->d.x, sizeof(double) * e->n, hipMemcpyDeviceToHost));
   if (z) HIPCHK(hipMemcpy(z, e->d.z, sizeof(double) * e->M, hipMemcpyDeviceToHost));
   if (y) HIPCHK(hipMemcpy(y, e->d.y, sizeof(double) * e->M, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int miosqp_qp_setup_models(int32_t B, const miosqp_setup_model *models, miosqp_qp_engine **out, miosqp_setup_models_stats *stats) {
+  return setup_models_run(B, models, out, stats);
+}
+
+int miosqp_qp_setup_models_eligible(int32_t n, int32_t M, const miosqp_qp_settings *s) {
+  if (!s) return 0;
+  miosqp::setup_models::Args a;
+  a.rho_auto = s->rho_auto; a.coop = s->coop; a.resident = s->resident; a.fold = s->fold; a.setup_on_device = s->setup_on_device;
+  return miosqp::setup_models::eligible_shape(n, M) && miosqp::setup_models::eligible_settings(a) && setup_models_env_ok() ? 1 : 0;
+}
+
+int miosqp_qp_setup_groups_live(void) {
+  std::lock_guard<std::mutex> lk(g_group_mutex);
+  return g_groups_live;
+}
+
+int64_t miosqp_qp_setup_group(miosqp_qp_engine *e) { return e && e->group ? e->group->id : 0; }
+
+// debug: one array of the product form copied to the host as it lies in device memory (beside miosqp_qp_debug_factor)
+int miosqp_qp_debug_product_form(miosqp_qp_engine *e, int32_t which, double *out, int64_t capacity, int32_t *rows, int32_t *ld) {
+  if (!e || !rows || !ld || which < 0 || which > 7) {
+    g_err = "debug_product_form: bad argument";
+    return MIOSQP_EARG;
+  }
+  ENTER(e);
+  const Dev &d = e->d;
+  const double *src = nullptr;
+  int r = 0, l = 0;
+  switch (which) {
+    case 0: src = d.f_rows; r = e->n; l = d.ldf; break;
+    case 1: src = d.f_GmT; r = e->M; l = d.ldn; break;
+    case 2: src = d.f_Ad; r = e->M; l = d.ldn; break;
+    case 3: src = d.f_Atd; r = e->n; l = d.ldm; break;
+    case 4: src = d.f_Pd; r = e->n; l = d.ldn; break;
+    case 5: src = d.q; r = e->n; l = 1; break;  // (vectors: rows of one value)
+    case 6: src = d.l; r = e->M; l = 1; break;
+    default: src = d.u; r = e->M; l = 1; break;
+  }
+  if ((which < 5 && !e->fold) || !src || l <= 0) {
+    g_err = "debug_product_form: this engine did not build the product form";
+    return MIOSQP_EUNSUPPORTED;
+  }
+  *rows = r;
+  *ld = l;
+  if (!out) return 0;
+  if (capacity < (int64_t)r * l) {
+    g_err = "debug_product_form: the output holds fewer than rows * ld values";
+    return MIOSQP_EARG;
+  }
+  HIPCHK(hipStreamSynchronize(e->stream));
+  HIPCHK(hipMemcpy(out, src, sizeof(double) * (size_t)r * l, hipMemcpyDeviceToHost));
   return 0;
 }
 

@@ -321,25 +321,14 @@ bool scale_problem(int n, int M, const int32_t *Pp, const int32_t *Pi, const dou
   return true;
 }
 
-bool build_factor(const Scaled &s, const int32_t *Pp_raw, const int32_t *Pi_raw,
-                  const double *Px_raw, double rho, double sigma, Factor &f, std::string &err,
-                  DenseLdlInv accel, void *accel_ctx, bool reuse_rows) {
+// The packed rows of a factor: the panel by variable and by constraint (with the plain values beside them) and the two
+// symmetric matrices by row.  Everything of build_factor that does not depend on the dense part; the set-up of many
+// models in one launch (host_setup_models.inc) packs the rows here and leaves the dense part to the device.
+static void pack_rows_of(const Scaled &s, const int32_t *Pp_raw, const int32_t *Pi_raw, const double *Px_raw, double rho,
+                         Factor &f, StageTimer *tm) {
   const int n = s.n, M = s.M;
-  StageTimer tm;
-  f.n = n;
-  f.M = M;
-  f.rho = rho;
-  f.sigma = sigma;
-  f.ld = (n + 15) & ~15;  // multiples of 16: the batched matrix-core tiles read whole 16-deep chunks of a row
-  const int ld = f.ld;
-
-  if (reuse_rows) {
-    // (a padding entry is 0.0 in a fresh build, not -rho * 0.0 = -0.0)
-    for (size_t k = 0; k < f.At_val.size(); k++) f.panel_by_var.val[k] = f.At_val[k] == 0.0 ? 0.0 : -rho * f.At_val[k];
-    for (size_t k = 0; k < f.A_val.size(); k++) f.panel_by_con.val[k] = f.A_val[k] == 0.0 ? 0.0 : -rho * f.A_val[k];
-  }
   // ---- panel: rows of Abar^T (per variable) and rows of Abar (per constraint) ----------
-  if (!reuse_rows) {
+  {
     std::vector<std::vector<Triplet>> byvar(n), bycon(M);
     for (int i = 0; i < n; i++) byvar[i].reserve(s.Ap[i + 1] - s.Ap[i]);
     for (int i = 0; i < n; i++)
@@ -353,9 +342,9 @@ bool build_factor(const Scaled &s, const int32_t *Pp_raw, const int32_t *Pi_raw,
     pack_rows(M, n, bycon, f.panel_by_con, &f.A_val);
     f.nnz_panel = f.panel_by_var.nnz;
   }
-  tm.lap("panel rows");
+  if (tm) tm->lap("panel rows");
   // ---- symmetric matrices by row (counting transpose of the upper triangle; columns ascend) ----
-  if (!reuse_rows) {
+  {
     // Row r of the full symmetric matrix = [column r of the upper triangle: entries (i, r), i <= r, as columns i]
     // followed by [row r of the strict upper triangle: entries (r, j), j > r] -- both ascending, so the row comes out
     // sorted.  The first part is copied per row; the second is a transpose of the strict upper triangle done in
@@ -425,6 +414,32 @@ bool build_factor(const Scaled &s, const int32_t *Pp_raw, const int32_t *Pi_raw,
     sym_rows(s.Pp.data(), s.Pi.data(), s.Px.data(), true, f.Pbar);
     sym_rows(Pp_raw, Pi_raw, Px_raw, false, f.Praw);
   }
+}
+
+void pack_factor_rows(const Scaled &s, const int32_t *Pp_raw, const int32_t *Pi_raw, const double *Px_raw, double rho,
+                      Factor &f) {
+  pack_rows_of(s, Pp_raw, Pi_raw, Px_raw, rho, f, nullptr);
+}
+
+bool build_factor(const Scaled &s, const int32_t *Pp_raw, const int32_t *Pi_raw,
+                  const double *Px_raw, double rho, double sigma, Factor &f, std::string &err,
+                  DenseLdlInv accel, void *accel_ctx, bool reuse_rows) {
+  const int n = s.n, M = s.M;
+  StageTimer tm;
+  f.n = n;
+  f.M = M;
+  f.rho = rho;
+  f.sigma = sigma;
+  f.ld = (n + 15) & ~15;  // multiples of 16: the batched matrix-core tiles read whole 16-deep chunks of a row
+  const int ld = f.ld;
+
+  if (reuse_rows) {
+    // (a padding entry is 0.0 in a fresh build, not -rho * 0.0 = -0.0)
+    for (size_t k = 0; k < f.At_val.size(); k++) f.panel_by_var.val[k] = f.At_val[k] == 0.0 ? 0.0 : -rho * f.At_val[k];
+    for (size_t k = 0; k < f.A_val.size(); k++) f.panel_by_con.val[k] = f.A_val[k] == 0.0 ? 0.0 : -rho * f.A_val[k];
+  }
+  if (!reuse_rows) pack_rows_of(s, Pp_raw, Pi_raw, Px_raw, rho, f, &tm);
+  else tm.lap("panel rows");
   tm.lap("P rows");
   // ---- Schur complement S = Pbar + sigma I + rho Abar^T Abar (dense, lower, row-major) -----
   DenseAccelCtx *actx_s = static_cast<DenseAccelCtx *>(accel_ctx);

@@ -140,4 +140,9 @@ bool build_factor(const Scaled &s, const int32_t *Pp_raw, const int32_t *Pi_raw,
                   const double *Px_raw, double rho, double sigma, Factor &f, std::string &err,
                   DenseLdlInv accel = nullptr, void *accel_ctx = nullptr, bool reuse_rows = false);
 
+// The part of build_factor that does not depend on the dense tail: the packed rows of the panel (with rho in the values of
+// L21, the plain values beside them) and the two symmetric matrices by row.  `f` keeps whatever else it holds.
+void pack_factor_rows(const Scaled &s, const int32_t *Pp_raw, const int32_t *Pi_raw, const double *Px_raw, double rho,
+                      Factor &f);
+
 }  // namespace miosqp

@@ -35,6 +35,8 @@ struct ParkedChunk {
   size_t bytes;
 };
 
+struct SetupGroup;  // host_setup_models.inc: what the engines of one miosqp_qp_setup_models call share
+
 struct RtBundle {
   int device = -1;
   hipStream_t stream = nullptr;
@@ -58,6 +60,7 @@ struct miosqp_qp_engine {
   Dev d{};
   Dev dh{};  // leaf pool: the 64-column harvest tile (same matrices, its own b_* / c_* arrays)
   RtBundle rt;  // stream, events, pinned staging: from / back to the per-process cache
+  SetupGroup *group = nullptr;  // set by miosqp_qp_setup_models: rt's stream and pinned buffers and the first pool chunk are the group's
   TreeArgs ta{};  // whole-tree launch: leaf arrays, incumbent, result record
   bool tree_ready = false;
   // miosqp_qp_solve_trees: per-instance arrays of a batch of trees (capacity tb_cap instances)
@@ -309,6 +312,8 @@ struct ChipGuard {
 // same device takes a bundle whose buffers are large enough.
 std::vector<RtBundle> g_rt_cache;
 std::mutex g_rt_mutex;
+// runtime objects this host thread has created so far (miosqp_qp_setup_models reports what one call added)
+thread_local int64_t g_made_device_mallocs = 0, g_made_host_mallocs = 0, g_made_streams = 0;
 
 void rt_destroy(RtBundle &b) {
   if (b.h_in) hipHostFree(b.h_in);
@@ -339,6 +344,8 @@ int rt_acquire(int device, size_t in_need, size_t out_need, RtBundle &b) {
   b.in_cap = std::max<size_t>(4096, in_need + in_need / 2);
   b.out_cap = std::max<size_t>(4096, out_need + out_need / 2);
   HIPCHK(hipStreamCreateWithFlags(&b.stream, hipStreamNonBlocking));
+  g_made_streams++;
+  g_made_host_mallocs += 4;
   HIPCHK(hipEventCreate(&b.ev0));
   HIPCHK(hipEventCreate(&b.ev1));
   HIPCHK(hipEventCreate(&b.evc0));
@@ -388,7 +395,10 @@ int pool_reserve(miosqp_qp_engine *e, size_t bytes) {
       }
   }
   const bool parked = p != nullptr;  // a parked chunk was zero-filled (and waited for) when its engine was cleaned up
-  if (!p) HIPCHK(hipMalloc(&p, bytes));
+  if (!p) {
+    HIPCHK(hipMalloc(&p, bytes));
+    g_made_device_mallocs++;
+  }
   // The zero fill must be ORDERED before the first kernel that touches the chunk.  The engine's stream is
   // non-blocking (it does not synchronise with the null stream) and hipMemset on device memory returns
   // before the fill has finished: a null-stream fill of a large chunk (312 MB for 1024 columns at config 2)
@@ -617,6 +627,34 @@ int inverse_guard(miosqp_qp_engine *e) {
     fprintf(stderr, "miosqp: explicit KKT inverse residual %.3g above %.3g (ill-conditioned KKT matrix): this engine iterates with "
                     "the factor's sweeps instead\n", r, tol);
   return 0;
+}
+
+// lanes per row of the LDS-resident solver's two sweeps: as many as keep every row of a sweep in flight at once
+void resident_lane_groups(miosqp_qp_engine *e) {
+  auto pow2_floor = [](int v) { int p = 1; while (2 * p <= v) p *= 2; return p; };
+  e->res_tg1 = std::min(64, std::max(1, pow2_floor(RES_THREADS / e->n)));
+  e->res_tg2 = std::min(64, std::max(1, pow2_floor(RES_THREADS / (e->n + e->M))));
+  if (const char *ev = getenv("MIOSQP_RES_TG")) {
+    int a1 = 0, b1 = 0;
+    if (sscanf(ev, "%d,%d", &a1, &b1) == 2) { e->res_tg1 = a1; e->res_tg2 = b1; }
+  }
+}
+
+// the tuning hooks of the environment an engine with the product form reads at set-up
+void tuning_from_env(miosqp_qp_engine *e) {
+  if (const char *ev = getenv("MIOSQP_BD_CFG")) e->bd_cfg = atoi(ev);
+  if (const char *ev = getenv("MIOSQP_BM_VAR")) e->bm_var = atoi(ev);
+  if (const char *ev = getenv("MIOSQP_SPIN_WAIT")) e->spin_wait = atoi(ev) != 0;
+  if (const char *ev = getenv("MIOSQP_COMPACT")) e->compact = atoi(ev) != 0;
+  if (const char *ev = getenv("MIOSQP_BM_ABLATE")) e->d.bm_ablate = atoi(ev);
+  if (const char *ev = getenv("MIOSQP_FOLD_TPR")) {  // tuning hook: "fwd,x,c"
+    int a = 0, b = 0, c = 0;
+    if (sscanf(ev, "%d,%d,%d", &a, &b, &c) == 3) {
+      e->tpr_ff = a;
+      e->tpr_fx = b;
+      e->tpr_fc = c;
+    }
+  }
 }
 
 // the registration words of the single-launch solvers start from zero again (after a launch that was called off)

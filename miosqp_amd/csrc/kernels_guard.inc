@@ -15,11 +15,8 @@
 constexpr int GUARD_NP = 3;
 constexpr double COOP_GUARD_TOL = 1e-9;
 
-__device__ __forceinline__ double guard_probe(int p, int c) {
-  unsigned h = (unsigned)(c + 1) * 2654435761u ^ (unsigned)(p + 1) * 0x9E3779B9u;
-  h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;
-  return (double)(int)(h & 0xFFFFFu) / 524288.0 - 1.0;
-}
+// (the entries themselves: guard_probe.hpp, shared with the one-launch set-up of many models)
+__device__ __forceinline__ double guard_probe(int p, int c) { return miosqp::guard_probe_value(p, c); }
 
 // u[p][row] for every row of W: one wavefront per row, lanes stride the row, fixed-order butterfly
 __global__ __launch_bounds__(256) void kg_apply(const double *__restrict__ W, int ldw, int N, int M, double rho,

@@ -1,0 +1,35 @@
+// part of engine.hip (included there, not compiled alone): the dense set-up of many small models in ONE launch
+// ------------------------------------------------------------------------------------------
+// k_setup_models: workgroup b reads entry b of a table in device memory and builds, for that model, what
+// miosqp_qp_setup builds one model at a time on a host core and with five launches: S, its LDL^T, Linv / LinvT / d2inv,
+// the product form, the explicit inverse W, Kc, the guard residual, the scaled bounds and the control block.  The
+// arithmetic is setup_models_body.hpp (phases between barriers; the same source runs on the CPU under tests/).
+// ------------------------------------------------------------------------------------------
+struct SetupModel {
+  miosqp::setup_models::IO io;  // final pointers into the call's arena
+  Ctrl *ctrl;
+};
+
+struct SetupExecDevice {
+  template <class F>
+  __device__ __forceinline__ void par(F f) {
+    f((int)threadIdx.x);
+    __syncthreads();
+  }
+};
+
+__global__ __launch_bounds__(miosqp::setup_models::THREADS) void k_setup_models(const SetupModel *__restrict__ tab) {
+  extern __shared__ double sm_lds[];
+  const SetupModel &m = tab[blockIdx.x];
+  if (threadIdx.x == 0) {  // k_reset_ctrl
+    Ctrl *c = m.ctrl;
+    c->done = 0;
+    c->pad = 0;
+    c->status = MIOSQP_QP_UNSOLVED;
+    c->iter = 0;
+    c->pri_res = c->dua_res = c->obj_val = 0.0;
+    c->lower = __builtin_nan("");
+  }
+  SetupExecDevice x;
+  miosqp::setup_models::body(m.io, sm_lds, x);
+}

@@ -1,0 +1,219 @@
+// Set-up of many small models in one launch (miosqp_qp_setup_models): the host logic that needs neither an engine nor the
+// device -- the argument checks that refuse a call before anything is queued, which model the launch takes, and where
+// every array of every model lies in the call's device arena and its pinned slab.
+// Plain C++ (no HIP): engine.hip includes it, and so does the stand-alone sanitized program under tests/.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "setup_models_body.hpp"  // eligible_shape, lds_doubles, Record (plain C++ too)
+
+namespace miosqp {
+namespace setup_models {
+
+constexpr int ERR_ARG = -1;          // MIOSQP_EARG
+constexpr int ERR_UNSUPPORTED = -5;  // MIOSQP_EUNSUPPORTED
+constexpr size_t ALIGN = 256;        // every array starts on a multiple of this (what the engine's pool hands out)
+constexpr size_t SLACK = 64;         // elements behind an array that tile loads may touch (dupload keeps the same)
+constexpr size_t CTRL_BYTES = 128;   // room of one control block (engine.hip: Ctrl is 120 bytes)
+
+// one model as the entry point receives it (pointers are only tested against NULL here, l and u are read)
+struct Args {
+  int n = 0, M = 0;
+  const void *Pp = nullptr, *Pi = nullptr, *Px = nullptr, *Ap = nullptr, *Ai = nullptr, *Ax = nullptr, *q = nullptr;
+  const double *l = nullptr, *u = nullptr;
+  const void *settings = nullptr;
+  double rho = 0, sigma = 0, alpha = 0;
+  int max_iter = 0, rho_auto = 0, coop = -1, resident = -1, fold = -1, setup_on_device = -1;
+  int n_int = -1, m_orig = 0;  // n_int < 0: no integer rows in the descriptor
+  const void *i_idx = nullptr;
+  const double *l_root = nullptr, *u_root = nullptr;
+};
+
+// settings under which miosqp_qp_setup would choose resident + fold + W at a fixed rho for an eligible shape
+inline bool eligible_settings(const Args &a) {
+  return a.rho_auto == 0 && a.coop != 1 && a.resident != 0 && a.fold != 0 && a.setup_on_device != 1;
+}
+
+// The launch writes the dense copies of Abar and Pbar entry by entry where the per-model set-up sums what a matrix stores
+// twice: a column whose row indices do not ascend strictly (an entry twice, or unsorted) keeps its model out of the launch.
+inline bool csc_strictly_ascending(int cols, const int32_t *ptr, const int32_t *idx) {
+  for (int j = 0; j < cols; j++)
+    for (int32_t p = ptr[j] + 1; p < ptr[j + 1]; p++)
+      if (idx[p] <= idx[p - 1]) return false;
+  return true;
+}
+
+// 0, or the error code with `err` naming the model's position
+inline int check_args(int32_t B, const Args *a, const void *out, const void *stats, std::string &err) {
+  const std::string who = "setup_models: ";
+  if (B < 1) {
+    err = who + "B must be at least 1";
+    return ERR_ARG;
+  }
+  if (!a || !out || !stats) {
+    err = who + "a NULL argument";
+    return ERR_ARG;
+  }
+  for (int b = 0; b < B; b++) {
+    const Args &m = a[b];
+    const std::string at = " (model " + std::to_string(b) + ")";
+    if (m.n <= 0 || m.M <= 0) {
+      err = who + "n and M must be at least 1" + at;
+      return ERR_ARG;
+    }
+    if (!m.Pp || !m.Ap || !m.q || !m.l || !m.u || !m.settings) {
+      err = who + "a NULL pointer" + at;
+      return ERR_ARG;
+    }
+    if (!(m.rho > 0) || !(m.sigma > 0) || !(m.alpha > 0 && m.alpha < 2) || m.max_iter <= 0) {
+      err = who + "settings out of range" + at;
+      return ERR_ARG;
+    }
+    if (m.n_int >= 0 && (m.n_int > m.n || m.m_orig < 0 || m.m_orig + m.n_int != m.M || (m.n_int > 0 && !m.i_idx))) {
+      err = who + "integer rows: need m_orig + n_int == M" + at;
+      return ERR_ARG;
+    }
+    if ((m.l_root || m.u_root) && (!m.l_root || !m.u_root || m.n_int < 0)) {
+      err = who + "a root needs both bounds and the integer rows" + at;
+      return ERR_ARG;
+    }
+    for (int i = 0; i < m.M; i++)
+      if (m.l[i] > m.u[i]) {
+        err = who + "lower bound above upper bound" + at;
+        return ERR_ARG;
+      }
+    if (!eligible_shape(m.n, m.M) || !eligible_settings(m)) {
+      err = who + "the launch does not take this model: n + M <= " + std::to_string(MAX_NM) +
+            ", a fixed rho, and settings that lead to the LDS-resident form with the explicit inverse" + at;
+      return ERR_UNSUPPORTED;
+    }
+  }
+  return 0;
+}
+
+struct Shape {
+  int n = 0, M = 0;
+  size_t nv = 0, nc = 0, npb = 0, npr = 0;  // lengths of the packed rows as stored (padding included): by variable, by
+                                            // constraint, Pbar, Praw
+};
+
+// the arrays of one model, in the order they lie in the arena
+enum Part {
+  // uploaded
+  PV_PTR, PV_IDX, PV_L, PV_AT, PC_PTR, PC_IDX, PC_L, PC_A, PB_PTR, PB_IDX, PB_VAL, PR_PTR, PR_IDX, PR_VAL, D_, DINV, E_, EINV,
+  Q, QRAW, RAW,  // RAW: raw_l | raw_u | raw_x | raw_y
+  // products of the launch
+  LINV, LINVT, D2INV, F_ROWS, F_GMT, F_AD, F_ATD, F_PD, W_, KC,
+  // iterates and staging
+  L_, U_, X_, Z_, Y_, WH, CV, UT, XT, DX, DY, SM, SN, XI, XIS, ROOT_L, ROOT_U, CTRL, OUT, I_IDX,
+  // left to the engine's pool: int_pos, f_rows2 and a_int of miosqp_qp_set_integer_rows, the guard's scratch, slack
+  RESERVE,
+  NPARTS
+};
+constexpr int FIRST_PRODUCT = LINV, FIRST_ITERATE = L_;
+
+struct Span {
+  size_t off = 0, bytes = 0;  // from the arena's base
+};
+
+struct Slot {
+  Span part[NPARTS];
+  size_t rec = 0;  // this model's Record
+  // the pinned slab: h_in (in_cap doubles), h_out (out_cap doubles), h_ctrl, h_ctrl2 (two control blocks)
+  size_t pin_in = 0, pin_out = 0, pin_ctrl = 0, pin_ctrl2 = 0, in_cap = 0, out_cap = 0;
+};
+
+// [ table | uploaded arrays of every model | products, iterates, reserve of every model | records ]: the first two parts
+// go up in ONE copy out of the pinned slab (which holds their image at the same offsets), the records come back in ONE.
+struct Plan {
+  std::vector<Slot> slot;
+  size_t table_bytes = 0;
+  size_t up_bytes = 0;             // [0, up_bytes) is staged and uploaded
+  size_t rec_off = 0, rec_bytes = 0;
+  size_t total_bytes = 0;          // the arena
+  size_t pin_bytes = 0;            // the slab: max(upload image, the engines' staging) + records
+  size_t pin_rec = 0;              // where the records land in the slab
+  size_t lds_bytes = 0;            // dynamic LDS of the launch: the largest model's
+};
+
+inline size_t round_up(size_t v, size_t to) { return (v + to - 1) / to * to; }
+inline size_t arr(size_t count, size_t elem) { return round_up((count + SLACK) * elem, ALIGN); }
+
+// bytes of every part of one model
+inline void part_bytes(const Shape &s, size_t (&by)[NPARTS]) {
+  const size_t n = (size_t)s.n, M = (size_t)s.M, N = n + M;
+  const size_t ld = (n + 15) & ~(size_t)15, ldf = (N + 15) & ~(size_t)15, ldn = ld, ldm = (M + 15) & ~(size_t)15,
+               ldw = (N + 7) & ~(size_t)7;
+  const size_t I = sizeof(int32_t), F = sizeof(double);
+  by[PV_PTR] = arr(n + 1, I); by[PV_IDX] = arr(s.nv, I); by[PV_L] = arr(s.nv, F); by[PV_AT] = arr(s.nv, F);
+  by[PC_PTR] = arr(M + 1, I); by[PC_IDX] = arr(s.nc, I); by[PC_L] = arr(s.nc, F); by[PC_A] = arr(s.nc, F);
+  by[PB_PTR] = arr(n + 1, I); by[PB_IDX] = arr(s.npb, I); by[PB_VAL] = arr(s.npb, F);
+  by[PR_PTR] = arr(n + 1, I); by[PR_IDX] = arr(s.npr, I); by[PR_VAL] = arr(s.npr, F);
+  by[D_] = arr(n, F); by[DINV] = arr(n, F); by[E_] = arr(M, F); by[EINV] = arr(M, F);
+  by[Q] = arr(n, F); by[QRAW] = arr(n, F); by[RAW] = arr(3 * M + n, F);
+  by[LINV] = arr(n * ld, F); by[LINVT] = arr(n * ld, F); by[D2INV] = arr(n, F);
+  by[F_ROWS] = arr(n * ldf, F); by[F_GMT] = arr(M * ldn, F); by[F_AD] = arr(M * ldn, F); by[F_ATD] = arr(n * ldm, F);
+  by[F_PD] = arr(n * ldn, F); by[W_] = arr(N * ldw, F); by[KC] = arr(N * ldw, F);
+  by[L_] = arr(M, F); by[U_] = arr(M, F); by[X_] = arr(n, F); by[Z_] = arr(M, F); by[Y_] = arr(M, F); by[WH] = arr(N, F);
+  by[CV] = arr(n, F); by[UT] = arr(n, F); by[XT] = arr(n, F); by[DX] = arr(n, F); by[DY] = arr(M, F);
+  by[SM] = arr(8 * M, F); by[SN] = arr(10 * n, F); by[XI] = arr(n, F); by[XIS] = arr(n, F);
+  by[ROOT_L] = arr(M, F); by[ROOT_U] = arr(M, F); by[CTRL] = round_up(CTRL_BYTES, ALIGN); by[OUT] = arr(N, F);
+  by[I_IDX] = arr(n, I);
+  by[RESERVE] = arr(n, I) + arr(n * ldf, F) + arr(n, F) + arr(3 * N + 8, F) + arr(8, F) + 4096;
+}
+
+inline Plan plan(const std::vector<Shape> &sh, size_t entry_bytes) {
+  Plan P;
+  const size_t B = sh.size();
+  P.slot.resize(B);
+  P.table_bytes = round_up(B * entry_bytes, ALIGN);
+  size_t at = P.table_bytes;
+  std::vector<size_t> by((size_t)NPARTS * B);
+  for (size_t b = 0; b < B; b++) {
+    size_t one[NPARTS];
+    part_bytes(sh[b], one);
+    for (int k = 0; k < NPARTS; k++) by[b * NPARTS + k] = one[k];
+    for (int k = 0; k < FIRST_PRODUCT; k++) {
+      P.slot[b].part[k] = Span{at, one[k]};
+      at += one[k];
+    }
+    const size_t lds = lds_doubles(sh[b].n, sh[b].M) * sizeof(double);
+    if (lds > P.lds_bytes) P.lds_bytes = lds;
+  }
+  P.up_bytes = at;
+  for (size_t b = 0; b < B; b++)
+    for (int k = FIRST_PRODUCT; k < NPARTS; k++) {
+      P.slot[b].part[k] = Span{at, by[b * NPARTS + k]};
+      at += by[b * NPARTS + k];
+    }
+  P.rec_off = at;
+  P.rec_bytes = round_up(B * sizeof(Record), ALIGN);
+  for (size_t b = 0; b < B; b++) P.slot[b].rec = P.rec_off + b * sizeof(Record);
+  at += P.rec_bytes;
+  P.total_bytes = at;
+  // the slab: while the call runs it holds the upload's image; afterwards the same bytes are the engines' staging
+  size_t pin = 0;
+  for (size_t b = 0; b < B; b++) {
+    const size_t n = (size_t)sh[b].n, M = (size_t)sh[b].M;
+    Slot &s = P.slot[b];
+    s.in_cap = round_up(3 * M + 2 * n + 8, 8);  // bounds | x, y or q (miosqp_qp_set_integer_rows stages n_int + n ints and n doubles)
+    s.out_cap = round_up(n + M + 1, 8);
+    s.pin_in = pin;
+    pin += round_up(s.in_cap * sizeof(double), ALIGN);
+    s.pin_out = pin;
+    pin += round_up(s.out_cap * sizeof(double), ALIGN);
+    s.pin_ctrl = pin;
+    pin += round_up(CTRL_BYTES, ALIGN);
+    s.pin_ctrl2 = pin;
+    pin += round_up(2 * CTRL_BYTES, ALIGN);
+  }
+  P.pin_rec = round_up(pin > P.up_bytes ? pin : P.up_bytes, ALIGN);
+  P.pin_bytes = P.pin_rec + P.rec_bytes;
+  return P;
+}
+
+}  // namespace setup_models
+}  // namespace miosqp

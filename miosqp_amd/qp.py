@@ -4,6 +4,7 @@ Presents exactly the surface the reference's branch-and-bound layer uses on its 
 (SURVEY.md sec. 8b):
 
     osqp.OSQP().setup(P, q, A, l, u, **qp_settings)      /root/reference/miosqp/workspace.py:63-68
+      (for many models at once: setup_models below, one launch for the dense part of all of them)
     solver.update(l=, u=) / solver.update(q=)            node.py:102 / solver.py:185
     solver.warm_start(x=, y=)                            node.py:105
     solver.solve() -> .x .y .info.status_val .iter .run_time          node.py:108-125
@@ -120,6 +121,86 @@ def solve_trees_models(solvers, q, l, u, x0, y0, upper0, x_inc0, rules, max_iter
     return x, list(infos)[:B], stats
 
 
+def _csc_arrays(P, A):
+    """(n, m, [Pp, Pi, Px, Ap, Ai, Ax]) as OSQP.setup hands them to the library"""
+    P = spa.csc_matrix(P)
+    A = spa.csc_matrix(A)
+    P.sort_indices()
+    A.sort_indices()
+    n, m = A.shape[1], A.shape[0]
+    if P.shape != (n, n):
+        raise ValueError("P must be %d x %d" % (n, n))
+    return n, m, [np.ascontiguousarray(P.indptr, dtype=np.int32), np.ascontiguousarray(P.indices, dtype=np.int32),
+                  np.ascontiguousarray(P.data, dtype=np.float64), np.ascontiguousarray(A.indptr, dtype=np.int32),
+                  np.ascontiguousarray(A.indices, dtype=np.int32), np.ascontiguousarray(A.data, dtype=np.float64)]
+
+
+def setup_models_eligible(n, m, settings):
+    """Does the one-launch set-up take a model of n variables and m rows under these settings (a dict as for OSQP.setup,
+    or a Settings structure) and this environment?  (miosqp_qp_setup_models_eligible)"""
+    s = settings if isinstance(settings, _lib.Settings) else _settings_from_kwargs(settings)
+    return bool(_lib.load().miosqp_qp_setup_models_eligible(int(n), int(m), C.byref(s)))
+
+
+def setup_groups_live():
+    """groups of setup_models that are alive in this process (miosqp_qp_setup_groups_live)"""
+    return int(_lib.load().miosqp_qp_setup_groups_live())
+
+
+def setup_models(models):
+    """The set-up of several DIFFERENT small models in ONE launch (miosqp_qp_setup_models): the dense part of every
+    model -- Schur complement, LDL^T, triangular inverse, product form, explicit inverse, its guard -- by one workgroup
+    per model; the engines share one stream, one device arena and one pinned slab.
+
+    models: dicts with P, q, A, l, u (as OSQP.setup takes them), settings (a dict of OSQP.setup's keywords), and
+    optionally i_idx with m_orig (set_integer_rows is applied) and root = (l_root, u_root, eps_int_feas, eps_lin)
+    (set_root is applied).  Returns (a list of set-up OSQP objects in the order given, the call's SetupModelsStats).
+    ValueError for l > u or a P of the wrong shape (the position named), RuntimeError with the library's text for every
+    other refusal -- a model the launch does not take (setup_models_eligible), a pivot that is not positive."""
+    lib = _lib.load()
+    B = len(models)
+    desc = (_lib.SetupModel * max(B, 1))()
+    keep = []
+    shapes = []
+    for k, md in enumerate(models):
+        try:
+            n, m, arrs = _csc_arrays(md["P"], md["A"])
+        except ValueError as ex:
+            raise ValueError("setup_models: model %d: %s" % (k, ex))
+        q, l, u = _f64(md["q"], n, "q"), _f64(md["l"], m, "l"), _f64(md["u"], m, "u")
+        if np.any(l > u):
+            raise ValueError("setup_models: model %d: Lower bound must be lower than or equal to upper bound" % k)
+        s = _settings_from_kwargs(md.get("settings", {}))
+        d = desc[k]
+        d.n, d.M = n, m
+        d.Pp, d.Pi, d.Px = _lib.as_i(arrs[0]), _lib.as_i(arrs[1]), _lib.as_d(arrs[2])
+        d.Ap, d.Ai, d.Ax = _lib.as_i(arrs[3]), _lib.as_i(arrs[4]), _lib.as_d(arrs[5])
+        d.q, d.l, d.u = _lib.as_d(q), _lib.as_d(l), _lib.as_d(u)
+        d.settings = C.pointer(s)
+        d.n_int = -1
+        held = [arrs, q, l, u, s]
+        if md.get("i_idx") is not None:
+            ii = np.ascontiguousarray(md["i_idx"], dtype=np.int32)
+            d.n_int, d.m_orig, d.i_idx = len(ii), int(md["m_orig"]), _lib.as_i(ii)
+            held.append(ii)
+            if md.get("root") is not None:
+                lr, ur, eps_int, eps_lin = md["root"]
+                lr, ur = _f64(lr, m, "l_root"), _f64(ur, m, "u_root")
+                d.l_root, d.u_root, d.eps_int_feas, d.eps_lin = _lib.as_d(lr), _lib.as_d(ur), float(eps_int), float(eps_lin)
+                held += [lr, ur]
+        keep.append(held)
+        shapes.append((n, m, s))
+    hs = (C.c_void_p * max(B, 1))()
+    stats = _lib.SetupModelsStats()
+    _check(lib.miosqp_qp_setup_models(B, desc, hs, C.byref(stats)), "setup_models")
+    out = []
+    for k, (n, m, s) in enumerate(shapes):
+        g = OSQP()
+        g._h, g.n, g.m, g.settings = C.c_void_p(hs[k]), n, m, s
+        out.append(g)
+    return out, stats
+
+
 class DevicePtr(object):
     """`count` doubles at address `addr` of DEVICE memory (a slice of a torch tensor, say): accepted wherever a leaf's
     vectors go in or come out (search_add_leaf / search_take_leaf, stream_*, pool_write_node / pool_read_node) -- the
@@ -167,21 +248,9 @@ class OSQP(object):
     def setup(self, P=None, q=None, A=None, l=None, u=None, **settings):
         if self._h is not None:
             raise RuntimeError("setup() called twice")
-        P = spa.csc_matrix(P)
-        A = spa.csc_matrix(A)
-        P.sort_indices()
-        A.sort_indices()
-        n, m = A.shape[1], A.shape[0]
-        if P.shape != (n, n):
-            raise ValueError("P must be %d x %d" % (n, n))
+        n, m, arrs = _csc_arrays(P, A)
         s = _settings_from_kwargs(settings)
-        arrs = [np.ascontiguousarray(P.indptr, dtype=np.int32),
-                np.ascontiguousarray(P.indices, dtype=np.int32),
-                np.ascontiguousarray(P.data, dtype=np.float64),
-                np.ascontiguousarray(A.indptr, dtype=np.int32),
-                np.ascontiguousarray(A.indices, dtype=np.int32),
-                np.ascontiguousarray(A.data, dtype=np.float64),
-                _f64(q, n, "q"), _f64(l, m, "l"), _f64(u, m, "u")]
+        arrs += [_f64(q, n, "q"), _f64(l, m, "l"), _f64(u, m, "u")]
         if np.any(arrs[7] > arrs[8]):
             raise ValueError("Lower bound must be lower than or equal to upper bound")
         h = C.c_void_p()
@@ -891,6 +960,27 @@ class OSQP(object):
         if which == 0:
             return raw[:, 0].copy(), raw
         return raw[:, :rows.value].copy(), raw
+
+    def debug_product_form(self, which):
+        """One array of the product form read back (miosqp_qp_debug_product_form): 0 f_rows (n x (M + n): [-G | strict
+        lower of Linv]), 1 f_GmT (M x n), 2 f_Ad (M x n), 3 f_Atd (n x M), 4 f_Pd (n x n); 5, 6, 7: the scaled q, l, u as
+        vectors.  Returns (the logical part, the raw padded array as it lies in device memory).  RuntimeError for an engine without the product form."""
+        rows, ld = C.c_int32(), C.c_int32()
+        _check(self._lib.miosqp_qp_debug_product_form(self._h, int(which), None, 0, C.byref(rows), C.byref(ld)),
+               "debug_product_form")
+        raw = np.empty((rows.value, ld.value))
+        _check(self._lib.miosqp_qp_debug_product_form(self._h, int(which), _lib.as_d(raw), raw.size, C.byref(rows),
+                                                      C.byref(ld)), "debug_product_form")
+        if which >= 5:
+            return raw[:, 0].copy(), raw
+        cols = (self.n + self.m, self.n, self.n, self.m, self.n)[int(which)]
+        return raw[:, :cols].copy(), raw
+
+    def setup_group(self):
+        """the group of setup_models this engine belongs to (a positive number, shared by the engines of one call), None
+        for an engine of setup()"""
+        g = int(self._lib.miosqp_qp_setup_group(self._h)) if self._h is not None else 0
+        return g if g > 0 else None
 
     def scaling(self):
         D, E, c = np.empty(self.n), np.empty(self.m), C.c_double()
