@@ -252,11 +252,11 @@ struct CoopNode {
 #include "host_pool.inc"  // host side of the leaf pool (C ABI miosqp_qp_pool_*)
 #include "host_search.inc"  // node-at-a-time branch and bound driven from the host in C++ (C ABI miosqp_qp_search_*)
 #include "host_stream.inc"  // the host side of the streaming search in C++ (C ABI miosqp_qp_stream_*)
-#include "host_lockstep.inc"  // B trees in lock step driven from the host in C++ (C ABI miosqp_qp_solve_trees_lockstep, miosqp_qp_solve_trees_lockstep_rf)
-#include "host_refill.inc"  // the same trees on columns refilled between chunks (C ABI miosqp_qp_solve_trees_refill)
-#include "host_lockstep_ahead.inc"  // the lock-step trees with spare columns solving open leaves early (C ABI miosqp_qp_solve_trees_lockstep_ahead); its two kernels
+#include "host_lockstep.inc"  // B trees in lock step driven from the host in C++: the store, the pieces every tree driver is built from (ls_*), the wave loop with a driver's step in it; the plain and the round-and-fix step (C ABI miosqp_qp_solve_trees_lockstep, miosqp_qp_solve_trees_lockstep_rf)
+#include "host_refill.inc"  // the same trees on columns refilled between chunks: its column arrays and chunk loop between those pieces (C ABI miosqp_qp_solve_trees_refill)
+#include "host_lockstep_ahead.inc"  // the lock-step trees with spare columns solving open leaves early: its two kernels and its own wave loop between those pieces (C ABI miosqp_qp_solve_trees_lockstep_ahead)
 #include "kernels_lockstep_sb.inc"  // strong and reliability branching in the lock-step trees: x at the integer positions, the children's gather, judge and bounds
-#include "host_lockstep_sb.inc"  // ... and its driver (C ABI miosqp_qp_solve_trees_lockstep_sb)
+#include "host_lockstep_sb.inc"  // ... and its step in host_lockstep.inc's wave loop (C ABI miosqp_qp_solve_trees_lockstep_sb)
 #include "kernels_setup_models.inc"  // the dense set-up of many small models in one launch (k_setup_models)
 #include "host_setup_models.inc"  // ... and its host side: the group, the arena, the engines (C ABI miosqp_qp_setup_models)
 #include "host_models.inc"  // what the one-launch tree entries share; trees of different models in one launch (C ABI miosqp_qp_tree_form, miosqp_qp_solve_trees_models)
@@ -1470,11 +1470,7 @@ int miosqp_qp_solve_batch_q(miosqp_qp_engine *e, int32_t B, const double *q, con
     if (l[k] > u[k]) return MIOSQP_EBOUNDS;
   if (int rc = ensure_batch(e)) return rc;
   if (int rc = ensure_batch_q(e)) return rc;
-  struct PqScope {  // every launch helper and the chunk-graph cache look at e->pq; off again on every way out
-    miosqp_qp_engine *e;
-    explicit PqScope(miosqp_qp_engine *e_) : e(e_) { e->pq = 1; }
-    ~PqScope() { e->pq = 0; }
-  } scope(e);
+  PqScope scope(e);  // (host_lockstep.inc)
   for (int s0 = 0; s0 < B; s0 += e->Bcap) {
     const int nb = B - s0 < e->Bcap ? B - s0 : e->Bcap;
     int rc = solve_slice(e, nb, l + s0 * M, u + s0 * M, x0 + s0 * n, y0 + s0 * M, x_out + s0 * n, y_out + s0 * M,

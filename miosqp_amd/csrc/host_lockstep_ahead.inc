@@ -8,6 +8,10 @@
 // and incumbent kernels are the lock-step driver's; per wave one upload (five integers and a flag per column), one
 // download (a 64-byte record per column), one synchronisation behind the chunk loop's own.
 //
+// This file owns the wave loop of this driver -- planning, the last slice with LsNeed and kls_scatter_ahead, settle, the
+// choice of the one incumbent per tree that goes up -- and its counters; checks, store, roots, slot growth, the record's
+// conversion, the incumbent push, the per-wave statistics and the end of the call are the pieces of host_lockstep.inc.
+//
 // The two kernels below are copies and a short count over vector loads and stores: one launch each, no spin wait, no
 // hand-off between workgroups, no whole-chip launch.  They are templates instantiated only here, behind every other
 // kernel of the code object (see kernels_lockstep.inc for why).
@@ -155,102 +159,48 @@ int ahead_reserve(miosqp_qp_engine *e, AheadCols &A, int cols) {
   return 0;
 }
 
-// the body of miosqp_qp_solve_trees_lockstep_ahead: lockstep_trees_run (host_lockstep.inc) without round and fix, the
-// wave planned and settled by lockstep_ahead.hpp
-int lockstep_ahead_run(miosqp_qp_engine *e, int32_t B, const double *q, const double *l, const double *u, const double *x0,
-                       const double *y0, const double *upper0, const double *x_inc0, int32_t tree_explor_rule,
-                       int32_t max_iter_bb, int32_t capacity, int32_t ahead, double *x_out, miosqp_tree_info *info,
-                       miosqp_lockstep_stats *stats, miosqp_lockstep_ahead_stats *as) {
+}  // namespace
+
+extern "C" {
+
+// the plain driver's call (the pieces of host_lockstep.inc) around a wave loop of its own: the wave is planned and
+// settled by lockstep_ahead.hpp, and its last slice ends with its mandatory columns
+int miosqp_qp_solve_trees_lockstep_ahead(miosqp_qp_engine *e, int32_t B, const double *q, const double *l, const double *u,
+                                         const double *x0, const double *y0, const double *upper0, const double *x_inc0,
+                                         int32_t tree_explor_rule, int32_t max_iter_bb, int32_t capacity, int32_t ahead,
+                                         double *x_out, miosqp_tree_info *info, miosqp_lockstep_stats *stats,
+                                         miosqp_lockstep_ahead_stats *as) {
   using miosqp::lockstep::AheadColumn;
   using miosqp::lockstep::AheadEvent;
   using miosqp::lockstep::AheadOutcome;
   using miosqp::lockstep::Tree;
-  if (!e || B < 1 || !q || !l || !u || !x0 || !y0 || !upper0 || !x_out || !info || !stats || !as || max_iter_bb < 1 ||
-      tree_explor_rule < 0 || tree_explor_rule > 3 || capacity < 0)
-    return MIOSQP_EARG;
+  const LsCall a{"solve_trees_lockstep_ahead", e, B, q, l, u, x0, y0, upper0, x_inc0, tree_explor_rule, max_iter_bb, capacity, x_out, info};
+  if (!ls_args_ok(a) || !stats || !as) return MIOSQP_EARG;
   if (ahead < 1) {
     g_err = "solve_trees_lockstep_ahead: ahead must be at least 1";
     return MIOSQP_EARG;
   }
   ENTER(e);
-  if (!e->have_int || !e->d.digest || e->d.n_int < 1) {
-    g_err = "solve_trees_lockstep_ahead: call miosqp_qp_set_integer_rows and miosqp_qp_set_root first";
-    return MIOSQP_EARG;
-  }
-  if (e->pool_pending) {
-    g_err = "solve_trees_lockstep_ahead: streaming chunks are still in flight (pool_collect first)";
-    return MIOSQP_EARG;
-  }
-  const size_t n = e->n, M = e->M, m = (size_t)e->d.m_orig, p = (size_t)e->d.n_int;
-  for (size_t k = 0; k < (size_t)B * M; k++)
-    if (l[k] > u[k]) {  // (nothing has been queued)
-      g_err = "solve_trees_lockstep_ahead: l > u in the root of instance " + std::to_string(k / M);
-      return MIOSQP_EBOUNDS;
-    }
-  stats->waves = stats->max_width = stats->grown = 0;
-  stats->nodes = stats->iters_slowest = stats->iters_all = 0;
-  stats->device_time = stats->run_time = stats->host_time = 0.0;
+  if (int rc = ls_refuse(a)) return rc;
+  ls_stats_zero(stats);
   as->waves = 0;
   as->columns = as->sent = as->hits = as->discarded = as->called_off = 0;
   as->hit_iters = as->discarded_iters = as->called_off_iters = 0;
-  if (int rc = ensure_batch(e)) return rc;
-  if (int rc = ensure_batch_q(e)) return rc;
-  if (!e->lockstep) e->lockstep = new LockstepStore();
-  LockstepStore &L = *static_cast<LockstepStore *>(e->lockstep);
   const int Bw = B + 64;  // a wave holds its mandatory columns and less than one tile of ahead columns
-  if (int rc = lockstep_reserve(e, L, Bw)) return rc;
+  LockstepStore *Lp = nullptr;
+  if (int rc = ls_open(a, Bw, &Lp, &stats->grown)) return rc;
+  LockstepStore &L = *Lp;
   if (!L.ahead) L.ahead = new AheadCols();
   AheadCols &A = *static_cast<AheadCols *>(L.ahead);
   if (int rc = ahead_reserve(e, A, Bw)) return rc;
-  {
-    // `capacity` is a starting size: a store left by an earlier call is kept when the caller leaves the size to us
-    const int want = capacity > 0 ? std::max(capacity, 4) : std::max(64, 4 * B);
-    if (!L.slot_block || (capacity > 0 ? L.cap != want : L.cap < want))
-      if (int rc = lockstep_slots(e, L, want, 0)) return rc;
-    while (L.cap < B) {  // (a starting size below the number of roots)
-      if (int rc = lockstep_slots(e, L, 2 * L.cap, 0)) return rc;
-      stats->grown++;
-    }
-  }
   const double t0 = wall();
-  struct PqScope {  // every launch helper and the chunk-graph cache look at e->pq; off again on every way out
-    miosqp_qp_engine *e;
-    explicit PqScope(miosqp_qp_engine *e_) : e(e_) { e->pq = 1; }
-    ~PqScope() { e->pq = 0; }
-  } scope(e);
+  PqScope scope(e);
   const Dev &d = e->d;
-  L.slots.reset(L.cap);
-  L.trees.assign((size_t)B, Tree());
+  const size_t n = e->n, M = e->M;
+  if (int rc = ls_upload_roots(a, L)) return rc;
   A.logic.reset(L.cap, B);
   A.pair_slot.assign((size_t)B, -1);
   A.pair_rounded.assign((size_t)B, 0);
-  // ---- the roots: bounds, costs and incumbents per instance; tree b's root is slot b (as lockstep_trees_run sends them) ----
-  {
-    const size_t tot = (size_t)B * (2 * M + 2 * n + 2 * p + n + M);
-    if (L.stage.size() < tot) L.stage.resize(tot);
-    double *h_inc = L.stage.data(), *h_lo = h_inc + (size_t)B * n, *h_hi = h_lo + (size_t)B * p;
-    for (int b = 0; b < B; b++) {
-      const bool have = x_inc0 != nullptr && upper0[b] < miosqp::lockstep::NO_UPPER;
-      if (have) memcpy(h_inc + (size_t)b * n, x_inc0 + (size_t)b * n, sizeof(double) * n);
-      else memset(h_inc + (size_t)b * n, 0, sizeof(double) * n);
-      memcpy(h_lo + (size_t)b * p, l + (size_t)b * M + m, sizeof(double) * p);
-      memcpy(h_hi + (size_t)b * p, u + (size_t)b * M + m, sizeof(double) * p);
-      const int s = L.slots.take();  // == b: the free list is fresh
-      L.trees[(size_t)b].start(L.slots, s, have ? upper0[b] : miosqp::lockstep::NO_UPPER);
-    }
-    HIPCHK(hipEventRecord(e->ev0, e->stream));
-    HIPCHK(hipMemcpyAsync(const_cast<double *>(L.dev.root_l), l, sizeof(double) * (size_t)B * M, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(const_cast<double *>(L.dev.root_u), u, sizeof(double) * (size_t)B * M, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(const_cast<double *>(L.dev.qraw), q, sizeof(double) * (size_t)B * n, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(L.dev.inc, h_inc, sizeof(double) * (size_t)B * n, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(L.dev.lo, h_lo, sizeof(double) * (size_t)B * p, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(L.dev.hi, h_hi, sizeof(double) * (size_t)B * p, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(L.dev.x, x0, sizeof(double) * (size_t)B * n, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(L.dev.y, y0, sizeof(double) * (size_t)B * M, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    hipLaunchKernelGGL(k_scale_q_batch, dim3((unsigned)(((size_t)B * n + 255) / 256)), dim3(256), 0, e->stream, d, L.dev.qraw,
-                       const_cast<double *>(L.dev.qs), B);
-  }
   std::vector<int> live;
   live.reserve((size_t)B);
   int *h_left = A.h_mand + A.cap, *d_left = A.d_mand + A.cap;
@@ -269,13 +219,9 @@ int lockstep_ahead_run(miosqp_qp_engine *e, int32_t B, const double *q, const do
     const int last0 = ((W0 - 1) / e->Bcap) * e->Bcap, nbl = W0 - last0;
     const int room = std::min(64 * ((nbl + 63) / 64), e->Bcap) - nbl;
     const int free_cols = ahead > 1 ? room : 0;
-    while (L.slots.free_count() < 2 * (size_t)(W0 + free_cols)) {  // two child slots per column sent
-      const int keep = L.cap;
-      if (int rc = lockstep_slots(e, L, 2 * L.cap, keep)) return rc;
-      L.slots.grow(L.cap);
-      A.logic.grow(L.cap);
-      stats->grown++;
-    }
+    int rc = 0;
+    if (ls_room(e, L, 2 * (size_t)(W0 + free_cols), &stats->grown, &rc)) A.logic.grow(L.cap);  // two child slots per column sent
+    if (rc) return rc;
     A.logic.plan(L.slots, L.trees, live, tree_explor_rule, ahead, free_cols, A.cols);
     const int W = (int)A.cols.size();
     for (int c = 0; c < W; c++) {
@@ -293,7 +239,7 @@ int lockstep_ahead_run(miosqp_qp_engine *e, int32_t B, const double *q, const do
     for (int s0 = 0; s0 < W0; s0 += e->Bcap) {
       const int nb = s0 == last0 ? W - s0 : e->Bcap;
       const int ntiles = (nb + 63) / 64;
-      if (int rc = slice_begin(e, nb)) return rc;
+      if ((rc = slice_begin(e, nb)) != 0) return rc;
       if (s0 == 0) {  // the wave's one upload (behind slice_begin, as solve_slice queues its own)
         HIPCHK(hipMemcpyAsync(L.d_trip, L.h_trip, sizeof(int) * LS_TRIP * (size_t)W, hipMemcpyHostToDevice, e->stream));
         if (W > W0) HIPCHK(hipMemcpyAsync(A.d_mand, A.h_mand, sizeof(int) * (size_t)W, hipMemcpyHostToDevice, e->stream));
@@ -305,11 +251,11 @@ int lockstep_ahead_run(miosqp_qp_engine *e, int32_t B, const double *q, const do
       const dim3 sgrid((int)((n + 63) / 64 + (M + 63) / 64) + 1, ntiles);
       if (s0 == last0 && W > W0) {
         LsNeed need{A.d_mand + s0, d_left, h_left, 0, false};
-        if (int rc = slice_run(e, nb, e->st.max_iter, &roots, &need)) return rc;
+        if ((rc = slice_run(e, nb, e->st.max_iter, &roots, &need)) != 0) return rc;
         hipLaunchKernelGGL(kls_scatter_ahead<0>, sgrid, dim3(256), 0, e->stream, d, L.dev, trip, L.d_rec + s0, nb, need.cut ? 1 : 0);
         need_chunks = need.chunks;
       } else {  // a slice of mandatory columns only: the launches of miosqp_qp_solve_trees_lockstep
-        if (int rc = slice_run(e, nb, e->st.max_iter, &roots)) return rc;
+        if ((rc = slice_run(e, nb, e->st.max_iter, &roots)) != 0) return rc;
         hipLaunchKernelGGL(kls_scatter<0>, sgrid, dim3(256), 0, e->stream, d, L.dev, trip, L.d_rec + s0, nb);
       }
     }
@@ -327,13 +273,7 @@ int lockstep_ahead_run(miosqp_qp_engine *e, int32_t B, const double *q, const do
       AheadOutcome &o = A.out[(size_t)c];
       o.finished = g.status != LS_UNFINISHED;
       o.crossed = g.crossed != 0;
-      o.r.ok = g.status == MIOSQP_QP_SOLVED || g.status == MIOSQP_QP_MAX_ITER_REACHED;
-      o.r.iter = g.iter;
-      o.r.lower = g.lower;
-      o.r.int_inf = g.int_inf;
-      o.r.nextvar = g.nextvar;
-      o.r.heur_feasible = g.hviol <= 0.0;
-      o.r.heur_obj = g.hobj;
+      o.r = ls_record(g);
       if (c < W0) {
         it_max = g.iter > it_max ? g.iter : it_max;
         it_sum += g.iter;
@@ -359,8 +299,7 @@ int lockstep_ahead_run(miosqp_qp_engine *e, int32_t B, const double *q, const do
     });
     if (!ok) {
       for (int b : A.touched) A.pair_slot[(size_t)b] = -1;
-      g_err = "solve_trees_lockstep_ahead: branching produced l > u (instance " + std::to_string(bad) + ")";
-      return MIOSQP_EBOUNDS;
+      return ls_crossed(a, bad);
     }
     int npairs = 0;
     for (int b : A.touched) {
@@ -371,22 +310,14 @@ int lockstep_ahead_run(miosqp_qp_engine *e, int32_t B, const double *q, const do
       A.pair_slot[(size_t)b] = -1;
     }
     host_s += wall() - th;
-    if (npairs > 0) {  // (a freed slot keeps its x until the next wave's scatter, which is queued behind this launch)
-      HIPCHK(hipMemcpyAsync(L.d_pairs, L.h_pairs, sizeof(int) * 3 * (size_t)npairs, hipMemcpyHostToDevice, e->stream));
-      hipLaunchKernelGGL(kls_incumbent<0>, dim3(npairs), dim3(256), 0, e->stream, d, L.dev, L.d_pairs, npairs);
-    }
-    stats->max_width = W > stats->max_width ? W : stats->max_width;
-    stats->iters_slowest += it_max;
+    // (a freed slot keeps its x until the next wave's scatter, which is queued behind this launch)
+    if ((rc = ls_push_incumbents(e, d, L.dev, L.d_pairs, L.h_pairs, npairs)) != 0) return rc;
+    ls_stats_wave(stats, wave, W, it_max, it_sum, W0);  // (the iteration figures are the mandatory columns')
     as->columns += W;
     // chunks: what the slowest slice ran -- counted where kls_need ended the loop, ceil(iterations / check_termination)
     // of the slowest column elsewhere (a slice of mandatory columns runs exactly that; the tail at max_iter is one chunk)
     const int chunks_mand = (it_max + e->chunk - 1) / e->chunk;
     const int chunks = need_chunks > chunks_mand ? need_chunks : chunks_mand;
-    if (wave <= stats->wave_cap) {
-      if (stats->wave_width) stats->wave_width[wave - 1] = W;
-      if (stats->wave_iter_max) stats->wave_iter_max[wave - 1] = it_max;
-      if (stats->wave_iter_mean) stats->wave_iter_mean[wave - 1] = (double)it_sum / W0;
-    }
     if (wave <= as->wave_cap) {
       if (as->wave_width) as->wave_width[wave - 1] = W;
       if (as->wave_iter_mandatory) as->wave_iter_mandatory[wave - 1] = it_max;
@@ -394,36 +325,14 @@ int lockstep_ahead_run(miosqp_qp_engine *e, int32_t B, const double *q, const do
     }
   }
   A.logic.finish(L.slots);  // the records nobody reached
-  // ---- the incumbents ----
-  double *h_inc = L.stage.data();
-  HIPCHK(hipMemcpyAsync(h_inc, L.dev.inc, sizeof(double) * (size_t)B * n, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipEventRecord(e->ev1, e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
-  HIPCHK(hipGetLastError());
-  float ms = 0;
-  HIPCHK(hipEventElapsedTime(&ms, e->ev0, e->ev1));
-  const double wall_s = wall() - t0;
-  int64_t iters_total = 0;
+  if (int rc = ls_finish(a, L, t0, host_s, stats)) return rc;
+  // nodes and iterations are the absorbed nodes', not the columns sent: what info[b] sums to
+  stats->nodes = stats->iters_all = 0;
   for (int b = 0; b < B; b++) {
-    const Tree &T = L.trees[(size_t)b];
-    const bool have = x_inc0 != nullptr && upper0[b] < miosqp::lockstep::NO_UPPER;
-    info[b].nodes = (int32_t)T.nodes;
-    info[b].osqp_iter = (int32_t)T.iters;
-    info[b].leaves_left = (int32_t)T.open.size();
-    info[b].overflow = 0;
-    info[b].max_leaves = (int32_t)T.max_open;
-    info[b].found = T.found ? 1 : 0;
-    info[b].upper_glob = T.upper;
-    info[b].lower_glob = T.lower_glob(L.slots);
-    info[b].device_time = 1e-3 * ms / B;
-    info[b].run_time = wall_s / B;
-    if (T.found || have) memcpy(x_out + (size_t)b * n, h_inc + (size_t)b * n, sizeof(double) * n);
-    if (stats->finished_at) stats->finished_at[b] = T.finished_at;
-    stats->nodes += T.nodes;
-    iters_total += T.iters;
+    stats->nodes += L.trees[(size_t)b].nodes;
+    stats->iters_all += L.trees[(size_t)b].iters;
   }
   const miosqp::lockstep::AheadCounts &cn = A.logic.n;
-  stats->iters_all = iters_total;  // (absorbed nodes only: what info[b].osqp_iter sums to)
   as->waves = stats->waves;
   as->sent = cn.sent;
   as->hits = cn.hits;
@@ -434,25 +343,7 @@ int lockstep_ahead_run(miosqp_qp_engine *e, int32_t B, const double *q, const do
   as->called_off_iters = cn.called_off_iters;
   as->free_slots = (int32_t)L.slots.free_count();
   as->slot_cap = (int32_t)L.slots.cap;
-  stats->device_time = 1e-3 * ms;
-  stats->run_time = wall_s;
-  stats->host_time = host_s;
-  e->loop_ms += ms;
-  e->loop_iters += iters_total;
   return 0;
-}
-
-}  // namespace
-
-extern "C" {
-
-int miosqp_qp_solve_trees_lockstep_ahead(miosqp_qp_engine *e, int32_t B, const double *q, const double *l, const double *u,
-                                         const double *x0, const double *y0, const double *upper0, const double *x_inc0,
-                                         int32_t tree_explor_rule, int32_t max_iter_bb, int32_t capacity, int32_t ahead,
-                                         double *x_out, miosqp_tree_info *info, miosqp_lockstep_stats *stats,
-                                         miosqp_lockstep_ahead_stats *ahead_stats) {
-  return lockstep_ahead_run(e, B, q, l, u, x0, y0, upper0, x_inc0, tree_explor_rule, max_iter_bb, capacity, ahead, x_out, info,
-                            stats, ahead_stats);
 }
 
 }  // extern "C"

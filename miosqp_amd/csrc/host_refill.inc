@@ -1,10 +1,13 @@
-// part of engine.hip (included there, not compiled alone; the LAST file of the translation unit): B branch-and-bound trees on
+// part of engine.hip (included there, not compiled alone; behind host_lockstep.inc, whose pieces it uses): B branch-and-bound trees on
 // columns that are refilled between chunks (C ABI miosqp_qp_solve_trees_refill).  The trees, slots, roots and costs are the
 // lock-step driver's (host_lockstep.inc, lockstep_trees.hpp); the wave is gone: a column holds one node of one tree, and
 // at every chunk boundary the columns the test decided are harvested, absorbed by their trees and loaded again with the next
 // leaf of a tree that has no node in flight (lockstep_refill.hpp).  Per boundary ONE download (the list of harvested columns
 // and their 64-byte records, behind a 64-byte head) and ONE synchronisation, then ONE upload (six integers per filled column
 // and the incumbent pairs); no vector crosses PCIe between the roots going up and the incumbents coming down.
+//
+// This file owns the column arrays, the chunk's capture and the chunk loop with its statistics; checks, store, roots,
+// slot growth, the record's conversion, the incumbent push and the end of the call are the pieces of host_lockstep.inc.
 namespace {
 
 struct RefillCols {
@@ -112,103 +115,44 @@ int capture_chunk_refill(miosqp_qp_engine *e, const Dev &d, int ntiles) {
 
 extern "C" {
 
+// the plain driver's call (the pieces of host_lockstep.inc) around a chunk loop instead of a wave loop
 int miosqp_qp_solve_trees_refill(miosqp_qp_engine *e, int32_t B, const double *q, const double *l, const double *u,
                                  const double *x0, const double *y0, const double *upper0, const double *x_inc0,
                                  int32_t tree_explor_rule, int32_t max_iter_bb, int32_t capacity, double *x_out,
                                  miosqp_tree_info *info, miosqp_refill_stats *stats) {
   using miosqp::lockstep::Fill;
-  using miosqp::lockstep::Record;
-  using miosqp::lockstep::Tree;
   using miosqp::lockstep::Verdict;
-  if (!e || B < 1 || !q || !l || !u || !x0 || !y0 || !upper0 || !x_out || !info || !stats || max_iter_bb < 1 ||
-      tree_explor_rule < 0 || tree_explor_rule > 3 || capacity < 0)
-    return MIOSQP_EARG;
+  const LsCall a{"solve_trees_refill", e, B, q, l, u, x0, y0, upper0, x_inc0, tree_explor_rule, max_iter_bb, capacity, x_out, info};
+  if (!ls_args_ok(a) || !stats) return MIOSQP_EARG;
   ENTER(e);
-  if (!e->have_int || !e->d.digest || e->d.n_int < 1) {
-    g_err = "solve_trees_refill: call miosqp_qp_set_integer_rows and miosqp_qp_set_root first";
-    return MIOSQP_EARG;
-  }
-  if (e->pool_pending) {
-    g_err = "solve_trees_refill: streaming chunks are still in flight (pool_collect first)";
-    return MIOSQP_EARG;
-  }
-  if (e->st.max_iter % e->chunk != 0) {
-    g_err = "solve_trees_refill: a column counts its own chunks: max_iter must be a multiple of check_termination";
-    return MIOSQP_EARG;
-  }
-  const size_t n = e->n, M = e->M, m = (size_t)e->d.m_orig, p = (size_t)e->d.n_int;
-  for (size_t k = 0; k < (size_t)B * M; k++)
-    if (l[k] > u[k]) {  // (nothing has been queued)
-      g_err = "solve_trees_refill: l > u in the root of instance " + std::to_string(k / M);
-      return MIOSQP_EBOUNDS;
-    }
+  if (int rc = ls_refuse(a, e->st.max_iter % e->chunk != 0
+                                ? "a column counts its own chunks: max_iter must be a multiple of check_termination"
+                                : nullptr))
+    return rc;
   stats->chunks = stats->columns = stats->grown = 0;
   stats->nodes = stats->iters_all = stats->col_chunks_busy = stats->col_chunks_total = 0;
   stats->device_time = stats->run_time = stats->host_time = stats->chunk_time = 0.0;
   stats->nodes_max_iter = stats->iters_max_iter = 0;
-  if (int rc = ensure_batch(e)) return rc;
-  if (int rc = ensure_batch_q(e)) return rc;
-  if (!e->lockstep) e->lockstep = new LockstepStore();
-  LockstepStore &L = *static_cast<LockstepStore *>(e->lockstep);
+  LockstepStore *Lp = nullptr;
+  if (int rc = ls_open(a, B, &Lp, &stats->grown)) return rc;
+  LockstepStore &L = *Lp;
   if (!L.refill) L.refill = new RefillCols();
   RefillCols &R = *static_cast<RefillCols *>(L.refill);
-  if (int rc = lockstep_reserve(e, L, B)) return rc;
   if (int rc = refill_reserve(e, R)) return rc;
-  {
-    // the slot store as miosqp_qp_solve_trees_lockstep sizes it
-    const int want = capacity > 0 ? std::max(capacity, 4) : std::max(64, 4 * B);
-    if (!L.slot_block || (capacity > 0 ? L.cap != want : L.cap < want))
-      if (int rc = lockstep_slots(e, L, want, 0)) return rc;
-    while (L.cap < B) {
-      if (int rc = lockstep_slots(e, L, 2 * L.cap, 0)) return rc;
-      stats->grown++;
-    }
-  }
+  const size_t n = e->n, M = e->M;
   const int C = B < e->Bcap ? B : e->Bcap, ntiles = (C + 63) / 64;
   stats->columns = C;
   e->pool_dirty = true;  // (the columns are ours now: as slice_begin marks them)
   if (int rcj = maybe_rejoin_kbp(e, 8)) return rcj;
   const double t0 = wall();
-  struct PqScope {  // every launch helper looks at e->pq; off again on every way out
-    miosqp_qp_engine *e;
-    explicit PqScope(miosqp_qp_engine *e_) : e(e_) { e->pq = 1; }
-    ~PqScope() { e->pq = 0; }
-  } scope(e);
+  PqScope scope(e);
   const Dev ds = refill_dev(e, R);
   RfDev rf = R.dev;
   rf.C = C;
   if (!e->xr_full[ntiles - 1])
     if (int rc = capture_chunk_refill(e, ds, ntiles)) return rc;
-  L.slots.reset(L.cap);
-  L.trees.assign((size_t)B, Tree());
   R.sched.reset(C, B);
-  // ---- the roots, exactly as the lock-step driver stores them: tree b's root is slot b ----
-  {
-    const size_t tot = (size_t)B * (2 * M + 2 * n + 2 * p + n + M);
-    if (L.stage.size() < tot) L.stage.resize(tot);
-    double *h_inc = L.stage.data(), *h_lo = h_inc + (size_t)B * n, *h_hi = h_lo + (size_t)B * p;
-    for (int b = 0; b < B; b++) {
-      const bool have = x_inc0 != nullptr && upper0[b] < miosqp::lockstep::NO_UPPER;
-      if (have) memcpy(h_inc + (size_t)b * n, x_inc0 + (size_t)b * n, sizeof(double) * n);
-      else memset(h_inc + (size_t)b * n, 0, sizeof(double) * n);
-      memcpy(h_lo + (size_t)b * p, l + (size_t)b * M + m, sizeof(double) * p);
-      memcpy(h_hi + (size_t)b * p, u + (size_t)b * M + m, sizeof(double) * p);
-      const int s = L.slots.take();  // == b: the free list is fresh
-      L.trees[(size_t)b].start(L.slots, s, have ? upper0[b] : miosqp::lockstep::NO_UPPER);
-    }
-    HIPCHK(hipEventRecord(e->ev0, e->stream));
-    HIPCHK(hipMemcpyAsync(const_cast<double *>(L.dev.root_l), l, sizeof(double) * (size_t)B * M, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(const_cast<double *>(L.dev.root_u), u, sizeof(double) * (size_t)B * M, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(const_cast<double *>(L.dev.qraw), q, sizeof(double) * (size_t)B * n, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(L.dev.inc, h_inc, sizeof(double) * (size_t)B * n, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(L.dev.lo, h_lo, sizeof(double) * (size_t)B * p, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(L.dev.hi, h_hi, sizeof(double) * (size_t)B * p, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(L.dev.x, x0, sizeof(double) * (size_t)B * n, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(L.dev.y, y0, sizeof(double) * (size_t)B * M, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    hipLaunchKernelGGL(k_scale_q_batch, dim3((unsigned)(((size_t)B * n + 255) / 256)), dim3(256), 0, e->stream, e->d, L.dev.qraw,
-                       const_cast<double *>(L.dev.qs), B);
-  }
+  if (int rc = ls_upload_roots(a, L)) return rc;
   // ---- the columns: all decided and idle, the working vectors zero (what a wave gives its padding) ----
   const int big = (int)(n > M ? n : M);
   hipLaunchKernelGGL(kb_reset, dim3((ds.Bs + 255) / 256), dim3(256), 0, e->stream, ds, 0);
@@ -228,12 +172,9 @@ int miosqp_qp_solve_trees_refill(miosqp_qp_engine *e, int32_t B, const double *q
     // ---- fill the free columns (at the first pass: all of them) and send the boundary's one upload ----
     double th = wall();
     const int want = R.sched.fillable(L.trees, max_iter_bb);
-    while (L.slots.free_count() < 2 * (size_t)want) {  // two child slots per filled column
-      const int keep = L.cap;
-      if (int rc = lockstep_slots(e, L, 2 * L.cap, keep)) return rc;
-      L.slots.grow(L.cap);
-      stats->grown++;
-    }
+    int rc = 0;
+    ls_room(e, L, 2 * (size_t)want, &stats->grown, &rc);  // two child slots per filled column
+    if (rc) return rc;
     R.fills.clear();
     const int nfill = R.sched.fill(L.slots, L.trees, tree_explor_rule, max_iter_bb, R.fills);
     for (int k = 0; k < nfill; k++) {
@@ -243,11 +184,8 @@ int miosqp_qp_solve_trees_refill(miosqp_qp_engine *e, int32_t B, const double *q
     }
     host_s += wall() - th;
     // (the pinned block was last read by the upload of the boundary before: the drain since then covers it)
-    if (npairs > 0) {
-      HIPCHK(hipMemcpyAsync(d_pairs, h_pairs, sizeof(int) * 3 * (size_t)npairs, hipMemcpyHostToDevice, e->stream));
-      hipLaunchKernelGGL(kls_incumbent<0>, dim3(npairs), dim3(256), 0, e->stream, ds, L.dev, d_pairs, npairs);
-      npairs = 0;
-    }
+    if ((rc = ls_push_incumbents(e, ds, L.dev, d_pairs, h_pairs, npairs)) != 0) return rc;
+    npairs = 0;
     if (nfill > 0) {
       epoch++;
       HIPCHK(hipMemcpyAsync(d_fills, h_fills, sizeof(int) * RF_FILL * (size_t)nfill, hipMemcpyHostToDevice, e->stream));
@@ -292,8 +230,8 @@ int miosqp_qp_solve_trees_refill(miosqp_qp_engine *e, int32_t B, const double *q
       }
       // the chunk's persistent launch was called off before anything was modified (the test decided nothing, nothing was
       // harvested): this chunk again, as launches.  kbp_leave drops every captured chunk, ours included, and clears pad.
-      if (int rc = kbp_leave(e)) return rc;
-      if (int rc = capture_chunk_refill(e, ds, ntiles)) return rc;
+      if ((rc = kbp_leave(e)) != 0) return rc;
+      if ((rc = capture_chunk_refill(e, ds, ntiles)) != 0) return rc;
       continue;  // (nothing to fill: the loop comes straight back to the chunk)
     }
     {
@@ -314,20 +252,9 @@ int miosqp_qp_solve_trees_refill(miosqp_qp_engine *e, int32_t B, const double *q
     for (int k = 0; k < count; k++) {
       const int c = h_list[k];
       const LsRec &g = h_rec[c];
-      Record r;
-      r.ok = g.status == MIOSQP_QP_SOLVED || g.status == MIOSQP_QP_MAX_ITER_REACHED;
-      r.iter = g.iter;
-      r.lower = g.lower;
-      r.int_inf = g.int_inf;
-      r.nextvar = g.nextvar;
-      r.heur_feasible = g.hviol <= 0.0;
-      r.heur_obj = g.hobj;
       int b = -1, slot = -1;
-      const Verdict v = R.sched.absorb(L.slots, L.trees, c, r, &b, &slot);
-      if (v.branch && g.crossed) {
-        g_err = "solve_trees_refill: branching produced l > u (instance " + std::to_string(b) + ")";
-        return MIOSQP_EBOUNDS;
-      }
+      const Verdict v = R.sched.absorb(L.slots, L.trees, c, ls_record(g), &b, &slot);
+      if (v.branch && g.crossed) return ls_crossed(a, b);
       if (v.incumbent) {
         int *pr = h_pairs + 3 * npairs++;
         pr[0] = b;
@@ -344,39 +271,10 @@ int miosqp_qp_solve_trees_refill(miosqp_qp_engine *e, int32_t B, const double *q
     stats->nodes += count;
     host_s += wall() - th;
   }
-  // ---- the incumbents ----
-  double *h_inc = L.stage.data();
-  HIPCHK(hipMemcpyAsync(h_inc, L.dev.inc, sizeof(double) * (size_t)B * n, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipEventRecord(e->ev1, e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
-  HIPCHK(hipGetLastError());
-  float ms = 0;
-  HIPCHK(hipEventElapsedTime(&ms, e->ev0, e->ev1));
-  const double wall_s = wall() - t0;
-  for (int b = 0; b < B; b++) {
-    const Tree &T = L.trees[(size_t)b];
-    const bool have = x_inc0 != nullptr && upper0[b] < miosqp::lockstep::NO_UPPER;
-    info[b].nodes = (int32_t)T.nodes;
-    info[b].osqp_iter = (int32_t)T.iters;
-    info[b].leaves_left = (int32_t)T.open.size();
-    info[b].overflow = 0;
-    info[b].max_leaves = (int32_t)T.max_open;
-    info[b].found = T.found ? 1 : 0;
-    info[b].upper_glob = T.upper;
-    info[b].lower_glob = T.lower_glob(L.slots);
-    info[b].device_time = 1e-3 * ms / B;
-    info[b].run_time = wall_s / B;
-    if (T.found || have) memcpy(x_out + (size_t)b * n, h_inc + (size_t)b * n, sizeof(double) * n);
-    if (stats->finished_at) stats->finished_at[b] = T.finished_at;
-  }
+  if (int rc = ls_finish(a, L, t0, host_s, stats)) return rc;
   stats->chunks = chunk_no;
   stats->iters_all = iters_total;
-  stats->device_time = 1e-3 * ms;
-  stats->run_time = wall_s;
-  stats->host_time = host_s;
   stats->chunk_time = 1e-3 * chunk_ms;
-  e->loop_ms += ms;
-  e->loop_iters += iters_total;
   return 0;
 }
 

@@ -588,11 +588,11 @@ class OSQP(object):
                                     (int(branching_rule), int(sb_candidates), int(sb_max_iter), int(sb_reliability),
                                      float(sb_eps), bool(first_call)))
 
-    def _trees_lockstep(self, q, l, u, x0, y0, upper0, x_inc0, tree_explor_rule, max_iter_bb, capacity, node_hviol, rf,
-                        sb=None):
-        who = "solve_trees_lockstep" if rf is None else "solve_trees_lockstep_rf"
-        if sb is not None:
-            who = "solve_trees_lockstep_sb"
+    # -- what the five tree drivers of the library share on this side ---------------------------------
+    def _trees_args(self, who, q, l, u, x0, y0, upper0, x_inc0, tree_explor_rule, max_iter_bb, capacity):
+        """The drivers' common arguments, normalised: instance-major float64 arrays (ValueError otherwise), upper0 capped
+        at what the library reads as "none", max_iter_bb clamped to 32 bits; x and infos for the call to fill.  `head`
+        is the C argument list up to `capacity`; `keep` holds the arrays it points into."""
         q = np.ascontiguousarray(q, dtype=np.float64)
         B = q.shape[0]
         l, u = np.ascontiguousarray(l, dtype=np.float64), np.ascontiguousarray(u, dtype=np.float64)
@@ -602,19 +602,53 @@ class OSQP(object):
             raise ValueError(who + ": instance-major arrays (B x n, B x M)")
         up = np.minimum(np.ascontiguousarray(upper0, dtype=np.float64).reshape(B), 1.7e308)
         xin = None if x_inc0 is None else np.ascontiguousarray(x_inc0, dtype=np.float64).reshape(B, self.n)
-        x = np.zeros((B, self.n))
-        infos = (_lib.TreeInfo * B)()
         max_iter_bb = 2 ** 31 - 1 if not np.isfinite(max_iter_bb) else int(min(int(max_iter_bb), 2 ** 31 - 1))
-        wcap = max(1, min(max_iter_bb, 65536))
-        width, imax = np.zeros(wcap, dtype=np.int32), np.zeros(wcap, dtype=np.int32)
-        imean, fin = np.zeros(wcap), np.zeros(B, dtype=np.int32)
-        hv = np.full((B, int(node_hviol)), np.nan) if node_hviol > 0 else None
+        head = (self._h, B, _lib.as_d(q), _lib.as_d(l), _lib.as_d(u), _lib.as_d(x0), _lib.as_d(y0), _lib.as_d(up),
+                None if xin is None else _lib.as_d(xin), int(tree_explor_rule), max_iter_bb, int(capacity))
+        return types.SimpleNamespace(B=B, max_iter_bb=max_iter_bb, head=head, keep=(q, l, u, x0, y0, up, xin),
+                                     x=np.zeros((B, self.n)), infos=(_lib.TreeInfo * B)())
+
+    @staticmethod
+    def _trees_refused(rc):
+        """rc 1 of a tree driver: a root with l > u (nothing was queued), or a branching that produced l > u"""
+        if rc == 1:
+            if "branching" in _lib.last_error():
+                raise RuntimeError("branching produced l > u")
+            raise ValueError("Lower bound must be lower than or equal to upper bound")
+
+    @staticmethod
+    def _lockstep_stats_in(t, node_hviol=0):
+        """(LockstepStats, its arrays): per wave (the first 65536), per instance, and node_hviol where asked for"""
+        wcap = max(1, min(t.max_iter_bb, 65536))
+        buf = types.SimpleNamespace(wcap=wcap, width=np.zeros(wcap, dtype=np.int32), imax=np.zeros(wcap, dtype=np.int32),
+                                    imean=np.zeros(wcap), fin=np.zeros(t.B, dtype=np.int32),
+                                    hv=np.full((t.B, int(node_hviol)), np.nan) if node_hviol > 0 else None)
         st = _lib.LockstepStats()
         st.wave_cap = wcap
-        st.wave_width, st.wave_iter_max, st.wave_iter_mean = _lib.as_i(width), _lib.as_i(imax), _lib.as_d(imean)
-        st.finished_at = _lib.as_i(fin)
-        if hv is not None:
-            st.node_hviol, st.node_cap = _lib.as_d(hv), int(node_hviol)
+        st.wave_width, st.wave_iter_max, st.wave_iter_mean = _lib.as_i(buf.width), _lib.as_i(buf.imax), _lib.as_d(buf.imean)
+        st.finished_at = _lib.as_i(buf.fin)
+        if buf.hv is not None:
+            st.node_hviol, st.node_cap = _lib.as_d(buf.hv), int(node_hviol)
+        return st, buf
+
+    @staticmethod
+    def _lockstep_stats(st, buf):
+        """the `stats` namespace of the wave drivers from a filled LockstepStats"""
+        k = min(st.waves, buf.wcap)
+        return types.SimpleNamespace(
+            waves=st.waves, nodes=st.nodes, max_width=st.max_width, grown=st.grown, iters_slowest=st.iters_slowest,
+            iters_all=st.iters_all, device_time=st.device_time, run_time=st.run_time, host_time=st.host_time,
+            width=buf.width[:k].tolist(), iters_max=buf.imax[:k].tolist(), iters_mean=buf.imean[:k].tolist(),
+            finished_at=buf.fin.tolist(), node_hviol=buf.hv)
+
+    def _trees_lockstep(self, q, l, u, x0, y0, upper0, x_inc0, tree_explor_rule, max_iter_bb, capacity, node_hviol, rf,
+                        sb=None):
+        who = "solve_trees_lockstep" if rf is None else "solve_trees_lockstep_rf"
+        if sb is not None:
+            who = "solve_trees_lockstep_sb"
+        t = self._trees_args(who, q, l, u, x0, y0, upper0, x_inc0, tree_explor_rule, max_iter_bb, capacity)
+        B = t.B
+        st, buf = self._lockstep_stats_in(t, node_hviol)
         if sb is not None:
             cnt = [np.zeros(B, dtype=np.int32) for _ in range(2)]
             sb_it = np.zeros(B, dtype=np.int64)
@@ -631,18 +665,13 @@ class OSQP(object):
                 bs.first_k, bs.first_chosen, bs.first_cand = _lib.as_i(first.k), _lib.as_i(first.chosen), _lib.as_i(first.cand)
                 bs.first_status, bs.first_iter, bs.first_lower = _lib.as_i(first.status), _lib.as_i(first.iter), \
                     _lib.as_d(first.lower)
-            rc = self._lib.miosqp_qp_solve_trees_lockstep_sb(
-                self._h, B, _lib.as_d(q), _lib.as_d(l), _lib.as_d(u), _lib.as_d(x0), _lib.as_d(y0), _lib.as_d(up),
-                None if xin is None else _lib.as_d(xin), int(tree_explor_rule), max_iter_bb, int(capacity), sb[0], sb[1], sb[2],
-                sb[3], sb[4], _lib.as_d(x), infos, C.byref(st), C.byref(bs))
+            rc = self._lib.miosqp_qp_solve_trees_lockstep_sb(*t.head, sb[0], sb[1], sb[2], sb[3], sb[4], _lib.as_d(t.x), t.infos,
+                                                             C.byref(st), C.byref(bs))
             if rc == -1 and "solve_trees_lockstep_sb: " in _lib.last_error() and \
                     any(w in _lib.last_error() for w in ("branching_rule", "sb_")):
                 raise ValueError(_lib.last_error())
         elif rf is None:
-            rc = self._lib.miosqp_qp_solve_trees_lockstep(
-                self._h, B, _lib.as_d(q), _lib.as_d(l), _lib.as_d(u), _lib.as_d(x0), _lib.as_d(y0), _lib.as_d(up),
-                None if xin is None else _lib.as_d(xin), int(tree_explor_rule), max_iter_bb, int(capacity), _lib.as_d(x), infos,
-                C.byref(st))
+            rc = self._lib.miosqp_qp_solve_trees_lockstep(*t.head, _lib.as_d(t.x), t.infos, C.byref(st))
         else:
             cnt = [np.zeros(B, dtype=np.int32) for _ in range(4)]
             rf_it = np.zeros(B, dtype=np.int64)
@@ -656,35 +685,25 @@ class OSQP(object):
                                               obj=np.full((B, Kc), np.nan), viol=np.full((B, Kc), np.nan))
                 rs.cand_status, rs.cand_iter = _lib.as_i(first.status), _lib.as_i(first.iter)
                 rs.cand_obj, rs.cand_viol = _lib.as_d(first.obj), _lib.as_d(first.viol)
-            rc = self._lib.miosqp_qp_solve_trees_lockstep_rf(
-                self._h, B, _lib.as_d(q), _lib.as_d(l), _lib.as_d(u), _lib.as_d(x0), _lib.as_d(y0), _lib.as_d(up),
-                None if xin is None else _lib.as_d(xin), int(tree_explor_rule), max_iter_bb, int(capacity), rf[0], rf[1], rf[2],
-                _lib.as_d(x), infos, C.byref(st), C.byref(rs))
+            rc = self._lib.miosqp_qp_solve_trees_lockstep_rf(*t.head, rf[0], rf[1], rf[2], _lib.as_d(t.x), t.infos, C.byref(st),
+                                                             C.byref(rs))
             if rc == -1 and "solve_trees_lockstep_rf: rf_" in _lib.last_error():
                 raise ValueError(_lib.last_error())
         _check(rc, who)
-        if rc == 1:
-            msg = _lib.last_error()
-            if "branching" in msg:
-                raise RuntimeError("branching produced l > u")
-            raise ValueError("Lower bound must be lower than or equal to upper bound")
-        k = min(st.waves, wcap)
-        stats = types.SimpleNamespace(
-            waves=st.waves, nodes=st.nodes, max_width=st.max_width, grown=st.grown, iters_slowest=st.iters_slowest,
-            iters_all=st.iters_all, device_time=st.device_time, run_time=st.run_time, host_time=st.host_time, width=width[:k].tolist(),
-            iters_max=imax[:k].tolist(), iters_mean=imean[:k].tolist(), finished_at=fin.tolist(), node_hviol=hv)
+        self._trees_refused(rc)
+        stats = self._lockstep_stats(st, buf)
         if sb is not None:
             sbs = types.SimpleNamespace(
                 batches=bs.batches, columns=bs.columns, iters_slowest=bs.iters_slowest, device_time=bs.device_time,
                 calls=cnt[0].tolist(), children=cnt[1].tolist(), iters=sb_it.tolist(), first_call=first)
-            return x, list(infos), stats, sbs
+            return t.x, list(t.infos), stats, sbs
         if rf is not None:
             rfs = types.SimpleNamespace(
                 batches=rs.batches, columns=rs.columns, iters_slowest=rs.iters_slowest, device_time=rs.device_time,
                 calls=cnt[0].tolist(), candidates=cnt[1].tolist(), feasible=cnt[2].tolist(), improved=cnt[3].tolist(),
                 iters=rf_it.tolist(), first_call=first)
-            return x, list(infos), stats, rfs
-        return x, list(infos), stats
+            return t.x, list(t.infos), stats, rfs
+        return t.x, list(t.infos), stats
 
     def solve_trees_lockstep_ahead(self, q, l, u, x0, y0, upper0, x_inc0, tree_explor_rule, max_iter_bb, ahead, capacity=0):
         """solve_trees_lockstep (same arrays) with the spare columns of every wave solving open leaves early
@@ -700,50 +719,22 @@ class OSQP(object):
         who = "solve_trees_lockstep_ahead"
         if int(ahead) != ahead or int(ahead) < 1:
             raise ValueError(who + ": ahead must be at least 1")
-        q = np.ascontiguousarray(q, dtype=np.float64)
-        B = q.shape[0]
-        l, u = np.ascontiguousarray(l, dtype=np.float64), np.ascontiguousarray(u, dtype=np.float64)
-        x0, y0 = np.ascontiguousarray(x0, dtype=np.float64), np.ascontiguousarray(y0, dtype=np.float64)
-        if B < 1 or q.shape != (B, self.n) or x0.shape != (B, self.n) or l.shape != (B, self.m) or u.shape != (B, self.m) \
-                or y0.shape != (B, self.m):
-            raise ValueError(who + ": instance-major arrays (B x n, B x M)")
-        up = np.minimum(np.ascontiguousarray(upper0, dtype=np.float64).reshape(B), 1.7e308)
-        xin = None if x_inc0 is None else np.ascontiguousarray(x_inc0, dtype=np.float64).reshape(B, self.n)
-        x = np.zeros((B, self.n))
-        infos = (_lib.TreeInfo * B)()
-        max_iter_bb = 2 ** 31 - 1 if not np.isfinite(max_iter_bb) else int(min(int(max_iter_bb), 2 ** 31 - 1))
-        wcap = max(1, min(max_iter_bb, 65536))
-        width, imax = np.zeros(wcap, dtype=np.int32), np.zeros(wcap, dtype=np.int32)
-        imean, fin = np.zeros(wcap), np.zeros(B, dtype=np.int32)
-        awidth, amand, achunks = (np.zeros(wcap, dtype=np.int32) for _ in range(3))
-        st = _lib.LockstepStats()
-        st.wave_cap = wcap
-        st.wave_width, st.wave_iter_max, st.wave_iter_mean = _lib.as_i(width), _lib.as_i(imax), _lib.as_d(imean)
-        st.finished_at = _lib.as_i(fin)
+        t = self._trees_args(who, q, l, u, x0, y0, upper0, x_inc0, tree_explor_rule, max_iter_bb, capacity)
+        st, buf = self._lockstep_stats_in(t)
+        awidth, amand, achunks = (np.zeros(buf.wcap, dtype=np.int32) for _ in range(3))
         ah = _lib.LockstepAheadStats()
-        ah.wave_cap = wcap
+        ah.wave_cap = buf.wcap
         ah.wave_width, ah.wave_iter_mandatory, ah.wave_chunks = _lib.as_i(awidth), _lib.as_i(amand), _lib.as_i(achunks)
-        rc = self._lib.miosqp_qp_solve_trees_lockstep_ahead(
-            self._h, B, _lib.as_d(q), _lib.as_d(l), _lib.as_d(u), _lib.as_d(x0), _lib.as_d(y0), _lib.as_d(up),
-            None if xin is None else _lib.as_d(xin), int(tree_explor_rule), max_iter_bb, int(capacity), int(ahead),
-            _lib.as_d(x), infos, C.byref(st), C.byref(ah))
+        rc = self._lib.miosqp_qp_solve_trees_lockstep_ahead(*t.head, int(ahead), _lib.as_d(t.x), t.infos, C.byref(st), C.byref(ah))
         _check(rc, who)
-        if rc == 1:
-            msg = _lib.last_error()
-            if "branching" in msg:
-                raise RuntimeError("branching produced l > u")
-            raise ValueError("Lower bound must be lower than or equal to upper bound")
-        k = min(st.waves, wcap)
-        stats = types.SimpleNamespace(
-            waves=st.waves, nodes=st.nodes, max_width=st.max_width, grown=st.grown, iters_slowest=st.iters_slowest,
-            iters_all=st.iters_all, device_time=st.device_time, run_time=st.run_time, host_time=st.host_time, width=width[:k].tolist(),
-            iters_max=imax[:k].tolist(), iters_mean=imean[:k].tolist(), finished_at=fin.tolist(), node_hviol=None)
+        self._trees_refused(rc)
+        k = min(st.waves, buf.wcap)
         ahs = types.SimpleNamespace(
             waves=ah.waves, columns=ah.columns, sent=ah.sent, hits=ah.hits, discarded=ah.discarded, called_off=ah.called_off,
             hit_iters=ah.hit_iters, discarded_iters=ah.discarded_iters, called_off_iters=ah.called_off_iters,
             free_slots=ah.free_slots, slot_cap=ah.slot_cap, width=awidth[:k].tolist(), iter_mandatory=amand[:k].tolist(),
             chunks=achunks[:k].tolist())
-        return x, list(infos), stats, ahs
+        return t.x, list(t.infos), self._lockstep_stats(st, buf), ahs
 
     def solve_trees_refill(self, q, l, u, x0, y0, upper0, x_inc0, tree_explor_rule, max_iter_bb, capacity=0):
         """The trees of solve_trees_lockstep (same arrays) on columns that are refilled between chunks
@@ -756,42 +747,24 @@ class OSQP(object):
         chunks), chunk_time (device seconds inside the chunks), nodes_max_iter and iters_max_iter (the nodes that ended
         MAX_ITER_REACHED and their iterations), chunk_busy (busy columns per chunk, the first 65536) and
         finished_at (per instance, a chunk number)."""
-        q = np.ascontiguousarray(q, dtype=np.float64)
-        B = q.shape[0]
-        l, u = np.ascontiguousarray(l, dtype=np.float64), np.ascontiguousarray(u, dtype=np.float64)
-        x0, y0 = np.ascontiguousarray(x0, dtype=np.float64), np.ascontiguousarray(y0, dtype=np.float64)
-        if B < 1 or q.shape != (B, self.n) or x0.shape != (B, self.n) or l.shape != (B, self.m) or u.shape != (B, self.m) \
-                or y0.shape != (B, self.m):
-            raise ValueError("solve_trees_refill: instance-major arrays (B x n, B x M)")
-        up = np.minimum(np.ascontiguousarray(upper0, dtype=np.float64).reshape(B), 1.7e308)
-        xin = None if x_inc0 is None else np.ascontiguousarray(x_inc0, dtype=np.float64).reshape(B, self.n)
-        x = np.zeros((B, self.n))
-        infos = (_lib.TreeInfo * B)()
-        max_iter_bb = 2 ** 31 - 1 if not np.isfinite(max_iter_bb) else int(min(int(max_iter_bb), 2 ** 31 - 1))
+        t = self._trees_args("solve_trees_refill", q, l, u, x0, y0, upper0, x_inc0, tree_explor_rule, max_iter_bb, capacity)
         ccap = 65536
-        busy, fin = np.zeros(ccap, dtype=np.int32), np.zeros(B, dtype=np.int32)
+        busy, fin = np.zeros(ccap, dtype=np.int32), np.zeros(t.B, dtype=np.int32)
         st = _lib.RefillStats()
         st.chunk_cap = ccap
         st.chunk_busy, st.finished_at = _lib.as_i(busy), _lib.as_i(fin)
-        rc = self._lib.miosqp_qp_solve_trees_refill(
-            self._h, B, _lib.as_d(q), _lib.as_d(l), _lib.as_d(u), _lib.as_d(x0), _lib.as_d(y0), _lib.as_d(up),
-            None if xin is None else _lib.as_d(xin), int(tree_explor_rule), max_iter_bb, int(capacity), _lib.as_d(x), infos,
-            C.byref(st))
+        rc = self._lib.miosqp_qp_solve_trees_refill(*t.head, _lib.as_d(t.x), t.infos, C.byref(st))
         if rc == -1 and "multiple of check_termination" in _lib.last_error():
             raise ValueError("solve_trees_refill: max_iter must be a multiple of check_termination")
         _check(rc, "solve_trees_refill")
-        if rc == 1:
-            msg = _lib.last_error()
-            if "branching" in msg:
-                raise RuntimeError("branching produced l > u")
-            raise ValueError("Lower bound must be lower than or equal to upper bound")
+        self._trees_refused(rc)
         stats = types.SimpleNamespace(
             chunks=st.chunks, nodes=st.nodes, columns=st.columns, grown=st.grown, iters_all=st.iters_all,
             busy=st.col_chunks_busy, total=st.col_chunks_total, device_time=st.device_time, run_time=st.run_time,
             host_time=st.host_time, chunk_time=st.chunk_time, nodes_max_iter=st.nodes_max_iter,
             iters_max_iter=st.iters_max_iter, chunk_busy=busy[:min(st.chunks, ccap)].tolist(),
             finished_at=fin.tolist())
-        return x, list(infos), stats
+        return t.x, list(t.infos), stats
 
     # -- node-at-a-time branch and bound driven from the host in C++ (miosqp_qp_search_*) --------------
     def search_create(self, capacity):

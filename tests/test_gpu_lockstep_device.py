@@ -256,6 +256,51 @@ def test_rounded_point_is_judged_against_the_instances_root(monkeypatch):
         m_.work.solver.close()
 
 
+def _entry_call(s, entry, Q, L, U, up, XI, rule, max_iter_bb):
+    """one of the five tree drivers on B x n / B x M vectors, each with settings under which its own step runs"""
+    ct = int(s.settings.check_termination)
+    zx, zy = np.zeros((len(Q), Q.shape[1])), np.zeros((len(Q), L.shape[1]))
+    args = (Q, L, U, zx, zy, up, XI, rule, max_iter_bb)
+    if entry == "lockstep":
+        return s.solve_trees_lockstep(*args)
+    if entry == "rf":  # K = 4 candidates at every fractional node
+        return s.solve_trees_lockstep_rf(*args, 4, ct, 1)
+    if entry == "sb":  # strong branching, K = 4
+        return s.solve_trees_lockstep_sb(*args, 1, 4, ct, 4, 1e-6)
+    if entry == "ahead":
+        return s.solve_trees_lockstep_ahead(*args, 4)
+    assert int(s.settings.max_iter) % ct == 0
+    return s.solve_trees_refill(*args)
+
+
+@pytest.mark.parametrize("entry", ["lockstep", "rf", "sb", "ahead", "refill"])
+def test_a_branching_that_crosses_is_refused_and_leaves_no_trace(entry):
+    """The error exit in the middle of a call.  Instance 1 gets [0.25, 0.75] at every integer position: its root
+    relaxation is fractional wherever it branches and both children have l > u.  The call is refused from inside the
+    first wave (chunk), after trees, slots and the driver's own lists have been written; the next call on the same
+    engine must be the call of an engine that never saw the refusal, bit for bit."""
+    pr = _problem()
+    inst = _instances(pr)[:3]
+    mdl, fresh = _model(pr, 1, 0.1), _model(pr, 1, 0.1)
+    m = mdl.work.data.m
+    Q, L, U, up, XI = _vectors(mdl, inst)
+    Lb, Ub = L.copy(), U.copy()
+    Lb[1, m:], Ub[1, m:] = 0.25, 0.75
+    with pytest.raises(RuntimeError, match="branching produced l > u"):
+        _entry_call(mdl.work.solver, entry, Q, Lb, Ub, up, XI, 1, 1000)
+    got = _entry_call(mdl.work.solver, entry, Q, L, U, up, XI, 1, 1000)
+    want = _entry_call(fresh.work.solver, entry, Q, L, U, up, XI, 1, 1000)
+    for k, (g, w) in enumerate(zip(got[1], want[1])):
+        print("%s, instance %d: %d nodes %d iterations %.12g, %d leaves left | fresh engine %d %d %.12g %d"
+              % (entry, k, g.nodes, g.osqp_iter, g.upper_glob, g.leaves_left, w.nodes, w.osqp_iter, w.upper_glob, w.leaves_left))
+    for k, (g, w) in enumerate(zip(got[1], want[1])):  # (found and leaves_left are what the status is made of)
+        assert (g.found, g.leaves_left, g.nodes, g.osqp_iter, g.upper_glob) == (w.found, w.leaves_left, w.nodes, w.osqp_iter, w.upper_glob), k
+        assert g.nodes > 5
+    np.testing.assert_array_equal(got[0], want[0])
+    for m_ in (mdl, fresh):
+        m_.work.solver.close()
+
+
 def test_edges_leave_the_engine_as_it_was():
     from miosqp_amd import bnb
     pr = _problem()
