@@ -501,6 +501,19 @@ typedef struct miosqp_setup_models_stats {
  * a column -- the launch copies entries where miosqp_qp_setup sums duplicates, so such a model goes to miosqp_qp_setup).  A pivot of the LDL^T that is not positive or not finite:
  * MIOSQP_EFACTOR, the text names the model and the pivot.  After any error everything of the call has been released. */
 int miosqp_qp_setup_models(int32_t B, const miosqp_setup_model *models, miosqp_qp_engine **out, miosqp_setup_models_stats *stats);
+/* miosqp_qp_setup_models with settings->rho_auto = 1 accepted per model (0 and 1 may be mixed in one call; when no model
+ * asks for it the call IS miosqp_qp_setup_models): the rho-once recipe of miosqp_qp_setup (engine.hip: for n + M <= 400 two
+ * complete set-ups and RHO_ONCE_ITERS = 50 iterations on a throw-away engine; oracle/qp_oracle.c: rho_once) becomes a stage
+ * of the launch (k_setup_models_auto).  The workgroup that builds the model runs the 50 iterations from x = z = y = 0 on the
+ * factor at the starting rho it holds in LDS, applies the rule (rho_estimate, rounded to two digits by rho_round2) and,
+ * where the rule moves rho, builds the factor again at the chosen value; every product and the panel's values are those of
+ * the chosen rho.  Still one upload, one launch, one download, one synchronisation.  The chosen rho agrees with
+ * miosqp_qp_setup's wherever the rule's value is not within rounding of a two-digit boundary; the engine reports it through
+ * miosqp_qp_get_rho and keeps rho_auto = 1 in its settings.  Every shape miosqp_qp_setup_models takes is taken.  A pivot that
+ * is not positive in either factor fails the whole call with MIOSQP_EFACTOR; for the second factor the text names the
+ * chosen rho as well. */
+int miosqp_qp_setup_models_auto(int32_t B, const miosqp_setup_model *models, miosqp_qp_engine **out,
+                                miosqp_setup_models_stats *stats);
 /* 1 when the launch takes a model of this shape under these settings and this environment, else 0: n + M <= 192 with the
  * kernel's LDS within 160 KB, and everything under which miosqp_qp_setup would choose the LDS-resident form with the product
  * form and the explicit inverse at a fixed rho -- not rho_auto, coop = 1, resident = 0, fold = 0, setup_on_device = 1,
@@ -515,6 +528,10 @@ int64_t miosqp_qp_setup_group(miosqp_qp_engine *e);
  * 3 f_Atd (n x ldm)   4 f_Pd (n x ldn); and the scaled vectors of the problem as the solvers read them: 5 q (n x 1)
  * 6 l (M x 1)   7 u (M x 1).  MIOSQP_EUNSUPPORTED for 0..4 on an engine without the product form. */
 int miosqp_qp_debug_product_form(miosqp_qp_engine *e, int32_t which, double *out, int64_t capacity, int32_t *rows, int32_t *ld);
+
+/* debug: the values of the factor's panel L21 = -rho Abar as stored (padding included).  which: 0 by variable and 1 by
+ * constraint as they lie in device memory, 2 and 3 the host's mirror of the two.  out == NULL: only *count is set. */
+int miosqp_qp_debug_panel(miosqp_qp_engine *e, int32_t which, double *out, int64_t capacity, int64_t *count);
 
 /* ---- B trees in lock step, driven from the host in C++ on device-resident leaves -----------------------
  * miosqp_qp_solve_trees for problems of any size: the B instances of the reference's MPC pattern

@@ -161,6 +161,8 @@ SYMBOLS = {
     "miosqp_qp_solve_trees_models": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), dpp, dpp, dpp, dpp, dpp, dp, dpp, ip, ip, dpp,
                                                C.POINTER(TreeInfo), C.POINTER(ModelsStats)]),
     "miosqp_qp_setup_models": (C.c_int, [C.c_int32, C.POINTER(SetupModel), C.POINTER(C.c_void_p), C.POINTER(SetupModelsStats)]),
+    "miosqp_qp_setup_models_auto": (C.c_int, [C.c_int32, C.POINTER(SetupModel), C.POINTER(C.c_void_p), C.POINTER(SetupModelsStats)]),
+    "miosqp_qp_debug_panel": (C.c_int, [C.c_void_p, C.c_int32, dp, C.c_int64, C.POINTER(C.c_int64)]),
     "miosqp_qp_setup_models_eligible": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(Settings)]),
     "miosqp_qp_setup_groups_live": (C.c_int, []),
     "miosqp_qp_setup_group": (C.c_int64, [C.c_void_p]),

@@ -1577,14 +1577,17 @@ def solve_models(models, instances=None, info=None):
     return out
 
 
-def _setup_models_own_reason(be, data, qp_settings):
+def _setup_models_own_reason(be, data, qp_settings, rho_auto_in_launch=False):
     """why `setup_models` leaves a model to `MIOSQP.setup` (None: it goes into the launch)"""
     if not hasattr(be, 'setup_models') or not hasattr(be, 'setup_models_eligible'):
         return 'backend without the one-launch set-up'
     if data.n_int == 0:
         return 'n_int == 0'
     if isinstance(qp_settings.get('rho'), str):
-        return 'rho="auto"'
+        if not rho_auto_in_launch:
+            return 'rho="auto"'
+        # the launch chooses rho itself; everything else about the model is judged as at a fixed rho
+        qp_settings = {k: v for k, v in qp_settings.items() if k != 'rho'}
     n, M = data.n, data.A.shape[0]
     if not be.setup_models_eligible(n, M, {}):  # (the library's size rule, asked with default settings)
         return 'n + M = %d: beyond one workgroup of the launch' % (n + M)
@@ -1595,7 +1598,7 @@ def _setup_models_own_reason(be, data, qp_settings):
     return None
 
 
-def setup_models(problems, settings, qp_settings, info=None, backend=None):
+def setup_models(problems, settings, qp_settings, info=None, backend=None, rho_auto=None):
     """Set up several DIFFERENT MIQP models -- each with its own P and A -- with ONE launch for the dense set-up of all of
     them (`qp.setup_models`, miosqp_qp_setup_models: one workgroup per model builds the Schur complement, its LDL^T, the
     triangular inverse, the product form, the explicit inverse and its guard; the engines share one stream, one device
@@ -1610,13 +1613,20 @@ def setup_models(problems, settings, qp_settings, info=None, backend=None):
     the engine form the launch builds (LDS-resident, product form, explicit inverse); every other model (the CPU oracle
     backend among them) is set up in its place by `MIOSQP.setup`.
 
+    rho_auto: None -- a model with rho="auto" is set up in its place, with MIOSQP.setup's two set-ups; "device" -- such a
+    model goes into the launch where everything else about it is eligible, and the workgroup that builds it chooses rho
+    (miosqp_qp_setup_models_auto: the probing iterations, the rule and the second factor are stages of the one launch).
+    On a backend without that entry (the CPU oracle) such models are still set up in place.  Any other value: ValueError.
+
     ValueError before anything is queued, with the positions named: an empty list, a wrong number of settings, l > u, a P
     of the wrong shape.  A pivot that is not positive raises what `MIOSQP.setup` raises, with the position added; nothing
     of the call is left behind.
 
-    info: a dict that is filled with batched (positions), own ({position: why}), launches, device_time, arena_bytes and
-    host_time (seconds of the call outside the library's one)."""
+    info: a dict that is filled with batched (positions), own ({position: why}), launches, device_time, arena_bytes,
+    host_time (seconds of the call outside the library's one) and rho (the rho in use per position)."""
     t_call = time()
+    if rho_auto not in (None, 'device'):
+        raise ValueError('setup_models: rho_auto must be None or "device", not %r' % (rho_auto,))
     problems = list(problems)
     B = len(problems)
     if B == 0:
@@ -1654,7 +1664,7 @@ def setup_models(problems, settings, qp_settings, info=None, backend=None):
     be = backend if backend is not None else _default_backend()
     own, batched = {}, []
     for k in range(B):
-        why = _setup_models_own_reason(be, datas[k], qp_settings[k])
+        why = _setup_models_own_reason(be, datas[k], qp_settings[k], rho_auto == 'device')
         if why is None:
             batched.append(k)
         else:
@@ -1673,7 +1683,10 @@ def setup_models(problems, settings, qp_settings, info=None, backend=None):
                 desc.append(md)
             t0 = time()
             try:
-                solvers, stats = be.setup_models(desc)
+                if rho_auto == 'device' and any(isinstance(md['settings'].get('rho'), str) for md in desc):
+                    solvers, stats = be.setup_models(desc, rho_auto_in_launch=True)
+                else:
+                    solvers, stats = be.setup_models(desc)
             except RuntimeError as ex:
                 import re
                 hit = re.search(r'\(model (\d+)', str(ex))
@@ -1698,6 +1711,7 @@ def setup_models(problems, settings, qp_settings, info=None, backend=None):
                 s.close()
         raise
     if info is not None:
+        rho = [float(m.work.solver.rho()) for m in out]
         info.update(batched=list(batched), own=dict(own), launches=launches, device_time=device_time, arena_bytes=arena_bytes,
-                    host_time=(time() - t_call) - lib_time)
+                    host_time=(time() - t_call) - lib_time, rho=rho)
     return out

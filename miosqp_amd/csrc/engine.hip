@@ -268,7 +268,7 @@ namespace {
 // the dynamic-LDS ceiling of a kernel is a property of (process, device, kernel): raised to the chip's 160 KB once instead of
 // at every set-up (the call costs ~40 us, a fifth of a small problem's set-up)
 hipError_t lds_limit_once(const void *fn, int which) {
-  static bool done[15][64] = {};  // (one row per kernel: 0 .. 13 as before, 14: k_setup_models)
+  static bool done[16][64] = {};  // (one row per kernel: 0 .. 13 as before, 14: k_setup_models, 15: k_setup_models_auto)
   int dev = 0;
   hipError_t rc = hipGetDevice(&dev);
   if (rc != hipSuccess) return rc;
@@ -2241,7 +2241,11 @@ int miosqp_qp_debug_iterate(miosqp_qp_engine *e, int32_t k, double *x, double *z
 }
 
 int miosqp_qp_setup_models(int32_t B, const miosqp_setup_model *models, miosqp_qp_engine **out, miosqp_setup_models_stats *stats) {
-  return setup_models_run(B, models, out, stats);
+  return setup_models_run(B, models, out, stats, false);
+}
+
+int miosqp_qp_setup_models_auto(int32_t B, const miosqp_setup_model *models, miosqp_qp_engine **out, miosqp_setup_models_stats *stats) {
+  return setup_models_run(B, models, out, stats, true);
 }
 
 int miosqp_qp_setup_models_eligible(int32_t n, int32_t M, const miosqp_qp_settings *s) {
@@ -2257,6 +2261,29 @@ int miosqp_qp_setup_groups_live(void) {
 }
 
 int64_t miosqp_qp_setup_group(miosqp_qp_engine *e) { return e && e->group ? e->group->id : 0; }
+
+// debug: the panel's values (L21 = -rho Abar as stored, padding included) from the device or from the host's mirror
+int miosqp_qp_debug_panel(miosqp_qp_engine *e, int32_t which, double *out, int64_t capacity, int64_t *count) {
+  if (!e || !count || which < 0 || which > 3) {
+    g_err = "debug_panel: bad argument";
+    return MIOSQP_EARG;
+  }
+  ENTER(e);
+  const std::vector<double> &mirror = (which & 1) ? e->fa.panel_by_con.val : e->fa.panel_by_var.val;
+  *count = (int64_t)mirror.size();
+  if (!out) return 0;
+  if (capacity < *count) {
+    g_err = "debug_panel: the output holds fewer than count values";
+    return MIOSQP_EARG;
+  }
+  if (which >= 2) {
+    if (*count) memcpy(out, mirror.data(), sizeof(double) * mirror.size());
+    return 0;
+  }
+  HIPCHK(hipStreamSynchronize(e->stream));
+  if (*count) HIPCHK(hipMemcpy(out, (which & 1) ? e->d.pc_L : e->d.pv_L, sizeof(double) * mirror.size(), hipMemcpyDeviceToHost));
+  return 0;
+}
 
 // debug: one array of the product form copied to the host as it lies in device memory (beside miosqp_qp_debug_factor)
 int miosqp_qp_debug_product_form(miosqp_qp_engine *e, int32_t which, double *out, int64_t capacity, int32_t *rows, int32_t *ld) {

@@ -120,7 +120,10 @@ void stage_vec(char *slab, const miosqp::setup_models::Slot &s, int part, const 
   if (count) memcpy(slab + s.part[part].off, src, count * sizeof(T));
 }
 
-int setup_models_run(int32_t B, const miosqp_setup_model *ms, miosqp_qp_engine **out, miosqp_setup_models_stats *stats) {
+// rho_auto_in_launch (miosqp_qp_setup_models_auto): models with settings->rho_auto = 1 are taken, and when there is one
+// the launch is k_setup_models_auto
+int setup_models_run(int32_t B, const miosqp_setup_model *ms, miosqp_qp_engine **out, miosqp_setup_models_stats *stats,
+                     bool rho_auto_in_launch) {
   namespace sm = miosqp::setup_models;
   static_assert(sizeof(Ctrl) <= sm::CTRL_BYTES, "Ctrl fits its place in the arena and the slab");
   // ---- refused before anything is queued ----
@@ -129,7 +132,7 @@ int setup_models_run(int32_t B, const miosqp_setup_model *ms, miosqp_qp_engine *
     if (B >= 1 && ms)
       for (int b = 0; b < B; b++) av.push_back(setup_args_of(ms[b]));
     std::string err;
-    if (int rc = sm::check_args(B, ms ? av.data() : nullptr, out, stats, err)) {
+    if (int rc = sm::check_args(B, ms ? av.data() : nullptr, out, stats, err, rho_auto_in_launch)) {
       g_err = err;
       return rc;
     }
@@ -167,6 +170,8 @@ int setup_models_run(int32_t B, const miosqp_setup_model *ms, miosqp_qp_engine *
     t_last = now;
   };
   for (int b = 0; b < B; b++) out[b] = nullptr;
+  bool any_auto = false;
+  for (int b = 0; b < B; b++) any_auto = any_auto || ms[b].settings->rho_auto != 0;
   const int64_t made0[3] = {g_made_device_mallocs, g_made_host_mallocs, g_made_streams};
   std::vector<miosqp_qp_engine *> eng((size_t)B, nullptr);
   SetupGroup *grp = nullptr;
@@ -212,7 +217,8 @@ int setup_models_run(int32_t B, const miosqp_setup_model *ms, miosqp_qp_engine *
     e->nnzA = m.Ap[m.n];
     e->A_raw.assign(m.Ax, m.Ax + m.Ap[m.n]);
     e->nnzPtriu = (int64_t)e->sc.Pi.size();
-    sh[(size_t)b] = sm::Shape{m.n, m.M, f.panel_by_var.idx.size(), f.panel_by_con.idx.size(), f.Pbar.idx.size(), f.Praw.idx.size()};
+    sh[(size_t)b] = sm::Shape{m.n, m.M, f.panel_by_var.idx.size(), f.panel_by_con.idx.size(), f.Pbar.idx.size(), f.Praw.idx.size(),
+                              m.settings->rho_auto ? 1 : 0};
   }
   const sm::Plan P = sm::plan(sh, sizeof(SetupModel));
   tick("host: equilibration + packed rows");
@@ -322,6 +328,12 @@ int setup_models_run(int32_t B, const miosqp_setup_model *ms, miosqp_qp_engine *
     io.W = arena_at<double>(dv, s, sm::W_); io.Kc = arena_at<double>(dv, s, sm::KC);
     io.rec = reinterpret_cast<sm::Record *>(dv + s.rec);
     t.ctrl = d.ctrl;
+    sm::Auto &au = t.au;
+    au.on = st->rho_auto ? 1 : 0;
+    au.nv = (int)f.panel_by_var.val.size(); au.nc = (int)f.panel_by_con.val.size();
+    au.alpha = d.alpha;
+    au.q = d.q; au.pv_At = d.pv_At;
+    au.pv_L = arena_at<double>(dv, s, sm::PV_L); au.pc_L = arena_at<double>(dv, s, sm::PC_L);
     // the engine joins the group: its pool is the rest of its slice, its stream the group's, its events its own
     e->pool_base = dv + s.part[sm::RESERVE].off;
     e->pool_cap = s.part[sm::RESERVE].bytes;
@@ -351,26 +363,53 @@ int setup_models_run(int32_t B, const miosqp_setup_model *ms, miosqp_qp_engine *
   }
   tick("host: upload image, table, events");
   // ---- one upload, one launch, one download, one synchronisation ----
-  SMCHK(lds_limit_once((const void *)k_setup_models, 14));
+  if (any_auto) SMCHK(lds_limit_once((const void *)k_setup_models_auto, 15));
+  else SMCHK(lds_limit_once((const void *)k_setup_models, 14));
   miosqp_qp_engine *e0 = eng[0];
   SMCHK(hipEventRecord(e0->ev0, grp->stream));
   SMCHK(hipMemcpyAsync(dv, hs, P.up_bytes, hipMemcpyHostToDevice, grp->stream));
-  hipLaunchKernelGGL(k_setup_models, dim3((unsigned)B), dim3(sm::THREADS), P.lds_bytes, grp->stream,
-                     reinterpret_cast<const SetupModel *>(dv));
+  if (any_auto)
+    hipLaunchKernelGGL(k_setup_models_auto, dim3((unsigned)B), dim3(sm::THREADS), P.lds_bytes, grp->stream,
+                       reinterpret_cast<const SetupModel *>(dv));
+  else
+    hipLaunchKernelGGL(k_setup_models, dim3((unsigned)B), dim3(sm::THREADS), P.lds_bytes, grp->stream,
+                       reinterpret_cast<const SetupModel *>(dv));
   SMCHK(hipGetLastError());
   SMCHK(hipMemcpyAsync(hs + P.pin_rec, dv + P.rec_off, P.rec_bytes, hipMemcpyDeviceToHost, grp->stream));
   SMCHK(hipEventRecord(e0->ev1, grp->stream));
   SMCHK(hipStreamSynchronize(grp->stream));
   float ms_dev = 0;
   SMCHK(hipEventElapsedTime(&ms_dev, e0->ev0, e0->ev1));
-  tick("upload, k_setup_models, records back");
+  tick(any_auto ? "upload, k_setup_models_auto, records back" : "upload, k_setup_models, records back");
   const sm::Record *rec = reinterpret_cast<const sm::Record *>(hs + P.pin_rec);
   for (int b = 0; b < B; b++)
     if (rec[b].bad_pivot) {
       g_err = "KKT factorisation: non-positive pivot in the reduced Hessian (P not PSD?) (model " + std::to_string(b) + ", pivot " +
-              std::to_string(rec[b].pivot) + ")";
+              std::to_string(rec[b].pivot);
+      if (rec[b].bad_pivot == 2) {  // the factor at the rho the launch chose (the per-model two-set-up path fails there too)
+        char at[64];
+        snprintf(at, sizeof at, ", at the rho chosen at set-up %.17g", rec[b].rho);
+        g_err += at;
+      }
+      g_err += ")";
       return fail(MIOSQP_EFACTOR);
     }
+  // ---- rho chosen in the launch: the host's mirror follows (st, Dev, the factor's rho and the panel's values, formed
+  //      with the expression the kernel used, which is build_factor(reuse_rows)'s) ----
+  for (int b = 0; b < B; b++) {
+    if (!ms[b].settings->rho_auto) continue;
+    miosqp_qp_engine *e = eng[(size_t)b];
+    const double rho = rec[b].rho;
+    e->st.rho_auto = 1;
+    if (rho == e->st.rho) continue;
+    e->st.rho = rho;
+    e->d.rho = rho;
+    e->d.rho_inv = 1.0 / rho;
+    miosqp::Factor &f = e->fa;
+    f.rho = rho;
+    for (size_t k = 0; k < f.At_val.size(); k++) f.panel_by_var.val[k] = f.At_val[k] == 0.0 ? 0.0 : -rho * f.At_val[k];
+    for (size_t k = 0; k < f.A_val.size(); k++) f.panel_by_con.val[k] = f.A_val[k] == 0.0 ? 0.0 : -rho * f.A_val[k];
+  }
   // ---- the engines: the fields miosqp_qp_setup sets for resident + fold + W.  (From here on the slab is staging.) ----
   int cus = 0;
   {

@@ -32,9 +32,16 @@ struct Args {
   const double *l_root = nullptr, *u_root = nullptr;
 };
 
-// settings under which miosqp_qp_setup would choose resident + fold + W at a fixed rho for an eligible shape
-inline bool eligible_settings(const Args &a) {
-  return a.rho_auto == 0 && a.coop != 1 && a.resident != 0 && a.fold != 0 && a.setup_on_device != 1;
+// settings under which miosqp_qp_setup would choose resident + fold + W at a fixed rho for an eligible shape;
+// rho_auto_in_launch (miosqp_qp_setup_models_auto): rho_auto = 1 is taken too, the launch chooses rho itself
+inline bool eligible_settings(const Args &a, bool rho_auto_in_launch = false) {
+  return (a.rho_auto == 0 || (rho_auto_in_launch && a.rho_auto == 1)) && a.coop != 1 && a.resident != 0 && a.fold != 0 &&
+         a.setup_on_device != 1;
+}
+// the size rule of the launch that chooses rho: the probing iterations' vectors fit the LDS as well.  The same set of
+// shapes as eligible_shape (the stand-alone program under tests/ walks the whole grid).
+inline bool eligible_shape_auto(int n, int M) {
+  return eligible_shape(n, M) && lds_doubles_auto(n, M) * sizeof(double) <= LDS_LIMIT;
 }
 
 // The launch writes the dense copies of Abar and Pbar entry by entry where the per-model set-up sums what a matrix stores
@@ -47,7 +54,8 @@ inline bool csc_strictly_ascending(int cols, const int32_t *ptr, const int32_t *
 }
 
 // 0, or the error code with `err` naming the model's position
-inline int check_args(int32_t B, const Args *a, const void *out, const void *stats, std::string &err) {
+inline int check_args(int32_t B, const Args *a, const void *out, const void *stats, std::string &err,
+                      bool rho_auto_in_launch = false) {
   const std::string who = "setup_models: ";
   if (B < 1) {
     err = who + "B must be at least 1";
@@ -85,9 +93,11 @@ inline int check_args(int32_t B, const Args *a, const void *out, const void *sta
         err = who + "lower bound above upper bound" + at;
         return ERR_ARG;
       }
-    if (!eligible_shape(m.n, m.M) || !eligible_settings(m)) {
+    if (!eligible_shape(m.n, m.M) || !eligible_settings(m, rho_auto_in_launch) ||
+        (rho_auto_in_launch && m.rho_auto && !eligible_shape_auto(m.n, m.M))) {
       err = who + "the launch does not take this model: n + M <= " + std::to_string(MAX_NM) +
-            ", a fixed rho, and settings that lead to the LDS-resident form with the explicit inverse" + at;
+            (rho_auto_in_launch ? ", rho fixed or rho_auto = 1" : ", a fixed rho") +
+            ", and settings that lead to the LDS-resident form with the explicit inverse" + at;
       return ERR_UNSUPPORTED;
     }
   }
@@ -98,6 +108,7 @@ struct Shape {
   int n = 0, M = 0;
   size_t nv = 0, nc = 0, npb = 0, npr = 0;  // lengths of the packed rows as stored (padding included): by variable, by
                                             // constraint, Pbar, Praw
+  int rho_auto = 0;                         // 1: the launch chooses this model's rho (LDS for the probing iterations)
 };
 
 // the arrays of one model, in the order they lie in the arena
@@ -180,7 +191,7 @@ inline Plan plan(const std::vector<Shape> &sh, size_t entry_bytes) {
       P.slot[b].part[k] = Span{at, one[k]};
       at += one[k];
     }
-    const size_t lds = lds_doubles(sh[b].n, sh[b].M) * sizeof(double);
+    const size_t lds = (sh[b].rho_auto ? lds_doubles_auto(sh[b].n, sh[b].M) : lds_doubles(sh[b].n, sh[b].M)) * sizeof(double);
     if (lds > P.lds_bytes) P.lds_bytes = lds;
   }
   P.up_bytes = at;

@@ -147,10 +147,14 @@ def setup_groups_live():
     return int(_lib.load().miosqp_qp_setup_groups_live())
 
 
-def setup_models(models):
+def setup_models(models, rho_auto_in_launch=False):
     """The set-up of several DIFFERENT small models in ONE launch (miosqp_qp_setup_models): the dense part of every
     model -- Schur complement, LDL^T, triangular inverse, product form, explicit inverse, its guard -- by one workgroup
     per model; the engines share one stream, one device arena and one pinned slab.
+
+    rho_auto_in_launch=True (miosqp_qp_setup_models_auto): models whose settings say rho="auto" are taken too, mixed with
+    fixed-rho ones as they come; the workgroup that builds such a model runs the fifty probing iterations, applies the
+    rule and builds the factor again at the rho it chose (OSQP.rho() reports it).  Without it such a model is refused.
 
     models: dicts with P, q, A, l, u (as OSQP.setup takes them), settings (a dict of OSQP.setup's keywords), and
     optionally i_idx with m_orig (set_integer_rows is applied) and root = (l_root, u_root, eps_int_feas, eps_lin)
@@ -192,7 +196,8 @@ def setup_models(models):
         shapes.append((n, m, s))
     hs = (C.c_void_p * max(B, 1))()
     stats = _lib.SetupModelsStats()
-    _check(lib.miosqp_qp_setup_models(B, desc, hs, C.byref(stats)), "setup_models")
+    entry = lib.miosqp_qp_setup_models_auto if rho_auto_in_launch else lib.miosqp_qp_setup_models
+    _check(entry(B, desc, hs, C.byref(stats)), "setup_models")
     out = []
     for k, (n, m, s) in enumerate(shapes):
         g = OSQP()
@@ -933,6 +938,15 @@ class OSQP(object):
         if which == 0:
             return raw[:, 0].copy(), raw
         return raw[:, :rows.value].copy(), raw
+
+    def debug_panel(self, which):
+        """The values of the factor's panel L21 = -rho Abar as stored, padding included (miosqp_qp_debug_panel): 0 by
+        variable and 1 by constraint as they lie in device memory, 2 and 3 the host's mirror of the two."""
+        count = C.c_int64()
+        _check(self._lib.miosqp_qp_debug_panel(self._h, int(which), None, 0, C.byref(count)), "debug_panel")
+        out = np.empty(count.value)
+        _check(self._lib.miosqp_qp_debug_panel(self._h, int(which), _lib.as_d(out), out.size, C.byref(count)), "debug_panel")
+        return out
 
     def debug_product_form(self, which):
         """One array of the product form read back (miosqp_qp_debug_product_form): 0 f_rows (n x (M + n): [-G | strict
