@@ -449,6 +449,54 @@ int miosqp_qp_solve_trees_models(int32_t B, miosqp_qp_engine *const *engines, co
                                  const int32_t *max_iter_bb, double *const *x_out, miosqp_tree_info *info,
                                  miosqp_models_stats *stats);
 
+/* ---- polishes of DIFFERENT models in one launch -------------------------------------------------------
+ * The polish of the "own P and A per MIQP" pattern: the reference sets up, solves and polishes one model per MIQP
+ * (miosqp/solver.py:174-212 per model; `polish` reaches OSQP through qp_settings, miosqp/workspace.py:67-68), and
+ * miosqp_qp_solve_trees_models returns B incumbents of B different engines from one call.  This entry polishes them in
+ * one call as well: workgroup b runs model b exactly as miosqp_qp_polish_many(engines[b], 1, q[b], ...) would with the
+ * same y -- info[b], x_out[b], y_out[b] and cls_out[b] bit for bit, whatever B is and wherever the model sits in the
+ * list (the kernel's sums depend on (n, M) and the data alone); only device_time / run_time differ: in every record
+ * they are the call's totals.  OSQP has NO batched polish and no repair loop.
+ * One pointer per model, because shapes differ: q[b], x[b], x_out[b] n_b doubles; l[b], u[b], y[b], y_out[b] M_b;
+ * cls_out[b] M_b bytes, the class of every row in the final set (-1 lower-active, 1 upper-active, 0 inactive), and
+ * cls_out or any cls_out[b] may be NULL; delta, refine_iter, repair_iter one per model.  q[b] NULL: engines[b]'s current
+ * linear cost.  y[b] NULL: a tree returns no multipliers, so the workgroup guesses them from the z = A x it computes
+ * anyway, before it classifies -- y_r = 0 where l_r == u_r or both bounds are at or beyond +-1e30, otherwise -tau where
+ * z_r - l_r < u_r - z_r, otherwise +tau (needs tau > 0) --, and that guess is the y a rejection returns.
+ * One upload, ONE launch, one download and one synchronisation, all on engines[0]'s stream; work queued on the other
+ * engines' streams is waited for first.  No engine's q, bounds, iterates or polish scratch is touched, and none is
+ * built: nothing is allocated per engine.  The table of per-workgroup arguments, the unscaled rows of A by constraint,
+ * the vectors and the output records are one arena [table | per model: rows of A, q, l, u, x, y | per model: record]
+ * taken from the device pool of engines[0], with a pinned host mirror -- the arena of miosqp_qp_solve_trees_models, with
+ * the same ownership: it belongs to that engine, is reused and grown by later calls that have it first, and is released
+ * by its miosqp_qp_cleanup.  Nothing of a call outlives it in any other engine, so the engines may be cleaned up in any
+ * order between calls.
+ * Refused before anything is queued, with a last_error text naming the model: B < 1 or a NULL argument, an engine
+ * listed twice, delta <= 0, refine_iter outside 0..10, repair_iter outside 0..20, a NaN in q, l, u, x or y, y[b] NULL
+ * with tau not positive, engines on different devices, an engine with streaming chunks in flight (MIOSQP_EARG); l > u
+ * (MIOSQP_EBOUNDS); a model whose reduced system and rows of A exceed one workgroup's 160 KB of LDS -- every
+ * n + M <= 192 fits, which is everything miosqp_qp_solve_trees_models takes --, or whose rows on the device do not
+ * follow the set-up's order (MIOSQP_EUNSUPPORTED: the caller polishes that model on its own). */
+typedef struct miosqp_polish_models_stats {
+  int32_t launches;         /* 1; 0 after a refusal that came later than the argument checks */
+  int32_t models;           /* B */
+  int64_t lds_bytes;        /* dynamic LDS of the launch: the largest need among its models */
+  int64_t arena_bytes;      /* what this call uses of the arena */
+  double device_time;       /* seconds between the events around upload, launch and download */
+  double run_time;          /* wall seconds of the call once the arena exists */
+  double upload_time, launch_time, download_time; /* device_time by part: the events after the upload and after the launch */
+} miosqp_polish_models_stats;
+
+int miosqp_qp_polish_models(int32_t B, miosqp_qp_engine *const *engines, const double *const *q, const double *const *l,
+                            const double *const *u, const double *const *x, const double *const *y, double tau,
+                            const double *delta, const int32_t *refine_iter, const int32_t *repair_iter, double *const *x_out,
+                            double *const *y_out, int8_t *const *cls_out, miosqp_polish_repair_info *info,
+                            miosqp_polish_models_stats *stats);
+
+/* 1 when miosqp_qp_polish_models takes this engine's sizes (the reduced system and the rows of A within one workgroup's
+ * 160 KB of LDS), 0 otherwise or for a NULL engine: what a caller asks before it puts a model into the list. */
+int miosqp_qp_polish_models_fits(miosqp_qp_engine *e);
+
 /* ---- set-up of many small models in ONE launch -----------------------------------------------------------
  * What the reference does once per MIQP with osqp.OSQP().setup() (/root/reference/miosqp/workspace.py:63-68), for B
  * models with their own P and A at once: the equilibration and the row packing stay on the host, per model, exactly as

@@ -42,6 +42,12 @@ class ModelsStats(C.Structure):
                 ("lds_bytes", C.c_int64), ("device_time", C.c_double), ("run_time", C.c_double)]
 
 
+class PolishModelsStats(C.Structure):
+    _fields_ = [("launches", C.c_int32), ("models", C.c_int32), ("lds_bytes", C.c_int64), ("arena_bytes", C.c_int64),
+                ("device_time", C.c_double), ("run_time", C.c_double), ("upload_time", C.c_double),
+                ("launch_time", C.c_double), ("download_time", C.c_double)]
+
+
 class SetupModel(C.Structure):
     _fields_ = [("n", C.c_int32), ("M", C.c_int32), ("Pp", ip), ("Pi", ip), ("Px", dp), ("Ap", ip), ("Ai", ip), ("Ax", dp),
                 ("q", dp), ("l", dp), ("u", dp), ("settings", C.POINTER(Settings)), ("n_int", C.c_int32), ("m_orig", C.c_int32),
@@ -160,6 +166,9 @@ SYMBOLS = {
     "miosqp_qp_tree_form": (C.c_int, [C.c_void_p]),
     "miosqp_qp_solve_trees_models": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), dpp, dpp, dpp, dpp, dpp, dp, dpp, ip, ip, dpp,
                                                C.POINTER(TreeInfo), C.POINTER(ModelsStats)]),
+    "miosqp_qp_polish_models": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), dpp, dpp, dpp, dpp, dpp, C.c_double, dp, ip, ip, dpp,
+                                          dpp, C.POINTER(C.c_void_p), C.POINTER(PolishRepairInfo), C.POINTER(PolishModelsStats)]),
+    "miosqp_qp_polish_models_fits": (C.c_int, [C.c_void_p]),
     "miosqp_qp_setup_models": (C.c_int, [C.c_int32, C.POINTER(SetupModel), C.POINTER(C.c_void_p), C.POINTER(SetupModelsStats)]),
     "miosqp_qp_setup_models_auto": (C.c_int, [C.c_int32, C.POINTER(SetupModel), C.POINTER(C.c_void_p), C.POINTER(SetupModelsStats)]),
     "miosqp_qp_debug_panel": (C.c_int, [C.c_void_p, C.c_int32, dp, C.c_int64, C.POINTER(C.c_int64)]),

@@ -1483,7 +1483,102 @@ def _models_own_reason(work):
     return None
 
 
-def solve_models(models, instances=None, info=None):
+def _polish_models_own_reason(work):
+    """why `polish_models` leaves a model to its own `polish_many` (None: it goes into the launch)"""
+    if not hasattr(work.backend, 'polish_models') or not hasattr(work.solver, 'polish_models_fits'):
+        return 'backend without polish_models'
+    if getattr(work, '_no_polish_many', False):
+        return 'polish_many declined this model before'
+    if not work.solver.polish_models_fits():
+        return 'beyond one workgroup'
+    return None
+
+
+def polish_models(models, instances, results, tau=None, repair_iter=20, guess="host", info=None):
+    """The list form of `MIOSQP.polish_many`: polishes the answers of `solve_models(models, instances)` in place, the
+    incumbents of all models in ONE device call (`qp.polish_models`, miosqp_qp_polish_models: one upload, one launch,
+    workgroup b polishes model b).  It replaces the loop `models[k].polish_many([instances[k]], [results[k]])`, whose
+    first call on every engine builds that engine's polish scratch: here nothing is allocated per model.
+
+    For every result with status MI_SOLVED / MI_MAX_ITER_FEASIBLE: its x with the integers rounded, the instance's l, u
+    with the integer rows fixed to them, that model's polish_delta and polish_refine_iter, up to `repair_iter` repair
+    rounds, tau None: 10 x that model's qp_settings['eps_abs'].  guess="host": the multipliers of
+    `primal_guess_multipliers(l, u, A x, tau)`, computed here as `polish_many` computes them -- result k is then what
+    `models[k].polish_many([instances[k]], [results[k]])` makes of it, bit for bit.  guess="device": no y is handed
+    over and the workgroup guesses by the same rule from the z it computes (the library takes one tau per call: models
+    with different taus go in one call per tau); the answer is that of guess="host" wherever no row sits within
+    rounding of the middle between its bounds.  Adoption as in `polish_many`: `accepted and stop == 0`; x gets its
+    integers set exactly and upper_glob is recomputed with the instance's q.  Every result gains polished,
+    polish_rounds, pri_after, dua_after.  The models are not touched.  Returns `results`.
+
+    A model goes to its own `polish_many`, in place, when its backend has no `polish_models` (the CPU oracle), its
+    `_no_polish_many` is set, its sizes are beyond one workgroup, or the library declines the call.
+
+    ValueError: list lengths that differ, tau not positive, another `guess`.  info: a dict that is filled with polished
+    (positions that went into a launch), polish_own ({position: why}), polish_launches and polish_device_time."""
+    models, instances = list(models), list(instances)
+    if not (len(models) == len(instances) == len(results)):
+        raise ValueError('polish_models: one instance and one result per model (%d models, %d instances, %d results)'
+                         % (len(models), len(instances), len(results)))
+    if guess not in ("host", "device"):
+        raise ValueError('polish_models: guess must be "host" or "device"')
+    if tau is not None and not tau > 0:
+        raise ValueError('polish_models: tau must be positive')
+    own, groups, prep = {}, {}, {}
+    for k, mdl in enumerate(models):
+        work, res = mdl.work, results[k]
+        res.update(polished=False, polish_rounds=0, pri_after=np.nan, dua_after=np.nan)
+        if res['status'] not in (MI_SOLVED, MI_MAX_ITER_FEASIBLE):
+            continue
+        why = _polish_models_own_reason(work)
+        if why is not None:
+            own[k] = why
+            continue
+        data = work.data
+        tk = 10. * work.qp_settings.get('eps_abs', 1e-3) if tau is None else float(tau)
+        Q, L, U = mdl._instance_vectors([instances[k]])
+        ii, m = data.i_idx, data.m
+        X = np.array(res['x'], dtype=float)
+        XI = np.round(X[ii])
+        X[ii] = XI
+        L[0, m:] = XI
+        U[0, m:] = XI
+        Y = primal_guess_multipliers(L[0], U[0], data.A.dot(X), tk) if guess == "host" else None
+        prep[k] = (Q[0], L[0], U[0], X, Y, XI)
+        groups.setdefault((work.backend, tk if guess == "device" else None), []).append(k)
+    launched, launches, device_time = [], 0, 0.0
+    for (be, tk), ks in groups.items():
+        r = be.polish_models([models[k].work.solver for k in ks], [prep[k][0] for k in ks], [prep[k][1] for k in ks],
+                             [prep[k][2] for k in ks], [prep[k][3] for k in ks], [prep[k][4] for k in ks],
+                             [models[k].work.pol['delta'] for k in ks], [models[k].work.pol['refine_iter'] for k in ks],
+                             repair_iter, tau=tk)
+        if r is None:  # (an engine declined after all: every model of the call on its own)
+            for k in ks:
+                own[k] = 'the library declined the call'
+            continue
+        recs, stats = r
+        launches += int(stats.launches)
+        device_time += float(stats.device_time)
+        for k, rec in zip(ks, recs):
+            launched.append(k)
+            res, data = results[k], models[k].work.data
+            res['polish_rounds'] = int(rec.rounds)
+            res['pri_after'], res['dua_after'] = float(rec.pri_after), float(rec.dua_after)
+            if rec.accepted and rec.stop == 0:
+                x = np.array(rec.x, dtype=float)
+                x[data.i_idx] = prep[k][5]
+                res['x'] = x
+                res['upper_glob'] = .5 * np.dot(x, data.P.dot(x)) + np.dot(prep[k][0], x)
+                res['polished'] = True
+    for k in sorted(own):
+        models[k].polish_many([instances[k]], [results[k]], tau=tau, repair_iter=repair_iter)
+    if info is not None:
+        info.update(polished=sorted(launched), polish_own=dict(own), polish_launches=launches,
+                    polish_device_time=device_time)
+    return results
+
+
+def solve_models(models, instances=None, info=None, polish=False, polish_guess="host"):
     """One MIQP on each of several DIFFERENT set-up models -- each with its own P, A, shapes and settings --, the trees
     of all of them in ONE call of the library (`qp.solve_trees_models`, miosqp_qp_solve_trees_models: at most two
     launches, workgroup or wavefront b runs model b).  It replaces the loop `models[k].solve_many([instances[k]])`: one
@@ -1504,8 +1599,15 @@ def solve_models(models, instances=None, info=None):
     ValueError before any launch: an empty list, len(instances) != len(models), a model listed twice (both positions
     named), a model that was not set up, l > u in an instance (its position named).
 
+    polish=True: the incumbents are then polished together by `polish_models` (one more launch for the whole list; a
+    model that does not go into it is polished by its own `polish_many`) with guess=polish_guess, and every dict gains
+    polished, polish_rounds, pri_after, dua_after: result k is then what `models[k].solve_many([instances[k]],
+    polish=True)[0]` returns.  polish=False (the default): no dict has those keys.  Any other value raises ValueError.
+
     info: a dict that is filled with launched (positions), own ({position: why}), forms ({'wave': .., 'group': ..}),
-    launches, device_time (seconds) and overflow (positions)."""
+    launches, device_time (seconds) and overflow (positions); with polish=True also what `polish_models` reports."""
+    if not (polish is False or polish is True):
+        raise ValueError('solve_models: polish must be False or True')
     models = list(models)
     B = len(models)
     if B == 0:
@@ -1574,6 +1676,8 @@ def solve_models(models, instances=None, info=None):
     if info is not None:
         info.update(launched=list(launched), own=dict(own), forms=forms, launches=launches, device_time=device_time,
                     overflow=list(overflow))
+    if polish:
+        polish_models(models, instances, out, guess=polish_guess, info=info)
     return out
 
 

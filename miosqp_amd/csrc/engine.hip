@@ -43,6 +43,7 @@
 #include "lockstep_ahead.hpp"  // ahead records, shadow leaves and the choice of ahead columns (plain C++; host_lockstep_ahead.inc drives it)
 #include "lockstep_sb.hpp"  // strong and reliability branching in the lock-step trees (plain C++; host_lockstep_sb.inc drives it)
 #include "setup_plan.hpp"  // set-up of many models in one launch: argument checks, eligibility, arena layout (plain C++; host_setup_models.inc drives it); with guard_probe.hpp and setup_models_body.hpp, the kernel's arithmetic
+#include "polish_models_plan.hpp"  // polishes of different models in one launch: argument checks and arena layout (plain C++; host_polish_models.inc drives it)
 #include "models_plan.hpp"  // trees of different models in one launch: argument checks and arena layout (plain C++; host_models.inc drives it)
 #include "lockstep_refill.hpp"  // which tree goes into which free column when the columns are refilled between chunks (plain C++; host_refill.inc drives it)
 
@@ -298,24 +299,32 @@ void polish_free(miosqp_qp_engine *e) {
 // The values of A as given at set-up in the layout of the scaled rows the device already holds: the same patterns
 // (pc_* by constraint, pv_* by variable), pads zero.  Both packings keep a column's / a row's entries in ascending order
 // (factor.cpp: pack_rows), which a cursor per row reproduces; every position is checked against the packed index.
-bool polish_raw_rows(const miosqp_qp_engine *e, std::vector<double> &by_con, std::vector<double> &by_var) {
+// by_con: room for the by-constraint pattern's entries; by_var nullptr: that half is neither built nor checked
+// (miosqp_qp_polish_models stages the rows by constraint of every model and needs nothing else).
+bool polish_raw_rows(const miosqp_qp_engine *e, double *by_con, std::vector<double> *by_var) {
   const miosqp::PCsr &C = e->fa.panel_by_con, &V = e->fa.panel_by_var;
   const std::vector<int> &Ap = e->sc.Ap, &Ai = e->sc.Ai;
   const int n = e->n, M = e->M;
   if ((int64_t)e->A_raw.size() != (int64_t)Ai.size() || (int)Ap.size() != n + 1) return false;
-  by_con.assign(C.idx.size(), 0.0);
-  by_var.assign(V.idx.size(), 0.0);
+  std::fill(by_con, by_con + C.idx.size(), 0.0);
+  if (by_var) by_var->assign(V.idx.size(), 0.0);
   std::vector<int> cur(M, 0);
   std::vector<std::pair<int, double>> col;
   for (int i = 0; i < n; i++) {
     col.clear();
     for (int p = Ap[i]; p < Ap[i + 1]; p++) col.push_back({Ai[p], e->A_raw[p]});
-    std::sort(col.begin(), col.end(), [](const std::pair<int, double> &a, const std::pair<int, double> &b) { return a.first < b.first; });
-    if (V.ptr[i] + (int)col.size() > V.ptr[i + 1]) return false;
+    if (by_var) {
+      std::sort(col.begin(), col.end(), [](const std::pair<int, double> &a, const std::pair<int, double> &b) { return a.first < b.first; });
+      if (V.ptr[i] + (int)col.size() > V.ptr[i + 1]) return false;
+    }
     for (size_t k = 0; k < col.size(); k++) {
-      const int r = col[k].first, pv = V.ptr[i] + (int)k;
-      if (r < 0 || r >= M || V.idx[pv] != r) return false;
-      by_var[pv] = col[k].second;
+      const int r = col[k].first;
+      if (r < 0 || r >= M) return false;
+      if (by_var) {
+        const int pv = V.ptr[i] + (int)k;
+        if (V.idx[pv] != r) return false;
+        (*by_var)[pv] = col[k].second;
+      }
       const int pc = C.ptr[r] + cur[r]++;
       if (pc >= C.ptr[r + 1] || C.idx[pc] != i) return false;
       by_con[pc] = col[k].second;
@@ -330,8 +339,8 @@ int polish_build(miosqp_qp_engine *e) {
     g_err = "polish: a row of the reduced system does not fit one workgroup's LDS";
     return MIOSQP_EUNSUPPORTED;
   }
-  std::vector<double> by_con, by_var;
-  if (!polish_raw_rows(e, by_con, by_var)) {
+  std::vector<double> by_con(e->fa.panel_by_con.idx.size()), by_var;
+  if (!polish_raw_rows(e, by_con.data(), &by_var)) {
     g_err = "polish: the rows of A on the device do not follow the order of the matrix given at set-up";
     return MIOSQP_EUNSUPPORTED;
   }
@@ -1727,6 +1736,8 @@ int miosqp_qp_get_polish_repair_trace(miosqp_qp_engine *e, int8_t *cls, double *
   return 0;
 }
 
+#include "host_polish_models.inc"  // polishes of different models in one launch (C ABI miosqp_qp_polish_models)
+
 // Both batched polish entries: the argument checks, one pinned block down, the one launch -- k_pol_many, or with `large`
 // k_pol_many_g on W slabs of device scratch --, one pinned block back, the records.  The answers stay in the entry's
 // scratch for its class getter.
@@ -1881,6 +1892,18 @@ static int polish_many_classes(miosqp_qp_engine *e, const miosqp::PolManyScratch
   const double *o = s->h_out + (size_t)b * miosqp::polm_out_stride((int)n, (int)M);
   memcpy(cls, o + miosqp::POLM_REC_DOUBLES + n + M, M);
   return 0;
+}
+
+int miosqp_qp_polish_models(int32_t B, miosqp_qp_engine *const *engines, const double *const *q, const double *const *l,
+                            const double *const *u, const double *const *x, const double *const *y, double tau,
+                            const double *delta, const int32_t *refine_iter, const int32_t *repair_iter, double *const *x_out,
+                            double *const *y_out, int8_t *const *cls_out, miosqp_polish_repair_info *info,
+                            miosqp_polish_models_stats *stats) {
+  return polish_models_run(B, engines, q, l, u, x, y, tau, delta, refine_iter, repair_iter, x_out, y_out, cls_out, info, stats);
+}
+
+int miosqp_qp_polish_models_fits(miosqp_qp_engine *e) {
+  return e && miosqp::polm_lds_bytes(e->n, e->M) <= miosqp::polish_models::LDS_LIMIT ? 1 : 0;
 }
 
 int miosqp_qp_get_polish_many_classes(miosqp_qp_engine *e, int32_t b, int8_t *cls) {

@@ -121,6 +121,72 @@ def solve_trees_models(solvers, q, l, u, x0, y0, upper0, x_inc0, rules, max_iter
     return x, list(infos)[:B], stats
 
 
+def polish_models(solvers, q, l, u, x, y, delta, refine_iter, repair_iter, tau=None):
+    """One polish on each of B DIFFERENT engines in ONE launch (miosqp_qp_polish_models): model b is what
+    `solvers[b].polish_many(q[b][None], l[b][None], ..., delta_b, refine_iter_b, repair_iter_b)[0]` answers, bit for bit,
+    without building or touching any engine's polish scratch.  Lists of per-model arrays (q, x: n_b; l, u, y: M_b); an
+    entry of q may be None (that engine's current linear cost), an entry of y may be None: the device then guesses the
+    multipliers from z = A x (0 on equality and free rows, otherwise -tau / +tau by the nearer bound), which needs
+    tau > 0.  delta, refine_iter, repair_iter: a scalar or one per model.  Returns (records, stats): one record per model
+    shaped like `OSQP.polish_many`'s, `active` included (device_time / run_time are the call's totals), and stats with
+    launches, models, lds_bytes, arena_bytes, device_time (and its parts upload_time, launch_time, download_time),
+    run_time -- or None when the library declines
+    (MIOSQP_EUNSUPPORTED: some model is beyond one workgroup).  ValueError for list lengths that differ and for l > u,
+    RuntimeError (with the library's text, which names the model) for every other refusal."""
+    B = len(solvers)
+
+    def per_model(v, name):
+        if np.ndim(v) == 0:
+            return [v] * B
+        if len(v) != B:
+            raise ValueError("polish_models: %s must be a scalar or have one entry per model" % name)
+        return list(v)
+
+    if not (len(q) == len(l) == len(u) == len(x) == len(y) == B):
+        raise ValueError("polish_models: one entry per model in every list")
+    dl = np.ascontiguousarray(per_model(delta, "delta"), dtype=np.float64).reshape(B)
+    ri = np.ascontiguousarray(per_model(refine_iter, "refine_iter"), dtype=np.int32).reshape(B)
+    pi = np.ascontiguousarray(per_model(repair_iter, "repair_iter"), dtype=np.int32).reshape(B)
+    lib = _lib.load()
+
+    def ptrs(arrs):
+        return (_lib.dp * max(B, 1))(*[None if a is None else _lib.as_d(a) for a in arrs])
+
+    for s in solvers:
+        if s._h is None:
+            raise ValueError("polish_models: an engine that was not set up (or was closed)")
+    q = [None if a is None else _f64(a, s.n, "q") for a, s in zip(q, solvers)]
+    l = [_f64(a, s.m, "l") for a, s in zip(l, solvers)]
+    u = [_f64(a, s.m, "u") for a, s in zip(u, solvers)]
+    x = [_f64(a, s.n, "x") for a, s in zip(x, solvers)]
+    y = [None if a is None else _f64(a, s.m, "y") for a, s in zip(y, solvers)]
+    xo = [np.empty(s.n) for s in solvers]
+    yo = [np.empty(s.m) for s in solvers]
+    cls = [np.zeros(s.m, dtype=np.int8) for s in solvers]
+    infos = (_lib.PolishRepairInfo * max(B, 1))()
+    stats = _lib.PolishModelsStats()
+    hs = (C.c_void_p * max(B, 1))(*[s._h.value for s in solvers])
+    cp = (C.c_void_p * max(B, 1))(*[c.ctypes.data for c in cls])
+    rc = lib.miosqp_qp_polish_models(B, hs, ptrs(q), ptrs(l), ptrs(u), ptrs(x), ptrs(y), 0.0 if tau is None else float(tau),
+                                     _lib.as_d(dl), _lib.as_i(ri), _lib.as_i(pi), ptrs(xo), ptrs(yo), cp, infos,
+                                     C.byref(stats))
+    if rc == -5:
+        return None
+    _check(rc, "polish_models")
+    if rc == 1:
+        raise ValueError("Lower bound must be lower than or equal to upper bound (%s)" % _lib.last_error())
+    out = []
+    for b in range(B):
+        rep, info = infos[b], infos[b].polish
+        out.append(types.SimpleNamespace(
+            x=xo[b], y=yo[b], accepted=bool(info.accepted), reason=info.reason, n_lower=info.n_lower,
+            n_upper=info.n_upper, pri_before=info.pri_before, dua_before=info.dua_before, pri_after=info.pri_after,
+            dua_after=info.dua_after, obj=info.obj, device_time=info.device_time, run_time=info.run_time,
+            rounds=rep.rounds, stop=rep.stop, n_added=rep.n_added, n_dropped=rep.n_dropped,
+            accepted0=bool(rep.accepted0), reason0=rep.reason0, active=cls[b].astype(np.int64)))
+    return out, stats
+
+
 def _csc_arrays(P, A):
     """(n, m, [Pp, Pi, Px, Ap, Ai, Ax]) as OSQP.setup hands them to the library"""
     P = spa.csc_matrix(P)
@@ -485,6 +551,10 @@ class OSQP(object):
                 rounds=rep.rounds, stop=rep.stop, n_added=rep.n_added, n_dropped=rep.n_dropped,
                 accepted0=bool(rep.accepted0), reason0=rep.reason0, active=cls.astype(np.int64)))
         return out
+
+    def polish_models_fits(self):
+        """whether `qp.polish_models` takes this engine's sizes (miosqp_qp_polish_models_fits)"""
+        return bool(self._lib.miosqp_qp_polish_models_fits(self._h))
 
     def polish_rounds(self):
         """Of the last polish call with repair_iter: per round (round 0 first, 21 entries, zeros for rounds not run) the
