@@ -415,11 +415,11 @@ int miosqp_qp_solve_trees(miosqp_qp_engine *e, int32_t B, const double *q, const
 int miosqp_qp_tree_form(miosqp_qp_engine *e);
 
 typedef struct miosqp_models_stats {
-  int32_t launches;         /* tree launches of the call: 0, 1 or 2 (the cost scaling before them is not counted) */
+  int32_t launches;         /* tree launches of the call: 0, 1 or 2 -- up to 3 from miosqp_qp_solve_trees_models_large -- (the cost scaling before them is not counted) */
   int32_t models_wave;      /* models run by the one-wavefront kernel (form 1) */
   int32_t models_group;     /* models run by the one-workgroup kernel (form 2) */
-  int32_t pad;
-  int64_t lds_bytes;        /* dynamic LDS of the workgroup launch: the largest need among its models (0: no such launch) */
+  int32_t pad;              /* 0; from miosqp_qp_solve_trees_models_large: models run by the reduced form (form 3) */
+  int64_t lds_bytes;        /* dynamic LDS of the workgroup launches: the largest need among their models (0: no such launch) */
   double device_time;       /* seconds between the events around upload, launches and download */
   double run_time;          /* wall seconds of the call */
 } miosqp_models_stats;
@@ -448,6 +448,30 @@ int miosqp_qp_solve_trees_models(int32_t B, miosqp_qp_engine *const *engines, co
                                  const double *upper0, const double *const *x_inc0, const int32_t *tree_explor_rule,
                                  const int32_t *max_iter_bb, double *const *x_out, miosqp_tree_info *info,
                                  miosqp_models_stats *stats);
+
+/* ---- ... also for models beyond one workgroup's product form (opt-in) ----------------------------------
+ * The third one-launch form: one workgroup keeps the strict lower triangle of L^-1 packed in LDS (n (n - 1) / 2 doubles)
+ * and iterates in REDUCED form, x~ = L^-T D^-1 L^-1 (rx + rho Abar^T wh), nu = rho (Abar x~ - wh), reading Abar from LDS
+ * copies of its packed rows where they fit and from L2 otherwise (miosqp_amd/csrc/tree_reduced_body.hpp).  Its leaf list
+ * has leaf_cap places (at least 2; 256 is the customary value) instead of the 1024 of the other forms: the leaf store of
+ * a model costs leaf_cap x (2 n_int + n + M) doubles of the arena.
+ * miosqp_qp_tree_form_large: 3 when this engine has integer rows, the root, the digest, the product-form rows on the
+ * device, an integer variable, an LDS need of the reduced form within 160 KB, AND miosqp_qp_tree_form answers 0 -- an
+ * engine that fits form 1 or 2 keeps it; else 0.
+ * miosqp_qp_solve_trees_models_large: miosqp_qp_solve_trees_models for engines of forms 1, 2 and 3 in one call -- at
+ * most three launches (wave, group, reduced), the same arena, ownership by engines[0], one upload, one download, one
+ * synchronisation.  A form 1 or 2 model gets bit for bit what miosqp_qp_solve_trees_models gives it.  A form 3 model's
+ * decisions are those of the host logic; its sums run in another order than the sequential path's, so its values agree
+ * with that path's to rounding, and they do not depend on B, on the model's position or on its neighbours.  stats->pad
+ * holds the number of form 3 models (miosqp_qp_solve_trees_models leaves 0 there); launches may be 3.
+ * Refused as miosqp_qp_solve_trees_models refuses, and: leaf_cap < 2 (MIOSQP_EARG); an arena beyond what the device can
+ * give, naming the model at which it is reached (MIOSQP_EARG) -- nothing is queued, no allocation is tried. */
+int miosqp_qp_tree_form_large(miosqp_qp_engine *e, int32_t leaf_cap);
+int miosqp_qp_solve_trees_models_large(int32_t B, miosqp_qp_engine *const *engines, const double *const *q, const double *const *l,
+                                       const double *const *u, const double *const *x0, const double *const *y0,
+                                       const double *upper0, const double *const *x_inc0, const int32_t *tree_explor_rule,
+                                       const int32_t *max_iter_bb, int32_t leaf_cap, double *const *x_out,
+                                       miosqp_tree_info *info, miosqp_models_stats *stats);
 
 /* ---- polishes of DIFFERENT models in one launch -------------------------------------------------------
  * The polish of the "own P and A per MIQP" pattern: the reference sets up, solves and polishes one model per MIQP

@@ -166,6 +166,9 @@ SYMBOLS = {
     "miosqp_qp_tree_form": (C.c_int, [C.c_void_p]),
     "miosqp_qp_solve_trees_models": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), dpp, dpp, dpp, dpp, dpp, dp, dpp, ip, ip, dpp,
                                                C.POINTER(TreeInfo), C.POINTER(ModelsStats)]),
+    "miosqp_qp_tree_form_large": (C.c_int, [C.c_void_p, C.c_int32]),
+    "miosqp_qp_solve_trees_models_large": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), dpp, dpp, dpp, dpp, dpp, dp, dpp, ip, ip,
+                                                     C.c_int32, dpp, C.POINTER(TreeInfo), C.POINTER(ModelsStats)]),
     "miosqp_qp_polish_models": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), dpp, dpp, dpp, dpp, dpp, C.c_double, dp, ip, ip, dpp,
                                           dpp, C.POINTER(C.c_void_p), C.POINTER(PolishRepairInfo), C.POINTER(PolishModelsStats)]),
     "miosqp_qp_polish_models_fits": (C.c_int, [C.c_void_p]),

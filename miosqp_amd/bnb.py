@@ -1457,8 +1457,18 @@ class MIOSQP(object):
         self.work.set_x0(x0)
 
 
-def _models_own_reason(work):
-    """why `solve_models` leaves a model to its own `solve_many` (None: it goes into the launch)"""
+_BEYOND_ONE_LAUNCH = 'tree_form 0: beyond the one-launch trees'
+
+
+def _models_own_reason(work, declined_counts=True):
+    """why `solve_models` leaves a model to its own `solve_many` (None: it goes into the launch); declined_counts=False
+    looks past an earlier decline of the one-launch trees (an engine beyond them declines `solve_many`'s own attempt)"""
+    if not declined_counts and getattr(work, '_no_trees', False):
+        work._no_trees = False
+        try:
+            return _models_own_reason(work)
+        finally:
+            work._no_trees = True
     st = work.settings
     if not hasattr(work.solver, 'solve_trees') or not hasattr(work.solver, 'tree_form'):
         return 'backend without the one-launch trees'
@@ -1479,7 +1489,7 @@ def _models_own_reason(work):
     except ValueError:
         return 'settings solve_many refuses'
     if work.solver.tree_form() == 0:
-        return 'tree_form 0: beyond the one-launch trees'
+        return _BEYOND_ONE_LAUNCH
     return None
 
 
@@ -1578,7 +1588,7 @@ def polish_models(models, instances, results, tau=None, repair_iter=20, guess="h
     return results
 
 
-def solve_models(models, instances=None, info=None, polish=False, polish_guess="host"):
+def solve_models(models, instances=None, info=None, polish=False, polish_guess="host", large=None, leaf_cap=256):
     """One MIQP on each of several DIFFERENT set-up models -- each with its own P, A, shapes and settings --, the trees
     of all of them in ONE call of the library (`qp.solve_trees_models`, miosqp_qp_solve_trees_models: at most two
     launches, workgroup or wavefront b runs model b).  It replaces the loop `models[k].solve_many([instances[k]])`: one
@@ -1604,10 +1614,31 @@ def solve_models(models, instances=None, info=None, polish=False, polish_guess="
     polished, polish_rounds, pri_after, dua_after: result k is then what `models[k].solve_many([instances[k]],
     polish=True)[0]` returns.  polish=False (the default): no dict has those keys.  Any other value raises ValueError.
 
-    info: a dict that is filled with launched (positions), own ({position: why}), forms ({'wave': .., 'group': ..}),
-    launches, device_time (seconds) and overflow (positions); with polish=True also what `polish_models` reports."""
+    large=None (the default): as above.  large="device": a model that stays out ONLY because its engine is beyond one
+    workgroup's product form (`tree_form()` 0: n + M > 192, or more than 160 KB of LDS) goes into the call as well when
+    its engine's `tree_form_large(leaf_cap)` answers 3 -- a third launch runs such trees with the relaxation in reduced
+    form (the packed triangle of L^-1 in LDS, `qp.solve_trees_models(..., leaf_cap=leaf_cap)`), with a leaf list of
+    leaf_cap places (default 256, at least 2; the other forms keep 1024).  Of the reference benchmark's grid this takes
+    (50,200,10), (100,200,15), (150,100,5) and (150,300,20).  Such a result is not bit for bit that of the model's own
+    `solve_many` (the sums run in another order): status, nodes and osqp_iter are those of the CPU oracle backend's
+    tree, x agrees at the integer positions, upper_glob to 1e-8 and x to 1e-6 relative, and the result does not depend
+    on the list around the model.  One workgroup iterates such a model 5-10 times slower than the whole chip does, but
+    pays no host round trip per node: measured, the keyword pays from one model on (1.4 x) and 15-22 x at 256 models per
+    call (profiles/solve_models_large.txt).  Models of the other forms
+    get what the call without the keyword gives them.  A backend without the entry (the CPU oracle) ignores the keyword.
+    polish=True polishes such a model as any other of the list: the result is what its own `polish_many` makes of the
+    tree's x.  Any other value of `large`, or leaf_cap < 2, raises ValueError.
+
+    info: a dict that is filled with launched (positions), own ({position: why}), forms ({'wave': .., 'group': ..}; with
+    large="device" also 'reduced'), launches, device_time (seconds) and overflow (positions); with polish=True also what
+    `polish_models` reports."""
     if not (polish is False or polish is True):
         raise ValueError('solve_models: polish must be False or True')
+    if large is not None and not (isinstance(large, str) and large == "device"):
+        raise ValueError('solve_models: large must be None or "device"')
+    if isinstance(leaf_cap, bool) or int(leaf_cap) != leaf_cap or leaf_cap < 2:
+        raise ValueError('solve_models: leaf_cap must be an integer of at least 2')
+    leaf_cap = int(leaf_cap)
     models = list(models)
     B = len(models)
     if B == 0:
@@ -1632,15 +1663,21 @@ def solve_models(models, instances=None, info=None, polish=False, polish_guess="
         vec.append((Q[0], L[0], U[0]))
     own = {}
     launched = []
+    any_large = False
     for k, mdl in enumerate(models):
         why = _models_own_reason(mdl.work)
+        if (large == "device" and why is not None and hasattr(mdl.work.solver, 'tree_form_large')
+                and _models_own_reason(mdl.work, declined_counts=False) == _BEYOND_ONE_LAUNCH
+                and mdl.work.solver.tree_form_large(leaf_cap) == 3):
+            why = None
+            any_large = True
         if why is None:
             launched.append(k)
         else:
             own[k] = why
     out = [None] * B
     overflow = []
-    forms = dict(wave=0, group=0)
+    forms = dict(wave=0, group=0, reduced=0) if large == "device" else dict(wave=0, group=0)
     launches, device_time = 0, 0.0
     if launched:
         from miosqp_amd import qp
@@ -1654,7 +1691,7 @@ def solve_models(models, instances=None, info=None, polish=False, polish_guess="
             [np.zeros(len(vec[k][1])) for k in launched], [np.inf if inc[k] is None else inc[k][0] for k in launched],
             [None if inc[k] is None else inc[k][1] for k in launched],
             [models[k].work.settings['tree_explor_rule'] for k in launched],
-            [models[k].work.settings['max_iter_bb'] for k in launched])
+            [models[k].work.settings['max_iter_bb'] for k in launched], **(dict(leaf_cap=leaf_cap) if any_large else {}))
         dt = time() - t0
         if r is None:  # (an engine declined after all: every model on its own)
             for k in launched:
@@ -1663,6 +1700,8 @@ def solve_models(models, instances=None, info=None, polish=False, polish_guess="
         else:
             X, infos, stats = r
             forms = dict(wave=int(stats.models_wave), group=int(stats.models_group))
+            if large == "device":
+                forms['reduced'] = int(stats.pad)
             launches, device_time = int(stats.launches), float(stats.device_time)
             for j, k in enumerate(launched):
                 models[k].work.trees_info = [infos[j]]

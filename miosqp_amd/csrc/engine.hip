@@ -44,6 +44,7 @@
 #include "lockstep_sb.hpp"  // strong and reliability branching in the lock-step trees (plain C++; host_lockstep_sb.inc drives it)
 #include "setup_plan.hpp"  // set-up of many models in one launch: argument checks, eligibility, arena layout (plain C++; host_setup_models.inc drives it); with guard_probe.hpp and setup_models_body.hpp, the kernel's arithmetic
 #include "polish_models_plan.hpp"  // polishes of different models in one launch: argument checks and arena layout (plain C++; host_polish_models.inc drives it)
+#include "tree_reduced_body.hpp"  // the one-launch trees' relaxation in reduced form (k_tree_r_m): LDS rule and the phases of an iteration (plain C++; also run on the CPU under tests/)
 #include "models_plan.hpp"  // trees of different models in one launch: argument checks and arena layout (plain C++; host_models.inc drives it)
 #include "lockstep_refill.hpp"  // which tree goes into which free column when the columns are refilled between chunks (plain C++; host_refill.inc drives it)
 
@@ -269,7 +270,7 @@ namespace {
 // the dynamic-LDS ceiling of a kernel is a property of (process, device, kernel): raised to the chip's 160 KB once instead of
 // at every set-up (the call costs ~40 us, a fifth of a small problem's set-up)
 hipError_t lds_limit_once(const void *fn, int which) {
-  static bool done[16][64] = {};  // (one row per kernel: 0 .. 13 as before, 14: k_setup_models, 15: k_setup_models_auto)
+  static bool done[17][64] = {};  // (one row per kernel: 0 .. 13 as before, 14: k_setup_models, 15: k_setup_models_auto, 16: k_tree_r_m)
   int dev = 0;
   hipError_t rc = hipGetDevice(&dev);
   if (rc != hipSuccess) return rc;
@@ -2222,6 +2223,21 @@ int miosqp_qp_solve_trees_models(int32_t B, miosqp_qp_engine *const *engines, co
                                  const int32_t *max_iter_bb, double *const *x_out, miosqp_tree_info *info,
                                  miosqp_models_stats *stats) {
   return models_run(B, engines, q, l, u, x0, y0, upper0, x_inc0, tree_explor_rule, max_iter_bb, x_out, info, stats);
+}
+
+int miosqp_qp_tree_form_large(miosqp_qp_engine *e, int32_t leaf_cap) {
+  if (!e) return 0;
+  if (e->device >= 0 && hipSetDevice(e->device) != hipSuccess) return 0;
+  const int form = tree_form_large_of(e, leaf_cap);
+  return form == 3 ? 3 : 0;
+}
+
+int miosqp_qp_solve_trees_models_large(int32_t B, miosqp_qp_engine *const *engines, const double *const *q, const double *const *l,
+                                       const double *const *u, const double *const *x0, const double *const *y0,
+                                       const double *upper0, const double *const *x_inc0, const int32_t *tree_explor_rule,
+                                       const int32_t *max_iter_bb, int32_t leaf_cap, double *const *x_out,
+                                       miosqp_tree_info *info, miosqp_models_stats *stats) {
+  return models_run(B, engines, q, l, u, x0, y0, upper0, x_inc0, tree_explor_rule, max_iter_bb, x_out, info, stats, true, leaf_cap);
 }
 
 int miosqp_qp_debug_iterate(miosqp_qp_engine *e, int32_t k, double *x, double *z, double *y) {

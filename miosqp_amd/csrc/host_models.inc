@@ -1,6 +1,8 @@
 // part of engine.hip (included there, not compiled alone): what the one-launch tree entries share, and the trees of
-// DIFFERENT models in one launch (C ABI miosqp_qp_tree_form, miosqp_qp_solve_trees_models; kernels k_tree_m / k_tree_w_m /
-// k_scale_q_models in kernels_tree.inc; argument checks and arena layout in models_plan.hpp).
+// DIFFERENT models in one launch (C ABI miosqp_qp_tree_form, miosqp_qp_solve_trees_models, and with the reduced form for
+// models beyond one workgroup's product form miosqp_qp_tree_form_large, miosqp_qp_solve_trees_models_large; kernels
+// k_tree_m / k_tree_w_m / k_tree_r_m / k_scale_q_models in kernels_tree.inc; argument checks and arena layout in
+// models_plan.hpp).
 extern "C" {
 static int stage_wait(miosqp_qp_engine *e, int k);
 }
@@ -71,10 +73,50 @@ int tree_form_of(miosqp_qp_engine *e) {
   return wave ? 1 : 2;
 }
 
+// dynamic LDS of k_tree_r_m (the reduced form) for this engine with a leaf list of `leaf_cap` places, and where the LDS
+// copies of Abar start inside it -- the rows the test walks at sp_off, the rows of Abar^T at pv_off --, both or neither
+// (the sp_off rule of res_sp_load: they are there when they fit behind everything else).  The rows of Abar^T are sized by
+// a bound: their padded length is at most that of the rows by constraint plus one per variable.
+size_t tree_r_lds_bytes(const miosqp_qp_engine *e, int leaf_cap, int *sp_off, int *pv_off) {
+  const int n = e->n, M = e->M;
+  size_t lds = tree_r_lds_doubles(n, M, leaf_cap);
+  *sp_off = *pv_off = -1;
+  const size_t sp = res_sp_doubles(e->sp_nnzA, e->sp_nnzP, n, M), pv = miosqp::tree_reduced::pv_doubles(e->sp_nnzA + (size_t)n, n);
+  if (e->sp_nnzA > 0 && (lds + sp + pv) * sizeof(double) <= miosqp::tree_reduced::LDS_LIMIT &&
+      !(getenv("MIOSQP_RES_SP") && atoi(getenv("MIOSQP_RES_SP")) == 0)) {
+    *sp_off = (int)lds;
+    *pv_off = (int)(lds + sp);
+    lds += sp + pv;
+  }
+  return lds * sizeof(double);
+}
+
+// miosqp_qp_tree_form_large without the entry's own checks: 3 when the reduced form takes an engine that no other form
+// takes, else 0 (or a negative error code of tree_form_of's lazy build)
+int tree_form_large_of(miosqp_qp_engine *e, int leaf_cap) {
+  if (leaf_cap < 2) return 0;
+  const int form = tree_form_of(e);
+  if (form != 0) return form < 0 ? form : 0;  // an engine that fits an existing form keeps that form
+  if (!e->have_int || !e->d.digest || !e->fold || !e->d.f_rows || e->d.n_int < 1) return 0;
+  return tree_r_lds_doubles(e->n, e->M, leaf_cap) * sizeof(double) <= miosqp::tree_reduced::LDS_LIMIT ? 3 : 0;
+}
+
+// which rows of Abar the reduced iteration reads from L2 (no LDS copy): 1 the dense copies, 0 the packed panels.
+// Measured (profiles/solve_models_large.txt); MIOSQP_TREE_R_DENSE overrides for that measurement.
+int tree_r_dense(const miosqp_qp_engine *e) {
+  if (!e->d.f_Ad || !e->d.f_Atd) return 0;
+  if (const char *v = getenv("MIOSQP_TREE_R_DENSE")) return atoi(v) != 0;
+  return 1;
+}
+
 // the arena of miosqp_qp_solve_trees_models and its pinned mirror: they belong to the engine that was first in the call
 int models_reserve(miosqp_qp_engine *e, size_t total_doubles, size_t up_doubles) {
   if (total_doubles > e->mm_cap) {  // (a larger call takes a new arena; the old one stays with the pool until cleanup)
-    const size_t cap = std::max(total_doubles, 2 * e->mm_cap);
+    size_t cap = std::max(total_doubles, 2 * e->mm_cap);
+    if (cap > total_doubles) {  // (growing ahead only where the device has the room; the caller checked total_doubles itself)
+      size_t fr = 0, tot = 0;
+      if (hipMemGetInfo(&fr, &tot) != hipSuccess || cap * sizeof(double) + 4096 > fr / 2) cap = total_doubles;
+    }
     int rc = pool_reserve(e, cap * sizeof(double) + 4096);
     if (!rc) rc = dalloc(e, &e->mm_dev, cap);
     if (rc) return rc;
@@ -95,9 +137,16 @@ int models_reserve(miosqp_qp_engine *e, size_t total_doubles, size_t up_doubles)
 int models_run(int32_t B, miosqp_qp_engine *const *engines, const double *const *q, const double *const *l,
                const double *const *u, const double *const *x0, const double *const *y0, const double *upper0,
                const double *const *x_inc0, const int32_t *rule, const int32_t *max_iter_bb, double *const *x_out,
-               miosqp_tree_info *info, miosqp_models_stats *stats) {
+               miosqp_tree_info *info, miosqp_models_stats *stats, bool large = false, int32_t leaf_cap = 0) {
   namespace mm = miosqp::models;
   // ---- refused before anything is queued ----
+  if (large) {
+    std::string err;
+    if (int rc = mm::check_leaf_cap(leaf_cap, err)) {
+      g_err = err;
+      return rc;
+    }
+  }
   {
     std::vector<int> Mv;
     if (B >= 1 && engines)
@@ -127,7 +176,9 @@ int models_run(int32_t B, miosqp_qp_engine *const *engines, const double *const 
   std::vector<mm::Shape> sh((size_t)B);
   for (int b = 0; b < B; b++) {
     miosqp_qp_engine *e = engines[b];
-    const int form = tree_form_of(e);  // (the lazy build of W / Kc and its guard: the engine's own state, on its own stream)
+    int form = tree_form_of(e);  // (the lazy build of W / Kc and its guard: the engine's own state, on its own stream)
+    if (form < 0) return form;
+    if (form == 0 && large) form = tree_form_large_of(e, leaf_cap);
     if (form < 0) return form;
     if (form == 0) {
       g_err = "solve_trees_models: the one-launch trees do not take model " + std::to_string(b) +
@@ -136,9 +187,20 @@ int models_run(int32_t B, miosqp_qp_engine *const *engines, const double *const 
     }
     sh[(size_t)b] = mm::Shape{e->n, e->M, e->d.n_int, form};
   }
-  const mm::Plan P = mm::plan(sh, sizeof(TreeModel), (size_t)TREE_CAP);
+  const mm::Plan P = mm::plan(sh, sizeof(TreeModel), (size_t)TREE_CAP, (size_t)leaf_cap);
+  if (P.n3) {  // the leaf stores of the reduced form are the large part of an arena: refused by name, not a failed allocation
+    size_t fr = 0, tot = 0;
+    HIPCHK(hipMemGetInfo(&fr, &tot));
+    const size_t have = e0->mm_cap * sizeof(double), room = (fr > ((size_t)256 << 20) ? fr - ((size_t)256 << 20) : 0);
+    std::string err;
+    if (int rc = mm::check_arena(P, sh, (size_t)TREE_CAP, (size_t)leaf_cap, std::max(have, room) / sizeof(double), err)) {
+      g_err = err;
+      return rc;
+    }
+  }
   if (int rc = models_reserve(e0, P.total_doubles, P.up_doubles)) return rc;
   if (P.n2) HIPCHK(lds_limit_once((const void *)k_tree_m, 13));
+  if (P.n3) HIPCHK(lds_limit_once((const void *)k_tree_r_m, 16));
   // every other engine's stream in front of the launches: an update or a lazy build queued there has finished
   for (int b = 1; b < B; b++) {
     if (int rc = stage_wait(engines[b], 0)) return rc;
@@ -149,7 +211,7 @@ int models_run(int32_t B, miosqp_qp_engine *const *engines, const double *const 
   //      update_lin_cost, a lazy build of W or a tripped guard) ----
   double *hs = e0->mm_host, *dv = e0->mm_dev;
   TreeModel *tab_h = reinterpret_cast<TreeModel *>(hs), *tab_d = reinterpret_cast<TreeModel *>(dv);
-  size_t lds_max = 0;
+  size_t lds_max = 0, lds_max_r = 0;
   for (int b = 0; b < B; b++) {
     miosqp_qp_engine *e = engines[b];
     const mm::Slot &s = P.slot[(size_t)b];
@@ -192,6 +254,15 @@ int models_run(int32_t B, miosqp_qp_engine *const *engines, const double *const 
     ta.sp_off = -1;
     ta.batch = 0;
     ta.upper_b = nullptr;
+    ta.leaf_cap = TREE_CAP;
+    ta.pv_off = -1;
+    ta.r_dense = 0;
+    if (sh[(size_t)b].form == 3) {
+      ta.leaf_cap = leaf_cap;
+      ta.TG1 = miosqp::tree_reduced::TGR;  // rows of Abar in the prologue, the test and the epilogue: as the iteration walks them
+      ta.r_dense = tree_r_dense(e);
+      lds_max_r = std::max(lds_max_r, tree_r_lds_bytes(e, leaf_cap, &ta.sp_off, &ta.pv_off));
+    }
     if (sh[(size_t)b].form == 2) {  // (after the form is settled: W may have come or gone in tree_form_of)
       const size_t lds = tree_lds_bytes(e, &ta.sp_off);
       lds_max = std::max(lds_max, lds);
@@ -205,6 +276,7 @@ int models_run(int32_t B, miosqp_qp_engine *const *engines, const double *const 
   hipLaunchKernelGGL(k_scale_q_models, dim3((unsigned)B), dim3(64), 0, e0->stream, tab_d);
   if (P.n1) hipLaunchKernelGGL(k_tree_w_m, dim3((unsigned)P.n1), dim3(TW), 0, e0->stream, tab_d);
   if (P.n2) hipLaunchKernelGGL(k_tree_m, dim3((unsigned)P.n2), dim3(RES_THREADS), lds_max, e0->stream, tab_d + P.n1);
+  if (P.n3) hipLaunchKernelGGL(k_tree_r_m, dim3((unsigned)P.n3), dim3(RES_THREADS), lds_max_r, e0->stream, tab_d + P.n1 + P.n2);
   HIPCHK(hipMemcpyAsync(hs + P.down_off, dv + P.down_off, sizeof(double) * P.down_doubles, hipMemcpyDeviceToHost, e0->stream));
   HIPCHK(hipEventRecord(e0->ev1, e0->stream));
   HIPCHK(hipStreamSynchronize(e0->stream));
@@ -232,11 +304,11 @@ int models_run(int32_t B, miosqp_qp_engine *const *engines, const double *const 
     e->loop_ms += ms / B;
     e->loop_iters += o.osqp_iter;
   }
-  stats->launches = (P.n1 ? 1 : 0) + (P.n2 ? 1 : 0);
+  stats->launches = (P.n1 ? 1 : 0) + (P.n2 ? 1 : 0) + (P.n3 ? 1 : 0);
   stats->models_wave = P.n1;
   stats->models_group = P.n2;
-  stats->pad = 0;
-  stats->lds_bytes = (int64_t)lds_max;
+  stats->pad = P.n3;  // (models run by the reduced form: 0 unless the call came through miosqp_qp_solve_trees_models_large)
+  stats->lds_bytes = (int64_t)std::max(lds_max, lds_max_r);
   stats->device_time = 1e-3 * ms;
   stats->run_time = wall_s;
   return 0;

@@ -33,6 +33,10 @@ struct TreeArgs {
   // start and incumbent -- every per-instance array holds `batch` instances back to back; upper_b[b]: its incumbent value
   int batch;
   const double *upper_b;
+  // k_tree_r_m (the reduced form, tree_reduced_body.hpp): the leaf list's capacity (the leaf store holds as many places);
+  // offset (doubles) of the LDS copy of Abar^T's packed rows, or -1 -- it is there exactly when sp_off is; and which rows of
+  // Abar the iteration reads where no LDS copy is: 1 the dense copies (f_Atd, f_Ad), 0 the packed panels (pv_At, pc_A)
+  int leaf_cap, pv_off, r_dense;
 };
 
 // workgroup b of a batched launch: the per-instance pointers of Dev and TreeArgs moved to instance b (the staging block
@@ -112,10 +116,11 @@ __device__ __forceinline__ void order_remove(int *order, int best, int count, in
   }
 }
 
+#define TREE_LIST_CAP TREE_CAP
 __global__ __launch_bounds__(RES_THREADS) void k_tree(Dev d, TreeArgs ta) {
   extern __shared__ __attribute__((aligned(16))) double sm[];
   tree_instance(d, ta);
-#include "kernels_tree_body.inc"  // the body, shared with k_tree_m
+#include "kernels_tree_body.inc"  // the body, shared with k_tree_m and k_tree_r_m
 }
 
 // ------------------------------------------------------------------------------------------
@@ -136,6 +141,103 @@ __global__ __launch_bounds__(RES_THREADS) void k_tree_m(const TreeModel *__restr
   const TreeArgs &ta = tab[blockIdx.x].ta;
 #include "kernels_tree_body.inc"  // the body of k_tree
 }
+#undef TREE_LIST_CAP
+
+// ------------------------------------------------------------------------------------------
+// The same tree for a model BEYOND one workgroup's product form (n + M > RES_W_MAX and n x (M + n) doubles above the
+// LDS): the relaxation in REDUCED form (tree_reduced_body.hpp) -- the packed strict lower triangle of L^-1 in LDS, Abar
+// read by variable and by constraint from LDS copies of its packed rows where they fit behind everything else, else
+// from L2.  Entry b of the same table; the tree logic is the same text (kernels_tree_body.inc under TREE_REDUCED).
+// Decisions, list semantics and results are those of k_tree; the summation order inside an iteration differs, and the
+// leaf list has ta.leaf_cap places.  miosqp_qp_solve_trees_models_large (host_models.inc) launches it.
+// ------------------------------------------------------------------------------------------
+static_assert(miosqp::tree_reduced::THREADS == RES_THREADS && miosqp::tree_reduced::WAVES == RES_WAVES &&
+                  miosqp::tree_reduced::NQ == NQ,
+              "tree_reduced_body.hpp restates the workgroup's size and the test's scratch");
+
+__host__ __device__ inline size_t tree_r_lds_doubles(int n, int M, int leaf_cap) {
+  return miosqp::tree_reduced::lds_doubles(n, M, leaf_cap);
+}
+
+// the executor of the phases on the device: every thread runs the phase, a barrier behind it; a row's partial sums meet
+// through the lane exchanges of group_reduce (a butterfly, small strides first)
+struct TreeRExec {
+  template <class F>
+  __device__ __forceinline__ void par(F f) {
+    f((int)threadIdx.x);
+    __syncthreads();
+  }
+  template <class F>
+  __device__ __forceinline__ double lane_sum(int TG, int t, F f) {
+    double v[1] = {f(t)};
+    group_reduce<1>(v, TG);
+    return v[0];
+  }
+};
+
+// the LDS arrays the termination test, the prologue and the epilogue read, at their places in the reduced carve-up
+__device__ __forceinline__ ResCtx res_carve_r(double *sm, const miosqp::tree_reduced::State &s, const miosqp::tree_reduced::Carve &cv) {
+  ResCtx c;
+  c.n = s.n; c.M = s.M; c.ldr = s.ld;
+  c.Rm = s.tri; c.wr = s.wr; c.wr2 = nullptr; c.tv = nullptr;
+  c.x = s.x; c.q = s.q; c.d2 = s.d2; c.ut = s.ut; c.dx = s.dx;
+  c.z = s.z; c.y = s.y; c.l = s.l; c.u = s.u; c.dy = s.dy;
+  c.vp = sm + cv.scr;
+  c.smc = c.vp + s.M;
+  c.snc = c.smc + 8 * (size_t)s.M;
+  c.part = sm + cv.part;
+  c.res = sm + cv.res;
+  return c;
+}
+
+// Abar for the iteration: by constraint the rows the test walks (sp: LDS or L2), by variable pv_* -- copied into LDS at
+// ta.pv_off (the caller synchronises afterwards) --, or the dense copies
+__device__ __forceinline__ miosqp::tree_reduced::Abar tree_r_abar(const Dev &d, const TreeArgs &ta, const ResSp &sp, double *sm) {
+  miosqp::tree_reduced::Abar a{d.pv_ptr, d.pv_idx, d.pv_At, sp.Ap, sp.Ai, sp.A, d.f_Atd, d.f_Ad, d.ldm, d.ldn, ta.r_dense};
+  if (ta.pv_off < 0) return a;
+  const int tid = threadIdx.x, n = d.n, nV = d.pv_ptr[n];
+  double *V = sm + ta.pv_off;
+  int *Vi = reinterpret_cast<int *>(V + nV), *Vp = Vi + nV;
+  for (int k = tid; k < nV; k += RES_THREADS) { V[k] = d.pv_At[k]; Vi[k] = d.pv_idx[k]; }
+  for (int k = tid; k <= n; k += RES_THREADS) Vp[k] = d.pv_ptr[k];
+  a.pv_At = V; a.pv_idx = Vi; a.pv_ptr = Vp;
+  a.dense = 0;
+  return a;
+}
+
+// the ADMM loop of res_admm on the reduced form: the same state, the same test at the same iterations
+__device__ __forceinline__ int res_admm_r(const Dev &d, const ResCtx &c, const miosqp::tree_reduced::State &s,
+                                          const miosqp::tree_reduced::Abar &A, int max_iter, int check_every, int final_check,
+                                          int TG1, int *iters, const ResSp &sp) {
+  TreeRExec x;
+  const miosqp::tree_reduced::Par p{d.rho, d.rho_inv, d.sigma, d.alpha};
+  int status = 0, it = 0;
+  bool checked = false;
+  for (it = 1; it <= max_iter; it++) {
+    miosqp::tree_reduced::iterate(x, s, A, p);
+    checked = false;
+    if (check_every > 0 && it % check_every == 0) {
+      checked = true;
+      status = res_check(d, c, it, TG1, sp);
+      if (status) break;
+    }
+  }
+  if (it > max_iter) it = max_iter;
+  if (!status && !checked && final_check) status = res_check(d, c, it, TG1, sp);
+  *iters = it;
+  return status;
+}
+
+#define TREE_LIST_CAP ta.leaf_cap
+#define TREE_REDUCED 1
+__global__ __launch_bounds__(RES_THREADS) void k_tree_r_m(const TreeModel *__restrict__ tab) {
+  extern __shared__ __attribute__((aligned(16))) double sm[];
+  const Dev &d = tab[blockIdx.x].d;
+  const TreeArgs &ta = tab[blockIdx.x].ta;
+#include "kernels_tree_body.inc"  // the body of k_tree, with the three pieces of the reduced form
+}
+#undef TREE_REDUCED
+#undef TREE_LIST_CAP
 
 // every model's cost vector in one launch: qbar = c D q, the expression (and operation order) of k_scale_q_batch and
 // k_scale_q; block b takes entry b (d.qraw -> d.q, both in the arena)

@@ -1,8 +1,11 @@
-// part of kernels_tree.inc (included there INSIDE k_tree and k_tree_m, nowhere else): the one body of the two kernels.
+// part of kernels_tree.inc (included there INSIDE k_tree, k_tree_m and k_tree_r_m, nowhere else): the one body of the
+// kernels.  TREE_LIST_CAP: the leaf list's capacity; TREE_REDUCED (k_tree_r_m): the carve-up, the factor load and the call
+// that runs the relaxation are those of the reduced form -- nothing else differs.
 // In scope: `sm` (the dynamic LDS block), `d` (Dev) and `ta` (TreeArgs) with final pointers -- kernel arguments moved to
 // the block's instance (k_tree), or references to the block's entry of a table in device memory (k_tree_m).  Everything
 // per block -- shapes, the LDS carve-up, sp_off, lane groupings, search settings, tolerances -- is read from them.
   const int n = d.n, M = d.M, p = d.n_int, m0 = d.m_orig, tid = threadIdx.x;
+#ifndef TREE_REDUCED
   const bool wform = d.W != nullptr && n + M <= RES_W_MAX;
   const ResCtx c = res_carve(sm, n, M, wform);
   double *xf = c.res + NQ + 8, *xi = xf + n, *prow = xi + n;  // prow: 2 n (objective rows at xf / xi)
@@ -15,23 +18,48 @@
   double *fm_v = sc + 16;                                         // best-bound choice: a pair per wavefront
   int *fm_k = reinterpret_cast<int *>(fm_v + RES_WAVES);
   int *iiL = reinterpret_cast<int *>(sc + 32);                    // i_idx (thread 0 walks it for every node)
+#else  // k_tree_r_m: the carve-up of tree_reduced_body.hpp -- no product form, the test's scratch shared with the epilogue's
+  // vectors, a leaf list of ta.leaf_cap places
+  namespace tr = miosqp::tree_reduced;
+  const tr::Carve cv = tr::carve(n, M, ta.leaf_cap);
+  const tr::State rs = tr::state(sm, n, M, ta.leaf_cap);
+  const ResCtx c = res_carve_r(sm, rs, cv);
+  double *xf = sm + cv.scr, *xi = xf + n, *prow = xi + n;
+  double *yf = prow + 2 * n, *rowbuf = yf + M;
+  double *lf_lower = sm + cv.lf_lower;
+  int *order = reinterpret_cast<int *>(sm + cv.order);
+  int *lf_depth = order + ta.leaf_cap;
+  int *freelist = lf_depth + ta.leaf_cap;
+  double *sc = sm + cv.sc;
+  double *fm_v = sc + 16;
+  int *fm_k = reinterpret_cast<int *>(fm_v + RES_WAVES);
+  int *iiL = reinterpret_cast<int *>(sm + cv.iiL);
+#endif
   // sc[0] upper, sc[1] action, sc[2] slot, sc[3] status, sc[4] lower, sc[5] heur_obj, sc[6] nextvar, sc[7] child0, sc[8] child1
   const double rinv = d.rho_inv, sigma = d.sigma;
   const int unsolved = MIOSQP_QP_UNSOLVED;
   (void)unsolved;
 
+#ifndef TREE_REDUCED
   if (!wform) res_load_factor(d, c);
   const ResSp sp = res_sp_load(d, ta.sp_off >= 0 ? sm + ta.sp_off : nullptr);
+#else  // the packed triangle of L^-1 instead of the product form; Abar by variable beside the rows the test walks
+  TreeRExec rex;
+  tr::load_triangle(rex, rs, d.f_rows, d.ldf, d.d2inv);
+  const ResSp sp = res_sp_load(d, ta.sp_off >= 0 ? sm + ta.sp_off : nullptr);
+  const tr::Abar ra = tree_r_abar(d, ta, sp, sm);
+#endif
   for (int i = tid; i < n; i += RES_THREADS) c.q[i] = d.q[i];
   for (int k = tid; k < p; k += RES_THREADS) iiL[k] = d.i_idx[k];
   // this thread's entries of the vectors every node's prologue and epilogue need (row / variable tid: the sizes that fit
-  // the LDS have at most RES_THREADS of either): read once instead of once per node and loop
+  // the LDS have at most RES_THREADS of either -- the reduced form also takes more rows: the strided loops cover them):
+  // read once instead of once per node and loop
   const bool cj = tid < M, ci = tid < n;
   const double E_t = cj ? d.E[tid] : 0.0, Einv_t = cj ? d.Einv[tid] : 0.0, D_t = ci ? d.D[tid] : 0.0,
                Dinv_t = ci ? d.Dinv[tid] : 0.0;
   const double rawl_t = (cj && tid < m0) ? d.raw_l[tid] : 0.0, rawu_t = (cj && tid < m0) ? d.raw_u[tid] : 0.0;
   const int pos_t = ci ? d.int_pos[tid] : -1;
-  for (int k = tid; k < TREE_CAP; k += RES_THREADS) freelist[k] = TREE_CAP - 1 - k;  // pop hands out slot 0 first
+  for (int k = tid; k < TREE_LIST_CAP; k += RES_THREADS) freelist[k] = TREE_LIST_CAP - 1 - k;  // pop hands out slot 0 first
   __syncthreads();
   // the root: slot 0, bounds and warm start from the staging block (raw_l | raw_u | raw_x | raw_y)
   for (int k = tid; k < p; k += RES_THREADS) {
@@ -40,7 +68,7 @@
   }
   for (int i = tid; i < n; i += RES_THREADS) ta.lf_x[i] = d.raw_x[i];
   for (int j = tid; j < M; j += RES_THREADS) ta.lf_y[j] = d.raw_y[j];
-  int count = 1, nfree = TREE_CAP - 1, nodes = 0, osqp_iter = 0, max_leaves = 1, overflow = 0, found = 0;
+  int count = 1, nfree = TREE_LIST_CAP - 1, nodes = 0, osqp_iter = 0, max_leaves = 1, overflow = 0, found = 0;
   double lower_glob = -1.0 / 0.0;
   if (tid == 0) {
     order[0] = 0;
@@ -143,7 +171,11 @@
     // ---- the relaxation ----
     KT_STAMP(0)
     int it = 0;
+#ifndef TREE_REDUCED
     int st = res_admm(d, c, ta.max_iter, ta.check_every, 1, ta.TG1, ta.TG2, &it, sp);
+#else
+    int st = res_admm_r(d, c, rs, ra, ta.max_iter, ta.check_every, 1, ta.TG1, &it, sp);
+#endif
     KT_STAMP(1)
     if (st == 0) st = MIOSQP_QP_MAX_ITER_REACHED;
     nodes++;
@@ -260,7 +292,7 @@
       }
       int c0 = -1, c1 = -1;
       if (action & 4) {
-        if (nfree < 2 || count + 2 > TREE_CAP) {
+        if (nfree < 2 || count + 2 > TREE_LIST_CAP) {
           overflow = 1;
         } else {
           c0 = freelist[--nfree];

@@ -62,8 +62,18 @@ inline int check_args(int32_t B, const void *const *engines, const int *M, const
 
 struct Shape {
   int n, M, p;  // variables, rows (general + integer), integer variables
-  int form;     // 1: one wavefront, 2: one workgroup
+  int form;     // 1: one wavefront, 2: one workgroup, 3: one workgroup in reduced form (miosqp_qp_solve_trees_models_large)
 };
+
+// what miosqp_qp_solve_trees_models_large checks beyond check_args: the leaf list of the reduced form needs room for the
+// two children of the root's branching
+inline int check_leaf_cap(int32_t leaf_cap, std::string &err) {
+  if (leaf_cap < 2) {
+    err = "solve_trees_models_large: leaf_cap must be at least 2 (got " + std::to_string(leaf_cap) + ")";
+    return ERR_ARG;
+  }
+  return 0;
+}
 
 // where model b's arrays lie in the arena (offsets in doubles from its base) and which table entry is its own
 struct Slot {
@@ -76,10 +86,12 @@ struct Slot {
 
 // [ table | raw, qraw of every model | inc, out of every model | q and leaf store of every model ]: the first three parts
 // go up in ONE copy, the third comes back in ONE copy.  The table holds the one-wavefront models first (the launch over
-// them reads entries [0, n1)), then the workgroup models (entries [n1, n1 + n2)), each group in the caller's order.
+// them reads entries [0, n1)), then the workgroup models (entries [n1, n1 + n2)), then the models of the reduced form
+// (entries [n1 + n2, n1 + n2 + n3)), each group in the caller's order.  The leaf store of a model has `tree_cap` places,
+// that of a reduced-form model `leaf_cap_r`.
 struct Plan {
   std::vector<Slot> slot;
-  int n1 = 0, n2 = 0;
+  int n1 = 0, n2 = 0, n3 = 0;
   size_t table_doubles = 0;
   size_t up_doubles = 0;               // what the host stages and uploads: [0, up_doubles)
   size_t down_off = 0, down_doubles = 0;  // what comes back
@@ -88,13 +100,13 @@ struct Plan {
 
 inline size_t round_up(size_t v, size_t to) { return (v + to - 1) / to * to; }
 
-inline Plan plan(const std::vector<Shape> &sh, size_t entry_bytes, size_t tree_cap) {
+inline Plan plan(const std::vector<Shape> &sh, size_t entry_bytes, size_t tree_cap, size_t leaf_cap_r = 0) {
   Plan P;
   const size_t B = sh.size();
   P.slot.resize(B);
-  for (const Shape &s : sh) (s.form == 1 ? P.n1 : P.n2)++;
-  int k1 = 0, k2 = P.n1;
-  for (size_t b = 0; b < B; b++) P.slot[b].entry = sh[b].form == 1 ? k1++ : k2++;
+  for (const Shape &s : sh) (s.form == 1 ? P.n1 : s.form == 3 ? P.n3 : P.n2)++;
+  int k1 = 0, k2 = P.n1, k3 = P.n1 + P.n2;
+  for (size_t b = 0; b < B; b++) P.slot[b].entry = sh[b].form == 1 ? k1++ : sh[b].form == 3 ? k3++ : k2++;
   P.table_doubles = round_up((B * entry_bytes + 7) / 8, 32);
   size_t at = P.table_doubles;
   for (size_t b = 0; b < B; b++) {
@@ -117,19 +129,36 @@ inline Plan plan(const std::vector<Shape> &sh, size_t entry_bytes, size_t tree_c
   at = round_up(at, 32);
   for (size_t b = 0; b < B; b++) {
     const size_t n = (size_t)sh[b].n, M = (size_t)sh[b].M, p = (size_t)sh[b].p;
+    const size_t cap = sh[b].form == 3 ? leaf_cap_r : tree_cap;
     P.slot[b].q = at;
     at += round_up(n, 2);
     P.slot[b].lf_lo = at;
-    at += tree_cap * p;
+    at += cap * p;
     P.slot[b].lf_hi = at;
-    at += tree_cap * p;
+    at += cap * p;
     P.slot[b].lf_x = at;
-    at += tree_cap * n;
+    at += cap * n;
     P.slot[b].lf_y = at;
-    at += tree_cap * M;
+    at += cap * M;
   }
   P.total_doubles = at;
   return P;
+}
+
+// The arena against what the device pool can give (`limit_doubles`): 0, or ERR_ARG with `err` naming the first model
+// whose leaf store ends beyond the limit (the staged part in front of the leaf stores counts against model 0).
+inline int check_arena(const Plan &P, const std::vector<Shape> &sh, size_t tree_cap, size_t leaf_cap_r, size_t limit_doubles,
+                       std::string &err) {
+  if (P.total_doubles <= limit_doubles) return 0;
+  size_t b = 0;
+  for (; b + 1 < sh.size(); b++) {
+    const size_t cap = sh[b].form == 3 ? leaf_cap_r : tree_cap;
+    if (P.slot[b].lf_y + cap * (size_t)sh[b].M > limit_doubles) break;
+  }
+  err = "solve_trees_models_large: the arena of the call (" + std::to_string(P.total_doubles * sizeof(double)) +
+        " bytes) is beyond what the device pool can give (" + std::to_string(limit_doubles * sizeof(double)) +
+        " bytes): reached at model " + std::to_string(b) + "; fewer models per call, or a smaller leaf_cap";
+  return ERR_ARG;
 }
 
 }  // namespace models

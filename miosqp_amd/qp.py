@@ -79,14 +79,21 @@ def _f64(a, size, name):
     return a
 
 
-def solve_trees_models(solvers, q, l, u, x0, y0, upper0, x_inc0, rules, max_iter_bb):
+def solve_trees_models(solvers, q, l, u, x0, y0, upper0, x_inc0, rules, max_iter_bb, leaf_cap=None):
     """One MIQP on each of B DIFFERENT engines, every tree in one launch per kernel form (miosqp_qp_solve_trees_models):
     model b is what `solvers[b].solve_trees(q[b][None], ...)` solves, bit for bit.  Lists of per-model arrays (q, x0: n_b;
     l, u, y0: M_b), upper0: B incumbent values (inf: none), x_inc0: per model an array or None, rules / max_iter_bb: per
     model.  Returns ([x_b], [TreeInfo], stats) -- stats: launches, models_wave, models_group, lds_bytes, device_time,
     run_time -- or None when the library declines (MIOSQP_EUNSUPPORTED: some engine's tree_form() is 0).  ValueError for
-    l > u in a root, RuntimeError (with the library's text, which names the model) for every other refusal."""
+    l > u in a root, RuntimeError (with the library's text, which names the model) for every other refusal.
+
+    leaf_cap (None: the call above, exactly): an int >= 2 sends the call to miosqp_qp_solve_trees_models_large, which also
+    takes engines whose `tree_form_large(leaf_cap)` is 3 -- the reduced form for models beyond one workgroup's product
+    form, with a leaf list of leaf_cap places -- in a third launch; stats.pad then counts them.  Engines of forms 1 and 2
+    get what the call without leaf_cap gives them, bit for bit."""
     B = len(solvers)
+    if leaf_cap is not None and int(leaf_cap) < 2:
+        raise ValueError("solve_trees_models: leaf_cap must be at least 2")
     if not (len(q) == len(l) == len(u) == len(x0) == len(y0) == len(upper0) == len(x_inc0) == len(rules) == len(max_iter_bb) == B):
         raise ValueError("solve_trees_models: one entry per model in every list")
     lib = _lib.load()
@@ -111,8 +118,13 @@ def solve_trees_models(solvers, q, l, u, x0, y0, upper0, x_inc0, rules, max_iter
     infos = (_lib.TreeInfo * max(B, 1))()
     stats = _lib.ModelsStats()
     hs = (C.c_void_p * max(B, 1))(*[s._h.value for s in solvers])
-    rc = lib.miosqp_qp_solve_trees_models(B, hs, ptrs(q), ptrs(l), ptrs(u), ptrs(x0), ptrs(y0), _lib.as_d(up), ptrs(xin),
-                                          _lib.as_i(rl), _lib.as_i(mi), ptrs(x), infos, C.byref(stats))
+    if leaf_cap is None:
+        rc = lib.miosqp_qp_solve_trees_models(B, hs, ptrs(q), ptrs(l), ptrs(u), ptrs(x0), ptrs(y0), _lib.as_d(up), ptrs(xin),
+                                              _lib.as_i(rl), _lib.as_i(mi), ptrs(x), infos, C.byref(stats))
+    else:
+        rc = lib.miosqp_qp_solve_trees_models_large(B, hs, ptrs(q), ptrs(l), ptrs(u), ptrs(x0), ptrs(y0), _lib.as_d(up),
+                                                    ptrs(xin), _lib.as_i(rl), _lib.as_i(mi), int(leaf_cap), ptrs(x), infos,
+                                                    C.byref(stats))
     if rc == -5:
         return None
     _check(rc, "solve_trees_models")
@@ -620,6 +632,14 @@ class OSQP(object):
         if self._h is None:
             return 0
         return int(self._lib.miosqp_qp_tree_form(self._h))
+
+    def tree_form_large(self, leaf_cap=256):
+        """3 when `solve_trees_models(..., leaf_cap=leaf_cap)` runs this engine's tree in the reduced form
+        (miosqp_qp_tree_form_large): `tree_form()` is 0, the engine has its integer rows, root, digest and product-form
+        rows, and the packed triangle of L^-1, the iterates and a leaf list of leaf_cap places fit 160 KB of LDS; else 0."""
+        if self._h is None:
+            return 0
+        return int(self._lib.miosqp_qp_tree_form_large(self._h, int(leaf_cap)))
 
     def solve_trees_lockstep(self, q, l, u, x0, y0, upper0, x_inc0, tree_explor_rule, max_iter_bb, capacity=0,
                              node_hviol=0):
