@@ -591,6 +591,34 @@ int miosqp_qp_setup_models_auto(int32_t B, const miosqp_setup_model *models, mio
  * form and the explicit inverse at a fixed rho -- not rho_auto, coop = 1, resident = 0, fold = 0, setup_on_device = 1,
  * MIOSQP_COOP=1 or MIOSQP_RES_W=0. */
 int miosqp_qp_setup_models_eligible(int32_t n, int32_t M, const miosqp_qp_settings *settings);
+/* miosqp_qp_setup_models (rho_auto_in_launch = 0) or miosqp_qp_setup_models_auto (not 0) with a SECOND launch for the models
+ * that one workgroup of k_setup_models cannot hold (n + M > 192): what the reference does for such a model with
+ * osqp.OSQP().setup() (/root/reference/miosqp/workspace.py:63-68), and miosqp_qp_setup one model at a time with the Schur
+ * complement, the LDL^T and the inverse on one host core, build_folded, five uploads, and for the cooperative grid the
+ * (n + M)^2 inverse, Kc, the guard's read-back and a dozen buffers.  k_setup_models_large builds, one workgroup per model,
+ * f_Ad / f_Atd / f_Pd from the packed rows, S on the packed triangle in LDS (Abar read back from memory; entry (i1, i2) one
+ * fused sum over the constraint rows ascending: the host's S bit for bit), the LDL^T and the inverse with the code of
+ * k_setup_models, d2inv, Linv, LinvT, f_rows, f_GmT, the scaled bounds and the control block -- no W, no Kc, no guard.
+ * Such a model comes out as the engine miosqp_qp_setup(..., coop = 0, resident = 0, fold = 1, pers = 0) builds: the product
+ * form on the device, the iterations as captured chunks, valid for every entry of this header; miosqp_qp_tree_form_large
+ * answers 3 for it wherever it does for that engine, and its settings say coop = 0 (whoever wants the cooperative grid for a
+ * long sequential search calls miosqp_qp_setup).  Its products agree with that set-up to rounding, the dense copies and
+ * the scalings bit for bit.
+ * A model miosqp_qp_setup_models_eligible's size rule takes keeps the existing launch.  All models share one group; one
+ * upload, at most two launches (stats->launches: 1 or 2), one download, one synchronisation.  out[b] and every "(model b)" of an error text are the caller's positions.  Refused before anything is
+ * queued, beside what miosqp_qp_setup_models refuses: a large model whose shape miosqp_qp_setup_models_eligible_large does
+ * not take, with settings->rho_auto = 1 (MIOSQP_EUNSUPPORTED: rho for such a model is not chosen in the launch), or with
+ * coop = 1, resident = 1, fold = 0, pers > 0 or setup_on_device = 1; MIOSQP_COOP=1 or MIOSQP_PERS in the environment. */
+int miosqp_qp_setup_models_large(int32_t B, const miosqp_setup_model *models, miosqp_qp_engine **out,
+                                 miosqp_setup_models_stats *stats, int32_t rho_auto_in_launch);
+/* 1 when the large launch takes a model of this shape under these settings and this environment, else 0: not a shape of
+ * miosqp_qp_setup_models_eligible, the packed triangle of n variables, two rows and d within 160 KB of LDS (n <= 198),
+ * n + M <= 2048, a fixed rho, and none of coop = 1, resident = 1, fold = 0, pers > 0, setup_on_device = 1, MIOSQP_COOP=1,
+ * MIOSQP_PERS > 0.  Every (n, M) miosqp_qp_tree_form_large takes with 256 leaf places is among them. */
+int miosqp_qp_setup_models_eligible_large(int32_t n, int32_t M, const miosqp_qp_settings *settings);
+/* the SIZE rules alone, whatever the settings and the environment say: 1 a shape of miosqp_qp_setup_models (n + M <= 192),
+ * 2 a shape of the large launch of miosqp_qp_setup_models_large (n <= 198, n + M <= 2048), 0 neither */
+int miosqp_qp_setup_models_shape(int32_t n, int32_t M);
 /* groups of miosqp_qp_setup_models that are alive in this process (engines of theirs not yet cleaned up) */
 int miosqp_qp_setup_groups_live(void);
 /* the group this engine belongs to (a positive number, the same for the engines of one call), 0 for an engine of miosqp_qp_setup */

@@ -1720,18 +1720,31 @@ def solve_models(models, instances=None, info=None, polish=False, polish_guess="
     return out
 
 
-def _setup_models_own_reason(be, data, qp_settings, rho_auto_in_launch=False):
-    """why `setup_models` leaves a model to `MIOSQP.setup` (None: it goes into the launch)"""
+def _setup_models_own_reason(be, data, qp_settings, rho_auto_in_launch=False, large=False):
+    """why `setup_models` leaves a model to `MIOSQP.setup` (None: it goes into the launch; 'large' in place of None with
+    large=True: it goes into the launch for models beyond one workgroup of the existing one)"""
     if not hasattr(be, 'setup_models') or not hasattr(be, 'setup_models_eligible'):
         return 'backend without the one-launch set-up'
     if data.n_int == 0:
         return 'n_int == 0'
+    n, M = data.n, data.A.shape[0]
+    if (large and hasattr(be, 'setup_models_eligible_large') and hasattr(be, 'setup_models_shape')
+            and be.setup_models_shape(n, M) != 1):
+        # out of the existing launch for its SIZE (asked apart from settings and environment): the large launch's rules
+        if be.setup_models_shape(n, M) == 0:
+            return 'n + M = %d: beyond one workgroup of either launch' % (n + M)
+        if isinstance(qp_settings.get('rho'), str):
+            return 'rho="auto" beyond one workgroup of the launch: the large launch builds a fixed rho only'
+        if not data.P.has_canonical_format or not spa.csc_matrix(data.A).has_canonical_format:
+            return 'duplicate entries in P or A'
+        if not be.setup_models_eligible_large(n, M, qp_settings):
+            return 'settings or environment that lead to another engine form than the large launch builds'
+        return 'large'
     if isinstance(qp_settings.get('rho'), str):
         if not rho_auto_in_launch:
             return 'rho="auto"'
         # the launch chooses rho itself; everything else about the model is judged as at a fixed rho
         qp_settings = {k: v for k, v in qp_settings.items() if k != 'rho'}
-    n, M = data.n, data.A.shape[0]
     if not be.setup_models_eligible(n, M, {}):  # (the library's size rule, asked with default settings)
         return 'n + M = %d: beyond one workgroup of the launch' % (n + M)
     if not data.P.has_canonical_format or not spa.csc_matrix(data.A).has_canonical_format:
@@ -1741,7 +1754,7 @@ def _setup_models_own_reason(be, data, qp_settings, rho_auto_in_launch=False):
     return None
 
 
-def setup_models(problems, settings, qp_settings, info=None, backend=None, rho_auto=None):
+def setup_models(problems, settings, qp_settings, info=None, backend=None, rho_auto=None, large=None):
     """Set up several DIFFERENT MIQP models -- each with its own P and A -- with ONE launch for the dense set-up of all of
     them (`qp.setup_models`, miosqp_qp_setup_models: one workgroup per model builds the Schur complement, its LDL^T, the
     triangular inverse, the product form, the explicit inverse and its guard; the engines share one stream, one device
@@ -1761,15 +1774,31 @@ def setup_models(problems, settings, qp_settings, info=None, backend=None, rho_a
     (miosqp_qp_setup_models_auto: the probing iterations, the rule and the second factor are stages of the one launch).
     On a backend without that entry (the CPU oracle) such models are still set up in place.  Any other value: ValueError.
 
+    large: None -- a model beyond one workgroup of the launch (n + M > 192) is set up in its place; "device" -- a model
+    that stays out ONLY for its size goes into the call where the large rule (`qp.setup_models_eligible_large`: the packed
+    triangle of n variables within 160 KB of LDS, n <= 198; n + M <= 2048) and its settings admit it: a second launch of
+    the same call builds it (miosqp_qp_setup_models_large, k_setup_models_large: S on the packed triangle in LDS, Abar read
+    from L2; no explicit inverse, no guard) as the engine `MIOSQP.setup` builds with coop=0, resident=0, fold=1 -- the
+    product form with captured chunks, NOT the cooperative grid `MIOSQP.setup` builds by default at these sizes, which
+    iterates a single relaxation faster.  The keyword is for lists that go to `solve_models(large="device")`, whose
+    one-launch trees read nothing of the grid; for a long sequential search on one model call `MIOSQP.setup`.  Of the
+    reference benchmark's grid this takes (50,200,10), (100,200,15), (150,100,5) and (150,300,20)
+    (profiles/setup_models_large.txt).  rho_auto="device" and large="device" combine in one call; a large model with
+    rho="auto" is set up in its place (its reason in info["own"]): rho for such a model is not chosen in the launch.  On a
+    backend without the entry such models are set up in place.  Any other value: ValueError.
+
     ValueError before anything is queued, with the positions named: an empty list, a wrong number of settings, l > u, a P
     of the wrong shape.  A pivot that is not positive raises what `MIOSQP.setup` raises, with the position added; nothing
     of the call is left behind.
 
     info: a dict that is filled with batched (positions), own ({position: why}), launches, device_time, arena_bytes,
-    host_time (seconds of the call outside the library's one) and rho (the rho in use per position)."""
+    host_time (seconds of the call outside the library's one), rho (the rho in use per position) and forms
+    ({'small': .., 'large': ..}: the batched models per launch)."""
     t_call = time()
     if rho_auto not in (None, 'device'):
         raise ValueError('setup_models: rho_auto must be None or "device", not %r' % (rho_auto,))
+    if large is not None and not (isinstance(large, str) and large == 'device'):
+        raise ValueError('setup_models: large must be None or "device", not %r' % (large,))
     problems = list(problems)
     B = len(problems)
     if B == 0:
@@ -1806,10 +1835,12 @@ def setup_models(problems, settings, qp_settings, info=None, backend=None, rho_a
         raise ValueError('setup_models: Lower bound must be lower than or equal to upper bound, at position(s) %s' % crossed)
     be = backend if backend is not None else _default_backend()
     own, batched = {}, []
+    forms = dict(small=0, large=0)
     for k in range(B):
-        why = _setup_models_own_reason(be, datas[k], qp_settings[k], rho_auto == 'device')
-        if why is None:
+        why = _setup_models_own_reason(be, datas[k], qp_settings[k], rho_auto == 'device', large == 'device')
+        if why is None or why == 'large':
             batched.append(k)
+            forms['small' if why is None else 'large'] += 1
         else:
             own[k] = why
     out = [None] * B
@@ -1826,10 +1857,12 @@ def setup_models(problems, settings, qp_settings, info=None, backend=None, rho_a
                 desc.append(md)
             t0 = time()
             try:
+                kw = {}
                 if rho_auto == 'device' and any(isinstance(md['settings'].get('rho'), str) for md in desc):
-                    solvers, stats = be.setup_models(desc, rho_auto_in_launch=True)
-                else:
-                    solvers, stats = be.setup_models(desc)
+                    kw['rho_auto_in_launch'] = True
+                if forms['large']:
+                    kw['large'] = True
+                solvers, stats = be.setup_models(desc, **kw)
             except RuntimeError as ex:
                 import re
                 hit = re.search(r'\(model (\d+)', str(ex))
@@ -1856,5 +1889,5 @@ def setup_models(problems, settings, qp_settings, info=None, backend=None, rho_a
     if info is not None:
         rho = [float(m.work.solver.rho()) for m in out]
         info.update(batched=list(batched), own=dict(own), launches=launches, device_time=device_time, arena_bytes=arena_bytes,
-                    host_time=(time() - t_call) - lib_time, rho=rho)
+                    host_time=(time() - t_call) - lib_time, rho=rho, forms=forms)
     return out

@@ -104,7 +104,7 @@ miosqp::setup_models::Args setup_args_of(const miosqp_setup_model &m) {
   if (m.settings) {
     const miosqp_qp_settings &s = *m.settings;
     a.rho = s.rho; a.sigma = s.sigma; a.alpha = s.alpha; a.max_iter = s.max_iter; a.rho_auto = s.rho_auto;
-    a.coop = s.coop; a.resident = s.resident; a.fold = s.fold; a.setup_on_device = s.setup_on_device;
+    a.coop = s.coop; a.resident = s.resident; a.fold = s.fold; a.setup_on_device = s.setup_on_device; a.pers = s.pers;
   }
   a.n_int = m.n_int; a.m_orig = m.m_orig; a.i_idx = m.i_idx;
   a.l_root = m.l_root; a.u_root = m.u_root;
@@ -120,10 +120,22 @@ void stage_vec(char *slab, const miosqp::setup_models::Slot &s, int part, const 
   if (count) memcpy(slab + s.part[part].off, src, count * sizeof(T));
 }
 
+// the switches of the environment under which miosqp_qp_setup would NOT build the engine of the large launch (product
+// form, captured chunks; neither cooperative grid nor persistent kernel)
+bool setup_models_large_env_ok() {
+  if (const char *ev = getenv("MIOSQP_COOP"))
+    if (atoi(ev) == 1) return false;
+  if (const char *ev = getenv("MIOSQP_PERS"))
+    if (atoi(ev) > 0) return false;
+  return true;
+}
+
 // rho_auto_in_launch (miosqp_qp_setup_models_auto): models with settings->rho_auto = 1 are taken, and when there is one
-// the launch is k_setup_models_auto
+// the launch is k_setup_models_auto.  large (miosqp_qp_setup_models_large): a model that k_setup_models does not take for
+// its size is built by k_setup_models_large, a second launch of the same call, as the engine miosqp_qp_setup builds with
+// coop = 0, resident = 0, fold = 1, pers = 0; the table holds the small models first.
 int setup_models_run(int32_t B, const miosqp_setup_model *ms, miosqp_qp_engine **out, miosqp_setup_models_stats *stats,
-                     bool rho_auto_in_launch) {
+                     bool rho_auto_in_launch, bool large = false) {
   namespace sm = miosqp::setup_models;
   static_assert(sizeof(Ctrl) <= sm::CTRL_BYTES, "Ctrl fits its place in the arena and the slab");
   // ---- refused before anything is queued ----
@@ -132,7 +144,7 @@ int setup_models_run(int32_t B, const miosqp_setup_model *ms, miosqp_qp_engine *
     if (B >= 1 && ms)
       for (int b = 0; b < B; b++) av.push_back(setup_args_of(ms[b]));
     std::string err;
-    if (int rc = sm::check_args(B, ms ? av.data() : nullptr, out, stats, err, rho_auto_in_launch)) {
+    if (int rc = sm::check_args(B, ms ? av.data() : nullptr, out, stats, err, rho_auto_in_launch, large)) {
       g_err = err;
       return rc;
     }
@@ -142,8 +154,19 @@ int setup_models_run(int32_t B, const miosqp_setup_model *ms, miosqp_qp_engine *
       g_err = "setup_models: the row indices of P and A must ascend strictly within a column, no entry twice (model " + std::to_string(b) + ")";
       return MIOSQP_EUNSUPPORTED;
     }
-  if (!setup_models_env_ok()) {
+  std::vector<int> form((size_t)B, sm::FORM_SMALL);
+  int n_large = 0;
+  for (int b = 0; b < B; b++)
+    if (large && !sm::eligible_shape(ms[b].n, ms[b].M)) {
+      form[(size_t)b] = sm::FORM_LARGE;
+      n_large++;
+    }
+  if (n_large < B && !setup_models_env_ok()) {
     g_err = "setup_models: MIOSQP_COOP=1 or MIOSQP_RES_W=0 asks for another engine form than the launch builds";
+    return MIOSQP_EUNSUPPORTED;
+  }
+  if (n_large > 0 && !setup_models_large_env_ok()) {
+    g_err = "setup_models: MIOSQP_COOP=1 or MIOSQP_PERS asks for another engine form than the large launch builds";
     return MIOSQP_EUNSUPPORTED;
   }
   for (int b = 1; b < B; b++)
@@ -207,6 +230,7 @@ int setup_models_run(int32_t B, const miosqp_setup_model *ms, miosqp_qp_engine *
     e->M = m.M;
     e->st = *m.settings;
     if (e->st.check_termination <= 0 || e->st.check_termination > e->st.max_iter) e->st.check_termination = e->st.max_iter;
+    if (form[(size_t)b] == sm::FORM_LARGE) e->st.coop = 0;  // (the engine that comes out is not the cooperative grid's)
     e->setup_on_device = false;
     miosqp::scale_problem(m.n, m.M, m.Pp, m.Pi, m.Px, m.Ap, m.Ai, m.Ax, m.q, m.settings->scaling, e->sc);
     miosqp::Factor &f = e->fa;  // the rows; Linv / LinvT stay empty on the host, as where the device keeps them
@@ -218,7 +242,7 @@ int setup_models_run(int32_t B, const miosqp_setup_model *ms, miosqp_qp_engine *
     e->A_raw.assign(m.Ax, m.Ax + m.Ap[m.n]);
     e->nnzPtriu = (int64_t)e->sc.Pi.size();
     sh[(size_t)b] = sm::Shape{m.n, m.M, f.panel_by_var.idx.size(), f.panel_by_con.idx.size(), f.Pbar.idx.size(), f.Praw.idx.size(),
-                              m.settings->rho_auto ? 1 : 0};
+                              m.settings->rho_auto ? 1 : 0, form[(size_t)b]};
   }
   const sm::Plan P = sm::plan(sh, sizeof(SetupModel));
   tick("host: equilibration + packed rows");
@@ -300,8 +324,9 @@ int setup_models_run(int32_t B, const miosqp_setup_model *ms, miosqp_qp_engine *
     d.f_rows2 = d.f_rows;
     d.ldf2 = d.ldf;
     d.ldw = (n + M + 7) & ~7;
-    d.W = arena_at<double>(dv, s, sm::W_);
-    d.Kc = arena_at<double>(dv, s, sm::KC);
+    const bool lg = form[(size_t)b] == sm::FORM_LARGE;  // (no W, no Kc: their parts have no bytes)
+    d.W = lg ? nullptr : arena_at<double>(dv, s, sm::W_);
+    d.Kc = lg ? nullptr : arena_at<double>(dv, s, sm::KC);
     d.l = arena_at<double>(dv, s, sm::L_); d.u = arena_at<double>(dv, s, sm::U_); d.x = arena_at<double>(dv, s, sm::X_);
     d.z = arena_at<double>(dv, s, sm::Z_); d.y = arena_at<double>(dv, s, sm::Y_); d.wh = arena_at<double>(dv, s, sm::WH);
     d.rx = d.wh + M;
@@ -315,7 +340,7 @@ int setup_models_run(int32_t B, const miosqp_setup_model *ms, miosqp_qp_engine *
     d.out_x = arena_at<double>(dv, s, sm::OUT);
     d.out_y = d.out_x + n;
     d.i_idx = arena_at<int>(dv, s, sm::I_IDX);
-    SetupModel &t = tab_h[b];
+    SetupModel &t = tab_h[s.entry];
     sm::IO &io = t.io;
     io.n = n; io.M = M; io.ld = d.ld; io.ldf = d.ldf; io.ldn = d.ldn; io.ldm = d.ldm; io.ldw = d.ldw;
     io.rho = d.rho; io.sigma = d.sigma;
@@ -325,7 +350,7 @@ int setup_models_run(int32_t B, const miosqp_setup_model *ms, miosqp_qp_engine *
     io.d2inv = arena_at<double>(dv, s, sm::D2INV); io.Linv = arena_at<double>(dv, s, sm::LINV); io.LinvT = arena_at<double>(dv, s, sm::LINVT);
     io.f_rows = arena_at<double>(dv, s, sm::F_ROWS); io.f_GmT = arena_at<double>(dv, s, sm::F_GMT); io.f_Ad = arena_at<double>(dv, s, sm::F_AD);
     io.f_Atd = arena_at<double>(dv, s, sm::F_ATD); io.f_Pd = arena_at<double>(dv, s, sm::F_PD);
-    io.W = arena_at<double>(dv, s, sm::W_); io.Kc = arena_at<double>(dv, s, sm::KC);
+    io.W = const_cast<double *>(d.W); io.Kc = const_cast<double *>(d.Kc);
     io.rec = reinterpret_cast<sm::Record *>(dv + s.rec);
     t.ctrl = d.ctrl;
     sm::Auto &au = t.au;
@@ -362,25 +387,31 @@ int setup_models_run(int32_t B, const miosqp_setup_model *ms, miosqp_qp_engine *
     e->ev_chunk[0] = r.ev_chunk[0]; e->ev_chunk[1] = r.ev_chunk[1];
   }
   tick("host: upload image, table, events");
-  // ---- one upload, one launch, one download, one synchronisation ----
-  if (any_auto) SMCHK(lds_limit_once((const void *)k_setup_models_auto, 15));
-  else SMCHK(lds_limit_once((const void *)k_setup_models, 14));
+  // ---- one upload, one launch per form, one download, one synchronisation ----
+  if (P.n_small) {
+    if (any_auto) SMCHK(lds_limit_once((const void *)k_setup_models_auto, 15));
+    else SMCHK(lds_limit_once((const void *)k_setup_models, 14));
+  }
+  if (P.n_large) SMCHK(lds_limit_once((const void *)k_setup_models_large, 17));
   miosqp_qp_engine *e0 = eng[0];
   SMCHK(hipEventRecord(e0->ev0, grp->stream));
   SMCHK(hipMemcpyAsync(dv, hs, P.up_bytes, hipMemcpyHostToDevice, grp->stream));
-  if (any_auto)
-    hipLaunchKernelGGL(k_setup_models_auto, dim3((unsigned)B), dim3(sm::THREADS), P.lds_bytes, grp->stream,
+  if (P.n_small && any_auto)
+    hipLaunchKernelGGL(k_setup_models_auto, dim3((unsigned)P.n_small), dim3(sm::THREADS), P.lds_bytes, grp->stream,
                        reinterpret_cast<const SetupModel *>(dv));
-  else
-    hipLaunchKernelGGL(k_setup_models, dim3((unsigned)B), dim3(sm::THREADS), P.lds_bytes, grp->stream,
+  else if (P.n_small)
+    hipLaunchKernelGGL(k_setup_models, dim3((unsigned)P.n_small), dim3(sm::THREADS), P.lds_bytes, grp->stream,
                        reinterpret_cast<const SetupModel *>(dv));
+  if (P.n_large)
+    hipLaunchKernelGGL(k_setup_models_large, dim3((unsigned)P.n_large), dim3(sm::THREADS), P.lds_bytes_large, grp->stream,
+                       reinterpret_cast<const SetupModel *>(dv) + P.n_small);
   SMCHK(hipGetLastError());
   SMCHK(hipMemcpyAsync(hs + P.pin_rec, dv + P.rec_off, P.rec_bytes, hipMemcpyDeviceToHost, grp->stream));
   SMCHK(hipEventRecord(e0->ev1, grp->stream));
   SMCHK(hipStreamSynchronize(grp->stream));
   float ms_dev = 0;
   SMCHK(hipEventElapsedTime(&ms_dev, e0->ev0, e0->ev1));
-  tick(any_auto ? "upload, k_setup_models_auto, records back" : "upload, k_setup_models, records back");
+  tick(P.n_large ? "upload, set-up launches, records back" : any_auto ? "upload, k_setup_models_auto, records back" : "upload, k_setup_models, records back");
   const sm::Record *rec = reinterpret_cast<const sm::Record *>(hs + P.pin_rec);
   for (int b = 0; b < B; b++)
     if (rec[b].bad_pivot) {
@@ -438,9 +469,29 @@ int setup_models_run(int32_t B, const miosqp_setup_model *ms, miosqp_qp_engine *
     e->tpr_ff = pick_tpr(M + 0.5 * n);
     e->tpr_fx = pick_tpr(0.5 * n);
     e->tpr_fc = pick_tpr((double)n);
-    size_t need = resident_lds_doubles(n, M, true) * sizeof(double);
     e->sp_nnzA = f.panel_by_con.idx.size();
     e->sp_nnzP = f.Pbar.idx.size();
+    if (form[(size_t)b] == sm::FORM_LARGE) {
+      // the fields miosqp_qp_setup sets with coop = 0, resident = 0, fold = 1, pers = 0: the product form on the device, the
+      // iterations as captured chunks (d.W and d.Kc are NULL: the graphs hold Dev by value)
+      e->coop_cus = cus;
+      if (const char *ev = getenv("MIOSQP_COOP_DBG")) d.coop_dbg = atoi(ev);
+      tuning_from_env(e);
+      e->chunk = e->st.check_termination;
+      e->tail_iters = e->st.max_iter % e->chunk;
+      int rc = capture_chunk(e, e->chunk, &e->g_full, &e->x_full);
+      if (!rc && e->tail_iters > 0) rc = capture_chunk(e, e->tail_iters, &e->g_tail, &e->x_tail);
+      if (!rc && m.n_int >= 0) {
+        rc = miosqp_qp_set_integer_rows(e, m.n_int, m.i_idx, m.m_orig);
+        if (!rc && m.l_root) rc = miosqp_qp_set_root(e, m.l_root, m.u_root, m.eps_int_feas, m.eps_lin);
+      }
+      if (rc) {
+        g_err += " (model " + std::to_string(b) + ")";
+        return fail(rc < 0 ? rc : MIOSQP_EARG);
+      }
+      continue;
+    }
+    size_t need = resident_lds_doubles(n, M, true) * sizeof(double);
     const bool sp_on = !(getenv("MIOSQP_RES_SP") && atoi(getenv("MIOSQP_RES_SP")) == 0);
     const size_t sp_bytes = res_sp_doubles(e->sp_nnzA, e->sp_nnzP, n, M) * sizeof(double);
     if (sp_on && need + sp_bytes <= 150 * 1024) {
@@ -496,14 +547,14 @@ int setup_models_run(int32_t B, const miosqp_setup_model *ms, miosqp_qp_engine *
   for (int b = 0; b < B; b++) out[b] = eng[(size_t)b];
   const double wall_s = wall() - t_begin;
   stats->models = B;
-  stats->launches = 1;
+  stats->launches = (P.n_small ? 1 : 0) + (P.n_large ? 1 : 0);
   stats->device_mallocs = (int32_t)(g_made_device_mallocs - made0[0]);  // (with what the engines' own pools took, if anything)
   stats->host_mallocs = (int32_t)(g_made_host_mallocs - made0[1]);
   stats->streams = (int32_t)(g_made_streams - made0[2]);
   stats->reserved = 0;
   stats->arena_bytes = (int64_t)P.total_bytes;
   stats->pinned_bytes = (int64_t)P.pin_bytes;
-  stats->lds_bytes = (int64_t)P.lds_bytes;
+  stats->lds_bytes = (int64_t)std::max(P.lds_bytes, P.lds_bytes_large);
   stats->device_time = 1e-3 * ms_dev;
   stats->run_time = wall_s;
   if (t_on) fprintf(stderr, "[miosqp setup_models] %-36s %8.3f ms  (%d models)\n", "miosqp_qp_setup_models, all of it", 1e3 * wall_s, (int)B);

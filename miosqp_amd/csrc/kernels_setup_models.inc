@@ -8,6 +8,8 @@
 // miosqp_qp_setup does with two set-ups and fifty iterations on a throw-away engine (the rho-once recipe there): the
 // probing iterations on the first factor in LDS, the rule, the factor again at the chosen rho, the panel's values.  A
 // kernel of its own (body_auto), so that k_setup_models stays the code it was.
+// k_setup_models_large: a model beyond n + M = 192 (setup_models_large_body.hpp): only the packed triangle in LDS, Abar
+// read from memory; what miosqp_qp_setup(coop = 0, resident = 0, fold = 1, pers = 0) builds -- no W, no Kc, no guard.
 // ------------------------------------------------------------------------------------------
 struct SetupModel {
   miosqp::setup_models::IO io;  // final pointers into the call's arena
@@ -48,4 +50,12 @@ __global__ __launch_bounds__(miosqp::setup_models::THREADS) void k_setup_models_
   if (threadIdx.x == 0) setup_models_reset_ctrl(m.ctrl);
   SetupExecDevice x;
   miosqp::setup_models::body_auto(m.io, m.au, sm_lds, x);
+}
+
+__global__ __launch_bounds__(miosqp::setup_models::THREADS) void k_setup_models_large(const SetupModel *__restrict__ tab) {
+  extern __shared__ double sm_lds[];
+  const SetupModel &m = tab[blockIdx.x];
+  if (threadIdx.x == 0) setup_models_reset_ctrl(m.ctrl);
+  SetupExecDevice x;
+  miosqp::setup_models::body_large(m.io, sm_lds, x);
 }

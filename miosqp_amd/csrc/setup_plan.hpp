@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "setup_models_body.hpp"  // eligible_shape, lds_doubles, Record (plain C++ too)
+#include "setup_models_large_body.hpp"  // eligible_shape_large, lds_doubles_large: the launch for models beyond n + M = 192
 
 namespace miosqp {
 namespace setup_models {
@@ -26,7 +27,7 @@ struct Args {
   const double *l = nullptr, *u = nullptr;
   const void *settings = nullptr;
   double rho = 0, sigma = 0, alpha = 0;
-  int max_iter = 0, rho_auto = 0, coop = -1, resident = -1, fold = -1, setup_on_device = -1;
+  int max_iter = 0, rho_auto = 0, coop = -1, resident = -1, fold = -1, setup_on_device = -1, pers = -1;
   int n_int = -1, m_orig = 0;  // n_int < 0: no integer rows in the descriptor
   const void *i_idx = nullptr;
   const double *l_root = nullptr, *u_root = nullptr;
@@ -44,6 +45,13 @@ inline bool eligible_shape_auto(int n, int M) {
   return eligible_shape(n, M) && lds_doubles_auto(n, M) * sizeof(double) <= LDS_LIMIT;
 }
 
+// A model beyond n + M = 192 (miosqp_qp_setup_models_large) comes out as the engine miosqp_qp_setup builds with coop = 0,
+// resident = 0, fold = 1, pers = 0: settings that ask for another form keep it out.  rho is fixed: choosing it for such
+// a model inside the launch is not built.
+inline bool eligible_settings_large(const Args &a) {
+  return a.rho_auto == 0 && a.setup_on_device != 1 && a.fold != 0 && a.coop != 1 && a.resident != 1 && a.pers <= 0;
+}
+
 // The launch writes the dense copies of Abar and Pbar entry by entry where the per-model set-up sums what a matrix stores
 // twice: a column whose row indices do not ascend strictly (an entry twice, or unsorted) keeps its model out of the launch.
 inline bool csc_strictly_ascending(int cols, const int32_t *ptr, const int32_t *idx) {
@@ -53,9 +61,10 @@ inline bool csc_strictly_ascending(int cols, const int32_t *ptr, const int32_t *
   return true;
 }
 
-// 0, or the error code with `err` naming the model's position
+// 0, or the error code with `err` naming the model's position.  large (miosqp_qp_setup_models_large): a model that the
+// small launch does not take for its SIZE is judged by the rules of the large one.
 inline int check_args(int32_t B, const Args *a, const void *out, const void *stats, std::string &err,
-                      bool rho_auto_in_launch = false) {
+                      bool rho_auto_in_launch = false, bool large = false) {
   const std::string who = "setup_models: ";
   if (B < 1) {
     err = who + "B must be at least 1";
@@ -93,6 +102,23 @@ inline int check_args(int32_t B, const Args *a, const void *out, const void *sta
         err = who + "lower bound above upper bound" + at;
         return ERR_ARG;
       }
+    if (large && !eligible_shape(m.n, m.M)) {
+      if (!eligible_shape_large(m.n, m.M)) {
+        err = who + "neither launch takes this model: the packed triangle of n variables within " +
+              std::to_string(LDS_LIMIT / 1024) + " KB of LDS (n <= 198) and n + M <= " + std::to_string(MAX_NM_LARGE) + at;
+        return ERR_UNSUPPORTED;
+      }
+      if (m.rho_auto != 0) {
+        err = who + "rho_auto = 1 beyond n + M = " + std::to_string(MAX_NM) + ": the large launch builds a fixed rho only" + at;
+        return ERR_UNSUPPORTED;
+      }
+      if (!eligible_settings_large(m)) {
+        err = who + "the large launch does not take this model: it builds the engine of coop = 0, resident = 0, fold = 1, "
+                    "pers = 0 on the host's set-up path (setup_on_device != 1)" + at;
+        return ERR_UNSUPPORTED;
+      }
+      continue;
+    }
     if (!eligible_shape(m.n, m.M) || !eligible_settings(m, rho_auto_in_launch) ||
         (rho_auto_in_launch && m.rho_auto && !eligible_shape_auto(m.n, m.M))) {
       err = who + "the launch does not take this model: n + M <= " + std::to_string(MAX_NM) +
@@ -104,11 +130,15 @@ inline int check_args(int32_t B, const Args *a, const void *out, const void *sta
   return 0;
 }
 
+constexpr int FORM_SMALL = 0;  // k_setup_models / k_setup_models_auto
+constexpr int FORM_LARGE = 1;  // k_setup_models_large
+
 struct Shape {
   int n = 0, M = 0;
   size_t nv = 0, nc = 0, npb = 0, npr = 0;  // lengths of the packed rows as stored (padding included): by variable, by
                                             // constraint, Pbar, Praw
   int rho_auto = 0;                         // 1: the launch chooses this model's rho (LDS for the probing iterations)
+  int form = FORM_SMALL;                    // which launch builds it (FORM_LARGE: no W, no Kc, the large LDS rule)
 };
 
 // the arrays of one model, in the order they lie in the arena
@@ -133,6 +163,7 @@ struct Span {
 struct Slot {
   Span part[NPARTS];
   size_t rec = 0;  // this model's Record
+  size_t entry = 0;  // its place in the table: small models first, then the large ones, each in the caller's order
   // the pinned slab: h_in (in_cap doubles), h_out (out_cap doubles), h_ctrl, h_ctrl2 (two control blocks)
   size_t pin_in = 0, pin_out = 0, pin_ctrl = 0, pin_ctrl2 = 0, in_cap = 0, out_cap = 0;
 };
@@ -148,6 +179,8 @@ struct Plan {
   size_t pin_bytes = 0;            // the slab: max(upload image, the engines' staging) + records
   size_t pin_rec = 0;              // where the records land in the slab
   size_t lds_bytes = 0;            // dynamic LDS of the launch: the largest model's
+  size_t n_small = 0, n_large = 0; // table entries [0, n_small) go to the small launch, [n_small, n_small + n_large) to the large one
+  size_t lds_bytes_large = 0;      // dynamic LDS of the large launch
 };
 
 inline size_t round_up(size_t v, size_t to) { return (v + to - 1) / to * to; }
@@ -167,7 +200,9 @@ inline void part_bytes(const Shape &s, size_t (&by)[NPARTS]) {
   by[Q] = arr(n, F); by[QRAW] = arr(n, F); by[RAW] = arr(3 * M + n, F);
   by[LINV] = arr(n * ld, F); by[LINVT] = arr(n * ld, F); by[D2INV] = arr(n, F);
   by[F_ROWS] = arr(n * ldf, F); by[F_GMT] = arr(M * ldn, F); by[F_AD] = arr(M * ldn, F); by[F_ATD] = arr(n * ldm, F);
-  by[F_PD] = arr(n * ldn, F); by[W_] = arr(N * ldw, F); by[KC] = arr(N * ldw, F);
+  by[F_PD] = arr(n * ldn, F);
+  const bool w = s.form != FORM_LARGE;  // (the large form builds neither: 2 x 1.7 MB at n + M = 470)
+  by[W_] = w ? arr(N * ldw, F) : 0; by[KC] = w ? arr(N * ldw, F) : 0;
   by[L_] = arr(M, F); by[U_] = arr(M, F); by[X_] = arr(n, F); by[Z_] = arr(M, F); by[Y_] = arr(M, F); by[WH] = arr(N, F);
   by[CV] = arr(n, F); by[UT] = arr(n, F); by[XT] = arr(n, F); by[DX] = arr(n, F); by[DY] = arr(M, F);
   by[SM] = arr(8 * M, F); by[SN] = arr(10 * n, F); by[XI] = arr(n, F); by[XIS] = arr(n, F);
@@ -191,9 +226,17 @@ inline Plan plan(const std::vector<Shape> &sh, size_t entry_bytes) {
       P.slot[b].part[k] = Span{at, one[k]};
       at += one[k];
     }
-    const size_t lds = (sh[b].rho_auto ? lds_doubles_auto(sh[b].n, sh[b].M) : lds_doubles(sh[b].n, sh[b].M)) * sizeof(double);
-    if (lds > P.lds_bytes) P.lds_bytes = lds;
+    if (sh[b].form == FORM_LARGE) {
+      const size_t lds = lds_doubles_large(sh[b].n, sh[b].M) * sizeof(double);
+      if (lds > P.lds_bytes_large) P.lds_bytes_large = lds;
+      P.n_large++;
+    } else {
+      const size_t lds = (sh[b].rho_auto ? lds_doubles_auto(sh[b].n, sh[b].M) : lds_doubles(sh[b].n, sh[b].M)) * sizeof(double);
+      if (lds > P.lds_bytes) P.lds_bytes = lds;
+      P.n_small++;
+    }
   }
+  for (size_t b = 0, s = 0, l = P.n_small; b < B; b++) P.slot[b].entry = sh[b].form == FORM_LARGE ? l++ : s++;
   P.up_bytes = at;
   for (size_t b = 0; b < B; b++)
     for (int k = FIRST_PRODUCT; k < NPARTS; k++) {

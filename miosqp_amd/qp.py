@@ -220,12 +220,26 @@ def setup_models_eligible(n, m, settings):
     return bool(_lib.load().miosqp_qp_setup_models_eligible(int(n), int(m), C.byref(s)))
 
 
+def setup_models_eligible_large(n, m, settings):
+    """Does the large launch of setup_models(..., large=True) take a model of n variables and m rows under these
+    settings and this environment: a model beyond n + M = 192 whose packed triangle one workgroup holds, with a fixed rho
+    and settings that allow the engine of coop=0, resident=0, fold=1?  (miosqp_qp_setup_models_eligible_large)"""
+    s = settings if isinstance(settings, _lib.Settings) else _settings_from_kwargs(settings)
+    return bool(_lib.load().miosqp_qp_setup_models_eligible_large(int(n), int(m), C.byref(s)))
+
+
+def setup_models_shape(n, m):
+    """The size rules of setup_models alone, whatever settings and environment say: 1 a shape of the existing launch
+    (n + M <= 192), 2 a shape of the large launch (n <= 198, n + M <= 2048), 0 neither (miosqp_qp_setup_models_shape)"""
+    return int(_lib.load().miosqp_qp_setup_models_shape(int(n), int(m)))
+
+
 def setup_groups_live():
     """groups of setup_models that are alive in this process (miosqp_qp_setup_groups_live)"""
     return int(_lib.load().miosqp_qp_setup_groups_live())
 
 
-def setup_models(models, rho_auto_in_launch=False):
+def setup_models(models, rho_auto_in_launch=False, large=False):
     """The set-up of several DIFFERENT small models in ONE launch (miosqp_qp_setup_models): the dense part of every
     model -- Schur complement, LDL^T, triangular inverse, product form, explicit inverse, its guard -- by one workgroup
     per model; the engines share one stream, one device arena and one pinned slab.
@@ -233,6 +247,12 @@ def setup_models(models, rho_auto_in_launch=False):
     rho_auto_in_launch=True (miosqp_qp_setup_models_auto): models whose settings say rho="auto" are taken too, mixed with
     fixed-rho ones as they come; the workgroup that builds such a model runs the fifty probing iterations, applies the
     rule and builds the factor again at the rho it chose (OSQP.rho() reports it).  Without it such a model is refused.
+
+    large=True (miosqp_qp_setup_models_large): a model beyond n + M = 192 (setup_models_eligible_large) is taken too, by a
+    second launch of the same call that keeps only the packed triangle in LDS; it comes out as the engine that
+    OSQP.setup(..., coop=0, resident=0, fold=1) builds (product form, no explicit inverse; tree_form_large answers 3 for
+    it where it does for that engine).  One group, one upload, at most two launches (stats.launches).  Such a model with
+    rho="auto" is refused.
 
     models: dicts with P, q, A, l, u (as OSQP.setup takes them), settings (a dict of OSQP.setup's keywords), and
     optionally i_idx with m_orig (set_integer_rows is applied) and root = (l_root, u_root, eps_int_feas, eps_lin)
@@ -274,8 +294,11 @@ def setup_models(models, rho_auto_in_launch=False):
         shapes.append((n, m, s))
     hs = (C.c_void_p * max(B, 1))()
     stats = _lib.SetupModelsStats()
-    entry = lib.miosqp_qp_setup_models_auto if rho_auto_in_launch else lib.miosqp_qp_setup_models
-    _check(entry(B, desc, hs, C.byref(stats)), "setup_models")
+    if large:
+        _check(lib.miosqp_qp_setup_models_large(B, desc, hs, C.byref(stats), 1 if rho_auto_in_launch else 0), "setup_models")
+    else:
+        entry = lib.miosqp_qp_setup_models_auto if rho_auto_in_launch else lib.miosqp_qp_setup_models
+        _check(entry(B, desc, hs, C.byref(stats)), "setup_models")
     out = []
     for k, (n, m, s) in enumerate(shapes):
         g = OSQP()
