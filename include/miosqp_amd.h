@@ -521,6 +521,44 @@ int miosqp_qp_polish_models(int32_t B, miosqp_qp_engine *const *engines, const d
  * 160 KB of LDS), 0 otherwise or for a NULL engine: what a caller asks before it puts a model into the list. */
 int miosqp_qp_polish_models_fits(miosqp_qp_engine *e);
 
+/* ---- ... also for models beyond one workgroup's LDS (opt-in) -------------------------------------------
+ * The third leg of the "own P and A per MIQP" pattern for the models miosqp_qp_polish_models does not take (more than
+ * 160 KB of LDS, or M > 256: of the reference benchmark's grid (100,200,15), (150,100,5), (150,300,20); the reference polishes
+ * per model through qp_settings, miosqp/workspace.py:67-68, after miosqp/solver.py:174-212).  miosqp_qp_polish_models_large is
+ * miosqp_qp_polish_models with the kernel of miosqp_qp_polish_many_large in table-driven form (k_pol_many_gm): W
+ * workgroups, W = min(B, two per compute unit, 1 GiB / the largest slab), workgroup w polishes models w, w + W, .. one
+ * after the other, each from classification to record in slab w of device scratch, which is sized for the largest model
+ * of the call.  Model b is exactly what miosqp_qp_polish_many_large(engines[b], 1, q[b], ...) answers with the same y --
+ * info[b], x_out[b], y_out[b], cls_out[b] bit for bit, whatever B and W are and wherever the model sits (the kernel's
+ * sums depend on (n, M) and the data alone; no floating-point atomics); device_time / run_time are the call's totals.
+ * The arguments are those of miosqp_qp_polish_models: q[b] NULL is engines[b]'s current cost, y[b] NULL the device's
+ * guess by the same rule (0 on equality and free rows, otherwise -tau / +tau by the nearer bound; needs tau > 0), which
+ * is written to the record's y slot, so a rejection returns it.  It takes every engine form miosqp_qp_polish_many_large
+ * takes -- the cooperative grid, the product form of miosqp_qp_setup_models_large, and small models as well.
+ * One upload, ONE launch, one download, one synchronisation on engines[0]'s stream; work queued on the other engines'
+ * streams is waited for first.  No engine's polish scratch is built or touched: the arena is
+ * [table | per model: rows of A by constraint, rows of A^T by variable, q, l, u, x, y | per model: record | W slabs],
+ * the arena of miosqp_qp_solve_trees_models with the same ownership (engines[0]'s, released by its miosqp_qp_cleanup);
+ * the slabs are device-only and take no room in the pinned mirror.  An engine that already holds the single polish's
+ * scratch lends its two copies of A instead.
+ * Refused before anything is queued exactly as miosqp_qp_polish_models refuses, in the same order, the text naming the
+ * model; MIOSQP_EUNSUPPORTED (the caller polishes that model on its own) for a model beyond the slab limits -- n > 512,
+ * M > 65536 or one slab beyond the budget -- or whose rows on the device do not follow the set-up's order.
+ * miosqp_qp_polish_models_large_fits: 1 when the entry takes this engine's sizes, 0 otherwise or for a NULL engine. */
+typedef struct miosqp_polish_models_large_stats {
+  int32_t launches, models, workgroups, pad; /* 1 (0 after a late refusal), B, W, 0 */
+  int64_t slab_bytes;   /* one workgroup's slab */
+  int64_t arena_bytes;  /* staged parts + records + slabs */
+  double device_time, run_time, upload_time, launch_time, download_time; /* as in miosqp_polish_models_stats */
+} miosqp_polish_models_large_stats;
+
+int miosqp_qp_polish_models_large(int32_t B, miosqp_qp_engine *const *engines, const double *const *q, const double *const *l,
+                                  const double *const *u, const double *const *x, const double *const *y, double tau,
+                                  const double *delta, const int32_t *refine_iter, const int32_t *repair_iter,
+                                  double *const *x_out, double *const *y_out, int8_t *const *cls_out,
+                                  miosqp_polish_repair_info *info, miosqp_polish_models_large_stats *stats);
+int miosqp_qp_polish_models_large_fits(miosqp_qp_engine *e);
+
 /* ---- set-up of many small models in ONE launch -----------------------------------------------------------
  * What the reference does once per MIQP with osqp.OSQP().setup() (/root/reference/miosqp/workspace.py:63-68), for B
  * models with their own P and A at once: the equilibration and the row packing stay on the host, per model, exactly as

@@ -48,6 +48,13 @@ class PolishModelsStats(C.Structure):
                 ("launch_time", C.c_double), ("download_time", C.c_double)]
 
 
+class PolishModelsLargeStats(C.Structure):
+    _fields_ = [("launches", C.c_int32), ("models", C.c_int32), ("workgroups", C.c_int32), ("pad", C.c_int32),
+                ("slab_bytes", C.c_int64), ("arena_bytes", C.c_int64), ("device_time", C.c_double),
+                ("run_time", C.c_double), ("upload_time", C.c_double), ("launch_time", C.c_double),
+                ("download_time", C.c_double)]
+
+
 class SetupModel(C.Structure):
     _fields_ = [("n", C.c_int32), ("M", C.c_int32), ("Pp", ip), ("Pi", ip), ("Px", dp), ("Ap", ip), ("Ai", ip), ("Ax", dp),
                 ("q", dp), ("l", dp), ("u", dp), ("settings", C.POINTER(Settings)), ("n_int", C.c_int32), ("m_orig", C.c_int32),
@@ -172,6 +179,10 @@ SYMBOLS = {
     "miosqp_qp_polish_models": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), dpp, dpp, dpp, dpp, dpp, C.c_double, dp, ip, ip, dpp,
                                           dpp, C.POINTER(C.c_void_p), C.POINTER(PolishRepairInfo), C.POINTER(PolishModelsStats)]),
     "miosqp_qp_polish_models_fits": (C.c_int, [C.c_void_p]),
+    "miosqp_qp_polish_models_large": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), dpp, dpp, dpp, dpp, dpp, C.c_double, dp, ip, ip,
+                                                dpp, dpp, C.POINTER(C.c_void_p), C.POINTER(PolishRepairInfo),
+                                                C.POINTER(PolishModelsLargeStats)]),
+    "miosqp_qp_polish_models_large_fits": (C.c_int, [C.c_void_p]),
     "miosqp_qp_setup_models": (C.c_int, [C.c_int32, C.POINTER(SetupModel), C.POINTER(C.c_void_p), C.POINTER(SetupModelsStats)]),
     "miosqp_qp_setup_models_auto": (C.c_int, [C.c_int32, C.POINTER(SetupModel), C.POINTER(C.c_void_p), C.POINTER(SetupModelsStats)]),
     "miosqp_qp_setup_models_large": (C.c_int, [C.c_int32, C.POINTER(SetupModel), C.POINTER(C.c_void_p), C.POINTER(SetupModelsStats),

@@ -1500,11 +1500,24 @@ def _polish_models_own_reason(work):
     if getattr(work, '_no_polish_many', False):
         return 'polish_many declined this model before'
     if not work.solver.polish_models_fits():
-        return 'beyond one workgroup'
+        return _BEYOND_ONE_WORKGROUP
     return None
 
 
-def polish_models(models, instances, results, tau=None, repair_iter=20, guess="host", info=None):
+_BEYOND_ONE_WORKGROUP = 'beyond one workgroup'
+
+
+def _polish_models_large_ok(work):
+    """whether a model that `polish_models` leaves out goes into the launch of large="device": it stays out for its size
+    alone (a `_no_polish_many` that a declined `polish_many` left on such a model says the same), the backend has the
+    entry, the sizes are within the slabs and `polish_many_large` has not declined it"""
+    if _polish_models_own_reason(work) == 'backend without polish_models' or work.solver.polish_models_fits():
+        return False
+    return (hasattr(work.backend, 'polish_models_large') and hasattr(work.solver, 'polish_models_large_fits')
+            and not getattr(work, '_no_polish_many_large', False) and work.solver.polish_models_large_fits())
+
+
+def polish_models(models, instances, results, tau=None, repair_iter=20, guess="host", info=None, large=None):
     """The list form of `MIOSQP.polish_many`: polishes the answers of `solve_models(models, instances)` in place, the
     incumbents of all models in ONE device call (`qp.polish_models`, miosqp_qp_polish_models: one upload, one launch,
     workgroup b polishes model b).  It replaces the loop `models[k].polish_many([instances[k]], [results[k]])`, whose
@@ -1524,8 +1537,22 @@ def polish_models(models, instances, results, tau=None, repair_iter=20, guess="h
     A model goes to its own `polish_many`, in place, when its backend has no `polish_models` (the CPU oracle), its
     `_no_polish_many` is set, its sizes are beyond one workgroup, or the library declines the call.
 
-    ValueError: list lengths that differ, tau not positive, another `guess`.  info: a dict that is filled with polished
-    (positions that went into a launch), polish_own ({position: why}), polish_launches and polish_device_time."""
+    large=None (the default): as above.  large="device": a model that stays out ONLY because it is beyond one workgroup
+    (more than 160 KB of LDS, or M > 256) goes into a second group, polished by ONE more launch
+    (`qp.polish_models_large`, miosqp_qp_polish_models_large: workgroups take the models one after the other, each in
+    a slab of device scratch), when its backend has the entry, its solver's `polish_models_large_fits()` is true
+    (n <= 512) and its `_no_polish_many_large` is not set.  The inputs are prepared as for the small group and with
+    guess="device" there is one call per tau; result k is then what `models[k].polish_many([instances[k]],
+    [results[k]], large=True)` makes of it, bit for bit -- instead of the host's restatement per model.  If the library
+    declines, every model of the group goes to its own `polish_many(..., large=True)`.  A backend without the entry (the
+    CPU oracle) ignores the keyword.  Measured on (100,200,15), (150,100,5), (150,300,20) against the call without the
+    keyword (profiles/polish_models_large.txt): SLOWER at one model per call (0.7-0.9 x), 2.9-4.5 x at 8
+    models, 5-10 x at 64 and 256.  (n + M > 192 alone does not put a model beyond one workgroup: `polish_models_fits()`
+    decides, 160 KB of LDS and M <= 256; (50,200,10) fits and is not affected.)
+
+    ValueError: list lengths that differ, tau not positive, another `guess`, another `large`.  info: a dict that is
+    filled with polished (positions that went into a launch), polish_own ({position: why}), polish_launches (both groups),
+    polish_forms ({'small': .., 'large': ..}: models that went into each kind of launch) and polish_device_time."""
     models, instances = list(models), list(instances)
     if not (len(models) == len(instances) == len(results)):
         raise ValueError('polish_models: one instance and one result per model (%d models, %d instances, %d results)'
@@ -1534,13 +1561,18 @@ def polish_models(models, instances, results, tau=None, repair_iter=20, guess="h
         raise ValueError('polish_models: guess must be "host" or "device"')
     if tau is not None and not tau > 0:
         raise ValueError('polish_models: tau must be positive')
-    own, groups, prep = {}, {}, {}
+    if large is not None and not (isinstance(large, str) and large == "device"):
+        raise ValueError('polish_models: large must be None or "device"')
+    own, groups, prep, own_large = {}, {}, {}, set()
     for k, mdl in enumerate(models):
         work, res = mdl.work, results[k]
         res.update(polished=False, polish_rounds=0, pri_after=np.nan, dua_after=np.nan)
         if res['status'] not in (MI_SOLVED, MI_MAX_ITER_FEASIBLE):
             continue
         why = _polish_models_own_reason(work)
+        form = 'small'
+        if large == "device" and why is not None and _polish_models_large_ok(work):
+            why, form = None, 'large'
         if why is not None:
             own[k] = why
             continue
@@ -1555,18 +1587,22 @@ def polish_models(models, instances, results, tau=None, repair_iter=20, guess="h
         U[0, m:] = XI
         Y = primal_guess_multipliers(L[0], U[0], data.A.dot(X), tk) if guess == "host" else None
         prep[k] = (Q[0], L[0], U[0], X, Y, XI)
-        groups.setdefault((work.backend, tk if guess == "device" else None), []).append(k)
-    launched, launches, device_time = [], 0, 0.0
-    for (be, tk), ks in groups.items():
-        r = be.polish_models([models[k].work.solver for k in ks], [prep[k][0] for k in ks], [prep[k][1] for k in ks],
-                             [prep[k][2] for k in ks], [prep[k][3] for k in ks], [prep[k][4] for k in ks],
-                             [models[k].work.pol['delta'] for k in ks], [models[k].work.pol['refine_iter'] for k in ks],
-                             repair_iter, tau=tk)
+        groups.setdefault((work.backend, tk if guess == "device" else None, form), []).append(k)
+    launched, launches, device_time, forms = [], 0, 0.0, dict(small=0, large=0)
+    for (be, tk, form), ks in groups.items():
+        entry = be.polish_models_large if form == 'large' else be.polish_models
+        r = entry([models[k].work.solver for k in ks], [prep[k][0] for k in ks], [prep[k][1] for k in ks],
+                  [prep[k][2] for k in ks], [prep[k][3] for k in ks], [prep[k][4] for k in ks],
+                  [models[k].work.pol['delta'] for k in ks], [models[k].work.pol['refine_iter'] for k in ks],
+                  repair_iter, tau=tk)
         if r is None:  # (an engine declined after all: every model of the call on its own)
             for k in ks:
                 own[k] = 'the library declined the call'
+            if form == 'large':
+                own_large.update(ks)
             continue
         recs, stats = r
+        forms[form] += len(ks)
         launches += int(stats.launches)
         device_time += float(stats.device_time)
         for k, rec in zip(ks, recs):
@@ -1581,14 +1617,15 @@ def polish_models(models, instances, results, tau=None, repair_iter=20, guess="h
                 res['upper_glob'] = .5 * np.dot(x, data.P.dot(x)) + np.dot(prep[k][0], x)
                 res['polished'] = True
     for k in sorted(own):
-        models[k].polish_many([instances[k]], [results[k]], tau=tau, repair_iter=repair_iter)
+        models[k].polish_many([instances[k]], [results[k]], tau=tau, repair_iter=repair_iter, large=k in own_large)
     if info is not None:
         info.update(polished=sorted(launched), polish_own=dict(own), polish_launches=launches,
-                    polish_device_time=device_time)
+                    polish_device_time=device_time, polish_forms=forms)
     return results
 
 
-def solve_models(models, instances=None, info=None, polish=False, polish_guess="host", large=None, leaf_cap=256):
+def solve_models(models, instances=None, info=None, polish=False, polish_guess="host", large=None, leaf_cap=256,
+                 polish_large=None):
     """One MIQP on each of several DIFFERENT set-up models -- each with its own P, A, shapes and settings --, the trees
     of all of them in ONE call of the library (`qp.solve_trees_models`, miosqp_qp_solve_trees_models: at most two
     launches, workgroup or wavefront b runs model b).  It replaces the loop `models[k].solve_many([instances[k]])`: one
@@ -1629,6 +1666,11 @@ def solve_models(models, instances=None, info=None, polish=False, polish_guess="
     polish=True polishes such a model as any other of the list: the result is what its own `polish_many` makes of the
     tree's x.  Any other value of `large`, or leaf_cap < 2, raises ValueError.
 
+    polish_large=None (the default): as above -- a model beyond one workgroup is polished by its own `polish_many`, the
+    host's restatement.  polish_large="device": handed to `polish_models(large="device")`, which polishes those models
+    in one more launch (result k is then what `models[k].polish_many(.., large=True)` makes of the tree's x).  Read
+    only with polish=True; any other value raises ValueError before any launch.
+
     info: a dict that is filled with launched (positions), own ({position: why}), forms ({'wave': .., 'group': ..}; with
     large="device" also 'reduced'), launches, device_time (seconds) and overflow (positions); with polish=True also what
     `polish_models` reports."""
@@ -1636,6 +1678,8 @@ def solve_models(models, instances=None, info=None, polish=False, polish_guess="
         raise ValueError('solve_models: polish must be False or True')
     if large is not None and not (isinstance(large, str) and large == "device"):
         raise ValueError('solve_models: large must be None or "device"')
+    if polish_large is not None and not (isinstance(polish_large, str) and polish_large == "device"):
+        raise ValueError('solve_models: polish_large must be None or "device"')
     if isinstance(leaf_cap, bool) or int(leaf_cap) != leaf_cap or leaf_cap < 2:
         raise ValueError('solve_models: leaf_cap must be an integer of at least 2')
     leaf_cap = int(leaf_cap)
@@ -1716,7 +1760,7 @@ def solve_models(models, instances=None, info=None, polish=False, polish_guess="
         info.update(launched=list(launched), own=dict(own), forms=forms, launches=launches, device_time=device_time,
                     overflow=list(overflow))
     if polish:
-        polish_models(models, instances, out, guess=polish_guess, info=info)
+        polish_models(models, instances, out, guess=polish_guess, info=info, large=polish_large)
     return out
 
 

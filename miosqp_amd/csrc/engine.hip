@@ -44,6 +44,7 @@
 #include "lockstep_sb.hpp"  // strong and reliability branching in the lock-step trees (plain C++; host_lockstep_sb.inc drives it)
 #include "setup_plan.hpp"  // set-up of many models in one launch: argument checks, eligibility, arena layout (plain C++; host_setup_models.inc drives it); with guard_probe.hpp and setup_models_body.hpp, the kernel's arithmetic
 #include "polish_models_plan.hpp"  // polishes of different models in one launch: argument checks and arena layout (plain C++; host_polish_models.inc drives it)
+#include "polish_models_large_plan.hpp"  // ... of different LARGER models: fit rule, workgroups and arena layout with the slabs (plain C++; host_polish_models_large.inc drives it)
 #include "tree_reduced_body.hpp"  // the one-launch trees' relaxation in reduced form (k_tree_r_m): LDS rule and the phases of an iteration (plain C++; also run on the CPU under tests/)
 #include "models_plan.hpp"  // trees of different models in one launch: argument checks and arena layout (plain C++; host_models.inc drives it)
 #include "lockstep_refill.hpp"  // which tree goes into which free column when the columns are refilled between chunks (plain C++; host_refill.inc drives it)
@@ -1738,6 +1739,7 @@ int miosqp_qp_get_polish_repair_trace(miosqp_qp_engine *e, int8_t *cls, double *
 }
 
 #include "host_polish_models.inc"  // polishes of different models in one launch (C ABI miosqp_qp_polish_models)
+#include "host_polish_models_large.inc"  // ... beyond one workgroup's LDS (C ABI miosqp_qp_polish_models_large)
 
 // Both batched polish entries: the argument checks, one pinned block down, the one launch -- k_pol_many, or with `large`
 // k_pol_many_g on W slabs of device scratch --, one pinned block back, the records.  The answers stay in the entry's
@@ -1905,6 +1907,19 @@ int miosqp_qp_polish_models(int32_t B, miosqp_qp_engine *const *engines, const d
 
 int miosqp_qp_polish_models_fits(miosqp_qp_engine *e) {
   return e && miosqp::polm_lds_bytes(e->n, e->M) <= miosqp::polish_models::LDS_LIMIT ? 1 : 0;
+}
+
+int miosqp_qp_polish_models_large(int32_t B, miosqp_qp_engine *const *engines, const double *const *q, const double *const *l,
+                                  const double *const *u, const double *const *x, const double *const *y, double tau,
+                                  const double *delta, const int32_t *refine_iter, const int32_t *repair_iter,
+                                  double *const *x_out, double *const *y_out, int8_t *const *cls_out,
+                                  miosqp_polish_repair_info *info, miosqp_polish_models_large_stats *stats) {
+  return polish_models_large_run(B, engines, q, l, u, x, y, tau, delta, refine_iter, repair_iter, x_out, y_out, cls_out, info,
+                                 stats);
+}
+
+int miosqp_qp_polish_models_large_fits(miosqp_qp_engine *e) {
+  return e && miosqp::polish_models_large::fits(e->n, e->M) ? 1 : 0;
 }
 
 int miosqp_qp_get_polish_many_classes(miosqp_qp_engine *e, int32_t b, int8_t *cls) {

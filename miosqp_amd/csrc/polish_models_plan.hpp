@@ -23,8 +23,9 @@ constexpr double INFTY = 1e30;  // the engine's infinite bound
 inline int check_args(int32_t B, const void *const *engines, const int *n, const int *M, const double *const *q,
                       const double *const *l, const double *const *u, const double *const *x, const double *const *y, double tau,
                       const double *delta, const int32_t *refine_iter, const int32_t *repair_iter, const void *const *x_out,
-                      const void *const *y_out, const void *info, const void *stats, std::string &err) {
-  const std::string who = "polish_models: ";
+                      const void *const *y_out, const void *info, const void *stats, std::string &err,
+                      const char *entry = "polish_models") {
+  const std::string who = std::string(entry) + ": ";  // (miosqp_qp_polish_models_large refuses with the same checks)
   auto model = [](int b) { return "model " + std::to_string(b); };
   if (B < 1) {
     err = who + "B must be at least 1";

@@ -145,17 +145,38 @@ def polish_models(solvers, q, l, u, x, y, delta, refine_iter, repair_iter, tau=N
     run_time -- or None when the library declines
     (MIOSQP_EUNSUPPORTED: some model is beyond one workgroup).  ValueError for list lengths that differ and for l > u,
     RuntimeError (with the library's text, which names the model) for every other refusal."""
+    return _polish_models_call("polish_models", _lib.PolishModelsStats, solvers, q, l, u, x, y, delta, refine_iter,
+                               repair_iter, tau)
+
+
+def polish_models_large(solvers, q, l, u, x, y, delta, refine_iter, repair_iter, tau=None):
+    """`polish_models` beyond one workgroup's LDS (miosqp_qp_polish_models_large): the same arguments, the same way of
+    returning.  Model b is what `solvers[b].polish_many_large(q[b][None], l[b][None], ..., delta_b, refine_iter_b,
+    repair_iter_b)[0]` answers, bit for bit, without building or touching any engine's polish scratch: W workgroups
+    (stats.workgroups = min(B, two per compute unit, what 1 GiB of slabs allows)) take the models one after the other,
+    each in its workgroup's slab of device scratch (stats.slab_bytes, sized for the call's largest model).  Every engine
+    form `OSQP.polish_many_large` takes goes in, small models as well.  Returns (records, stats) -- stats with launches,
+    models, workgroups, slab_bytes, arena_bytes, device_time (upload_time, launch_time, download_time), run_time -- or
+    None when the library declines (MIOSQP_EUNSUPPORTED: some model has n > 512 or M > 65536).  ValueError for list
+    lengths that differ and for l > u, RuntimeError (the library's text names the model) for every other refusal."""
+    return _polish_models_call("polish_models_large", _lib.PolishModelsLargeStats, solvers, q, l, u, x, y, delta,
+                               refine_iter, repair_iter, tau)
+
+
+def _polish_models_call(name, stats_type, solvers, q, l, u, x, y, delta, refine_iter, repair_iter, tau):
+    """`polish_models` / `polish_models_large`: the two entries take the same arguments (name: the entry's, as the
+    messages say it; stats_type: its stats structure)"""
     B = len(solvers)
 
-    def per_model(v, name):
+    def per_model(v, what):
         if np.ndim(v) == 0:
             return [v] * B
         if len(v) != B:
-            raise ValueError("polish_models: %s must be a scalar or have one entry per model" % name)
+            raise ValueError("%s: %s must be a scalar or have one entry per model" % (name, what))
         return list(v)
 
     if not (len(q) == len(l) == len(u) == len(x) == len(y) == B):
-        raise ValueError("polish_models: one entry per model in every list")
+        raise ValueError("%s: one entry per model in every list" % name)
     dl = np.ascontiguousarray(per_model(delta, "delta"), dtype=np.float64).reshape(B)
     ri = np.ascontiguousarray(per_model(refine_iter, "refine_iter"), dtype=np.int32).reshape(B)
     pi = np.ascontiguousarray(per_model(repair_iter, "repair_iter"), dtype=np.int32).reshape(B)
@@ -166,7 +187,7 @@ def polish_models(solvers, q, l, u, x, y, delta, refine_iter, repair_iter, tau=N
 
     for s in solvers:
         if s._h is None:
-            raise ValueError("polish_models: an engine that was not set up (or was closed)")
+            raise ValueError("%s: an engine that was not set up (or was closed)" % name)
     q = [None if a is None else _f64(a, s.n, "q") for a, s in zip(q, solvers)]
     l = [_f64(a, s.m, "l") for a, s in zip(l, solvers)]
     u = [_f64(a, s.m, "u") for a, s in zip(u, solvers)]
@@ -176,15 +197,15 @@ def polish_models(solvers, q, l, u, x, y, delta, refine_iter, repair_iter, tau=N
     yo = [np.empty(s.m) for s in solvers]
     cls = [np.zeros(s.m, dtype=np.int8) for s in solvers]
     infos = (_lib.PolishRepairInfo * max(B, 1))()
-    stats = _lib.PolishModelsStats()
+    stats = stats_type()
     hs = (C.c_void_p * max(B, 1))(*[s._h.value for s in solvers])
     cp = (C.c_void_p * max(B, 1))(*[c.ctypes.data for c in cls])
-    rc = lib.miosqp_qp_polish_models(B, hs, ptrs(q), ptrs(l), ptrs(u), ptrs(x), ptrs(y), 0.0 if tau is None else float(tau),
-                                     _lib.as_d(dl), _lib.as_i(ri), _lib.as_i(pi), ptrs(xo), ptrs(yo), cp, infos,
-                                     C.byref(stats))
+    rc = getattr(lib, "miosqp_qp_" + name)(B, hs, ptrs(q), ptrs(l), ptrs(u), ptrs(x), ptrs(y), 0.0 if tau is None else float(tau),
+                                           _lib.as_d(dl), _lib.as_i(ri), _lib.as_i(pi), ptrs(xo), ptrs(yo), cp, infos,
+                                           C.byref(stats))
     if rc == -5:
         return None
-    _check(rc, "polish_models")
+    _check(rc, name)
     if rc == 1:
         raise ValueError("Lower bound must be lower than or equal to upper bound (%s)" % _lib.last_error())
     out = []
@@ -586,6 +607,10 @@ class OSQP(object):
                 rounds=rep.rounds, stop=rep.stop, n_added=rep.n_added, n_dropped=rep.n_dropped,
                 accepted0=bool(rep.accepted0), reason0=rep.reason0, active=cls.astype(np.int64)))
         return out
+
+    def polish_models_large_fits(self):
+        """whether `qp.polish_models_large` takes this engine's sizes (miosqp_qp_polish_models_large_fits)"""
+        return bool(self._lib.miosqp_qp_polish_models_large_fits(self._h))
 
     def polish_models_fits(self):
         """whether `qp.polish_models` takes this engine's sizes (miosqp_qp_polish_models_fits)"""
