@@ -654,6 +654,30 @@ int miosqp_qp_setup_models_large(int32_t B, const miosqp_setup_model *models, mi
  * n + M <= 2048, a fixed rho, and none of coop = 1, resident = 1, fold = 0, pers > 0, setup_on_device = 1, MIOSQP_COOP=1,
  * MIOSQP_PERS > 0.  Every (n, M) miosqp_qp_tree_form_large takes with 256 leaf places is among them. */
 int miosqp_qp_setup_models_eligible_large(int32_t n, int32_t M, const miosqp_qp_settings *settings);
+/* miosqp_qp_setup_models_large with settings->rho_auto = 1 accepted for the LARGE models as well (opt-in; small fixed, small
+ * rho_auto with rho_auto_in_launch, large fixed and large rho_auto models may be mixed in one call; when no large model asks
+ * for it the call IS miosqp_qp_setup_models_large).  It replaces what the reference does for such a model with
+ * osqp.OSQP().setup(rho=..) behind its own choice of rho (miosqp/workspace.py:63-68 of the reference), and what
+ * miosqp_qp_setup does with rho_auto = 1: for n + M <= 400 two complete set-ups and RHO_ONCE_ITERS = 50 iterations on a
+ * throw-away engine, above that an inline probe and a second host factor.  Here the recipe is a stage of the large launch
+ * (k_setup_models_large_auto): the workgroup that builds the model runs the 50 iterations from x = z = y = 0 on the first
+ * factor -- L^-1 and 1 / d on the packed triangle in LDS, Abar read from f_Ad / f_Atd out of L2, the iterates in LDS behind
+ * d -- applies the rule of miosqp_qp_setup_models_auto (the same code; every sum on one thread in ascending order, so the
+ * chosen rho does not depend on the list around the model) and, where the rule moves rho, forms S again at the chosen value
+ * with the terms of the first pass in their order, factors it and rewrites the panel's values; every product is that of
+ * miosqp_qp_setup_models_large at a fixed rho equal to the chosen one, bit for bit.  Still one upload, at most two
+ * launches, one download, one synchronisation.  miosqp_qp_get_rho reports the chosen rho, the settings keep rho_auto = 1.
+ * Refused before anything is queued, beside what miosqp_qp_setup_models_large refuses (a large rho_auto model no longer
+ * is): such a model beyond miosqp_qp_setup_models_eligible_large_auto's size rule (MIOSQP_EUNSUPPORTED, the rule and
+ * "(model b)" in the text).  A pivot that is not positive in either factor fails the whole call with MIOSQP_EFACTOR; for
+ * the second factor the text names the chosen rho as well. */
+int miosqp_qp_setup_models_large_auto(int32_t B, const miosqp_setup_model *models, miosqp_qp_engine **out,
+                                      miosqp_setup_models_stats *stats, int32_t rho_auto_in_launch);
+/* miosqp_qp_setup_models_eligible_large for the large launch of miosqp_qp_setup_models_large_auto: rho_auto = 1 is
+ * taken where the probing iterations' n + 3 M + 8 doubles fit the 160 KB of LDS beside the triangle, two rows and d
+ * (n <= 197; every (n, M) miosqp_qp_tree_form_large takes with 256 leaf places is still among them); with rho_auto = 0 the
+ * answer is miosqp_qp_setup_models_eligible_large's. */
+int miosqp_qp_setup_models_eligible_large_auto(int32_t n, int32_t M, const miosqp_qp_settings *settings);
 /* the SIZE rules alone, whatever the settings and the environment say: 1 a shape of miosqp_qp_setup_models (n + M <= 192),
  * 2 a shape of the large launch of miosqp_qp_setup_models_large (n <= 198, n + M <= 2048), 0 neither */
 int miosqp_qp_setup_models_shape(int32_t n, int32_t M);

@@ -1764,9 +1764,10 @@ def solve_models(models, instances=None, info=None, polish=False, polish_guess="
     return out
 
 
-def _setup_models_own_reason(be, data, qp_settings, rho_auto_in_launch=False, large=False):
+def _setup_models_own_reason(be, data, qp_settings, rho_auto_in_launch=False, large=False, large_rho_auto=False):
     """why `setup_models` leaves a model to `MIOSQP.setup` (None: it goes into the launch; 'large' in place of None with
-    large=True: it goes into the launch for models beyond one workgroup of the existing one)"""
+    large=True: it goes into the launch for models beyond one workgroup of the existing one; 'large auto' with
+    large_rho_auto=True: into that launch, which chooses its rho)"""
     if not hasattr(be, 'setup_models') or not hasattr(be, 'setup_models_eligible'):
         return 'backend without the one-launch set-up'
     if data.n_int == 0:
@@ -1778,7 +1779,19 @@ def _setup_models_own_reason(be, data, qp_settings, rho_auto_in_launch=False, la
         if be.setup_models_shape(n, M) == 0:
             return 'n + M = %d: beyond one workgroup of either launch' % (n + M)
         if isinstance(qp_settings.get('rho'), str):
-            return 'rho="auto" beyond one workgroup of the launch: the large launch builds a fixed rho only'
+            if not large_rho_auto:
+                return 'rho="auto" beyond one workgroup of the launch: the large launch builds a fixed rho only'
+            if not hasattr(be, 'setup_models_eligible_large_auto'):
+                return 'rho="auto" beyond one workgroup of the launch: backend without the large launch that chooses rho'
+            if not data.P.has_canonical_format or not spa.csc_matrix(data.A).has_canonical_format:
+                return 'duplicate entries in P or A'
+            if not be.setup_models_eligible_large_auto(n, M, qp_settings):
+                fixed = {k: v for k, v in qp_settings.items() if k != 'rho'}
+                if be.setup_models_eligible_large(n, M, fixed):  # (everything but the probe's room in the LDS is in order)
+                    return ('rho="auto" beyond the LDS rule of the large launch that chooses rho: the packed triangle and '
+                            'the probing iterations\' n + 3 M + 8 doubles within 160 KB (n <= 197)')
+                return 'settings or environment that lead to another engine form than the large launch builds'
+            return 'large auto'
         if not data.P.has_canonical_format or not spa.csc_matrix(data.A).has_canonical_format:
             return 'duplicate entries in P or A'
         if not be.setup_models_eligible_large(n, M, qp_settings):
@@ -1798,7 +1811,7 @@ def _setup_models_own_reason(be, data, qp_settings, rho_auto_in_launch=False, la
     return None
 
 
-def setup_models(problems, settings, qp_settings, info=None, backend=None, rho_auto=None, large=None):
+def setup_models(problems, settings, qp_settings, info=None, backend=None, rho_auto=None, large=None, large_rho_auto=None):
     """Set up several DIFFERENT MIQP models -- each with its own P and A -- with ONE launch for the dense set-up of all of
     them (`qp.setup_models`, miosqp_qp_setup_models: one workgroup per model builds the Schur complement, its LDL^T, the
     triangular inverse, the product form, the explicit inverse and its guard; the engines share one stream, one device
@@ -1828,21 +1841,34 @@ def setup_models(problems, settings, qp_settings, info=None, backend=None, rho_a
     one-launch trees read nothing of the grid; for a long sequential search on one model call `MIOSQP.setup`.  Of the
     reference benchmark's grid this takes (50,200,10), (100,200,15), (150,100,5) and (150,300,20)
     (profiles/setup_models_large.txt).  rho_auto="device" and large="device" combine in one call; a large model with
-    rho="auto" is set up in its place (its reason in info["own"]): rho for such a model is not chosen in the launch.  On a
+    rho="auto" is set up in its place (its reason in info["own"]) unless large_rho_auto says otherwise.  On a
     backend without the entry such models are set up in place.  Any other value: ValueError.
+
+    large_rho_auto: read only with large="device", and independent of rho_auto, which goes on deciding for the small
+    models.  None -- as above.  "device" -- a large model with rho="auto" goes into the call where
+    `qp.setup_models_eligible_large_auto` admits it (the probing iterations' vectors fit the LDS beside the packed
+    triangle: n <= 197, which holds every shape `solve_models(large="device")` solves), and the workgroup that builds it
+    chooses rho (miosqp_qp_setup_models_large_auto, k_setup_models_large_auto: the fifty probing iterations on the first
+    factor in LDS with Abar read from L2, the rule, S and the factor again at the chosen rho); its products are those of the
+    same model at a fixed rho equal to the chosen one, bit for bit.  A model beyond that rule, and every model on a
+    backend without the entry (the CPU oracle), is set up in place, the rule named in info["own"].  Opt-in; measured in
+    profiles/setup_models_large_rho_auto.txt.  Any other value: ValueError.
 
     ValueError before anything is queued, with the positions named: an empty list, a wrong number of settings, l > u, a P
     of the wrong shape.  A pivot that is not positive raises what `MIOSQP.setup` raises, with the position added; nothing
     of the call is left behind.
 
     info: a dict that is filled with batched (positions), own ({position: why}), launches, device_time, arena_bytes,
-    host_time (seconds of the call outside the library's one), rho (the rho in use per position) and forms
-    ({'small': .., 'large': ..}: the batched models per launch)."""
+    host_time (seconds of the call outside the library's one), rho (the rho in use per position), forms
+    ({'small': .., 'large': ..}: the batched models per launch) and rho_auto_large (the positions whose rho the large
+    launch chose)."""
     t_call = time()
     if rho_auto not in (None, 'device'):
         raise ValueError('setup_models: rho_auto must be None or "device", not %r' % (rho_auto,))
     if large is not None and not (isinstance(large, str) and large == 'device'):
         raise ValueError('setup_models: large must be None or "device", not %r' % (large,))
+    if large_rho_auto is not None and not (isinstance(large_rho_auto, str) and large_rho_auto == 'device'):
+        raise ValueError('setup_models: large_rho_auto must be None or "device", not %r' % (large_rho_auto,))
     problems = list(problems)
     B = len(problems)
     if B == 0:
@@ -1880,11 +1906,15 @@ def setup_models(problems, settings, qp_settings, info=None, backend=None, rho_a
     be = backend if backend is not None else _default_backend()
     own, batched = {}, []
     forms = dict(small=0, large=0)
+    rho_auto_large = []
     for k in range(B):
-        why = _setup_models_own_reason(be, datas[k], qp_settings[k], rho_auto == 'device', large == 'device')
-        if why is None or why == 'large':
+        why = _setup_models_own_reason(be, datas[k], qp_settings[k], rho_auto == 'device', large == 'device',
+                                       large == 'device' and large_rho_auto == 'device')
+        if why is None or why in ('large', 'large auto'):
             batched.append(k)
             forms['small' if why is None else 'large'] += 1
+            if why == 'large auto':
+                rho_auto_large.append(k)
         else:
             own[k] = why
     out = [None] * B
@@ -1902,10 +1932,13 @@ def setup_models(problems, settings, qp_settings, info=None, backend=None, rho_a
             t0 = time()
             try:
                 kw = {}
-                if rho_auto == 'device' and any(isinstance(md['settings'].get('rho'), str) for md in desc):
+                if rho_auto == 'device' and any(isinstance(md['settings'].get('rho'), str)
+                                                for k, md in zip(batched, desc) if k not in rho_auto_large):
                     kw['rho_auto_in_launch'] = True
                 if forms['large']:
                     kw['large'] = True
+                if rho_auto_large:
+                    kw['large_auto'] = True
                 solvers, stats = be.setup_models(desc, **kw)
             except RuntimeError as ex:
                 import re
@@ -1933,5 +1966,5 @@ def setup_models(problems, settings, qp_settings, info=None, backend=None, rho_a
     if info is not None:
         rho = [float(m.work.solver.rho()) for m in out]
         info.update(batched=list(batched), own=dict(own), launches=launches, device_time=device_time, arena_bytes=arena_bytes,
-                    host_time=(time() - t_call) - lib_time, rho=rho, forms=forms)
+                    host_time=(time() - t_call) - lib_time, rho=rho, forms=forms, rho_auto_large=rho_auto_large)
     return out

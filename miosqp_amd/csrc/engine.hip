@@ -271,7 +271,7 @@ namespace {
 // the dynamic-LDS ceiling of a kernel is a property of (process, device, kernel): raised to the chip's 160 KB once instead of
 // at every set-up (the call costs ~40 us, a fifth of a small problem's set-up)
 hipError_t lds_limit_once(const void *fn, int which) {
-  static bool done[18][64] = {};  // (one row per kernel: 0 .. 13 as before, 14: k_setup_models, 15: k_setup_models_auto, 16: k_tree_r_m, 17: k_setup_models_large)
+  static bool done[19][64] = {};  // (one row per kernel: 0 .. 13 as before, 14: k_setup_models, 15: k_setup_models_auto, 16: k_tree_r_m, 17: k_setup_models_large, 18: k_setup_models_large_auto)
   int dev = 0;
   hipError_t rc = hipGetDevice(&dev);
   if (rc != hipSuccess) return rc;
@@ -2323,6 +2323,20 @@ int miosqp_qp_setup_models_eligible_large(int32_t n, int32_t M, const miosqp_qp_
                  setup_models_large_env_ok()
              ? 1
              : 0;
+}
+
+int miosqp_qp_setup_models_large_auto(int32_t B, const miosqp_setup_model *models, miosqp_qp_engine **out,
+                                      miosqp_setup_models_stats *stats, int32_t rho_auto_in_launch) {
+  return setup_models_run(B, models, out, stats, rho_auto_in_launch != 0, true, true);
+}
+
+int miosqp_qp_setup_models_eligible_large_auto(int32_t n, int32_t M, const miosqp_qp_settings *s) {
+  if (!s) return 0;
+  miosqp::setup_models::Args a;
+  a.rho_auto = s->rho_auto; a.coop = s->coop; a.resident = s->resident; a.fold = s->fold; a.setup_on_device = s->setup_on_device;
+  a.pers = s->pers;
+  const bool shape = a.rho_auto ? miosqp::setup_models::eligible_shape_large_auto(n, M) : miosqp::setup_models::eligible_shape_large(n, M);
+  return shape && miosqp::setup_models::eligible_settings_large(a, true) && setup_models_large_env_ok() ? 1 : 0;
 }
 
 int miosqp_qp_setup_models_shape(int32_t n, int32_t M) {

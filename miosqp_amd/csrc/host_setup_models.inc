@@ -133,9 +133,11 @@ bool setup_models_large_env_ok() {
 // rho_auto_in_launch (miosqp_qp_setup_models_auto): models with settings->rho_auto = 1 are taken, and when there is one
 // the launch is k_setup_models_auto.  large (miosqp_qp_setup_models_large): a model that k_setup_models does not take for
 // its size is built by k_setup_models_large, a second launch of the same call, as the engine miosqp_qp_setup builds with
-// coop = 0, resident = 0, fold = 1, pers = 0; the table holds the small models first.
+// coop = 0, resident = 0, fold = 1, pers = 0; the table holds the small models first.  large_rho_auto
+// (miosqp_qp_setup_models_large_auto): large models with rho_auto = 1 are taken, and when there is one the large launch
+// is k_setup_models_large_auto.
 int setup_models_run(int32_t B, const miosqp_setup_model *ms, miosqp_qp_engine **out, miosqp_setup_models_stats *stats,
-                     bool rho_auto_in_launch, bool large = false) {
+                     bool rho_auto_in_launch, bool large = false, bool large_rho_auto = false) {
   namespace sm = miosqp::setup_models;
   static_assert(sizeof(Ctrl) <= sm::CTRL_BYTES, "Ctrl fits its place in the arena and the slab");
   // ---- refused before anything is queued ----
@@ -144,7 +146,7 @@ int setup_models_run(int32_t B, const miosqp_setup_model *ms, miosqp_qp_engine *
     if (B >= 1 && ms)
       for (int b = 0; b < B; b++) av.push_back(setup_args_of(ms[b]));
     std::string err;
-    if (int rc = sm::check_args(B, ms ? av.data() : nullptr, out, stats, err, rho_auto_in_launch, large)) {
+    if (int rc = sm::check_args(B, ms ? av.data() : nullptr, out, stats, err, rho_auto_in_launch, large, large_rho_auto)) {
       g_err = err;
       return rc;
     }
@@ -193,8 +195,9 @@ int setup_models_run(int32_t B, const miosqp_setup_model *ms, miosqp_qp_engine *
     t_last = now;
   };
   for (int b = 0; b < B; b++) out[b] = nullptr;
-  bool any_auto = false;
-  for (int b = 0; b < B; b++) any_auto = any_auto || ms[b].settings->rho_auto != 0;
+  bool any_auto = false, any_auto_large = false;  // per launch: a small model, a large model that asks for rho_auto
+  for (int b = 0; b < B; b++)
+    if (ms[b].settings->rho_auto != 0) (form[(size_t)b] == sm::FORM_LARGE ? any_auto_large : any_auto) = true;
   const int64_t made0[3] = {g_made_device_mallocs, g_made_host_mallocs, g_made_streams};
   std::vector<miosqp_qp_engine *> eng((size_t)B, nullptr);
   SetupGroup *grp = nullptr;
@@ -392,7 +395,10 @@ int setup_models_run(int32_t B, const miosqp_setup_model *ms, miosqp_qp_engine *
     if (any_auto) SMCHK(lds_limit_once((const void *)k_setup_models_auto, 15));
     else SMCHK(lds_limit_once((const void *)k_setup_models, 14));
   }
-  if (P.n_large) SMCHK(lds_limit_once((const void *)k_setup_models_large, 17));
+  if (P.n_large) {
+    if (any_auto_large) SMCHK(lds_limit_once((const void *)k_setup_models_large_auto, 18));
+    else SMCHK(lds_limit_once((const void *)k_setup_models_large, 17));
+  }
   miosqp_qp_engine *e0 = eng[0];
   SMCHK(hipEventRecord(e0->ev0, grp->stream));
   SMCHK(hipMemcpyAsync(dv, hs, P.up_bytes, hipMemcpyHostToDevice, grp->stream));
@@ -402,7 +408,10 @@ int setup_models_run(int32_t B, const miosqp_setup_model *ms, miosqp_qp_engine *
   else if (P.n_small)
     hipLaunchKernelGGL(k_setup_models, dim3((unsigned)P.n_small), dim3(sm::THREADS), P.lds_bytes, grp->stream,
                        reinterpret_cast<const SetupModel *>(dv));
-  if (P.n_large)
+  if (P.n_large && any_auto_large)
+    hipLaunchKernelGGL(k_setup_models_large_auto, dim3((unsigned)P.n_large), dim3(sm::THREADS), P.lds_bytes_large, grp->stream,
+                       reinterpret_cast<const SetupModel *>(dv) + P.n_small);
+  else if (P.n_large)
     hipLaunchKernelGGL(k_setup_models_large, dim3((unsigned)P.n_large), dim3(sm::THREADS), P.lds_bytes_large, grp->stream,
                        reinterpret_cast<const SetupModel *>(dv) + P.n_small);
   SMCHK(hipGetLastError());

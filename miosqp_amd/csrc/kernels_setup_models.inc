@@ -10,11 +10,14 @@
 // kernel of its own (body_auto), so that k_setup_models stays the code it was.
 // k_setup_models_large: a model beyond n + M = 192 (setup_models_large_body.hpp): only the packed triangle in LDS, Abar
 // read from memory; what miosqp_qp_setup(coop = 0, resident = 0, fold = 1, pers = 0) builds -- no W, no Kc, no guard.
+// k_setup_models_large_auto: the same, and for a model whose settings say rho_auto the choice of rho inside the launch
+// (body_large_auto): the probing iterations on the triangle in LDS with Abar from L2, the rule, S and the factor again at
+// the chosen rho, the panel's values.  A kernel of its own, so that k_setup_models_large stays the code it was.
 // ------------------------------------------------------------------------------------------
 struct SetupModel {
   miosqp::setup_models::IO io;  // final pointers into the call's arena
   Ctrl *ctrl;
-  miosqp::setup_models::Auto au;  // read by k_setup_models_auto only
+  miosqp::setup_models::Auto au;  // read by k_setup_models_auto and k_setup_models_large_auto only
 };
 
 struct SetupExecDevice {
@@ -58,4 +61,14 @@ __global__ __launch_bounds__(miosqp::setup_models::THREADS) void k_setup_models_
   if (threadIdx.x == 0) setup_models_reset_ctrl(m.ctrl);
   SetupExecDevice x;
   miosqp::setup_models::body_large(m.io, sm_lds, x);
+}
+
+// (as in k_setup_models_auto the probing iterations keep their vectors in LDS: the model's iterates in the arena stay at
+//  the zero the arena was filled with)
+__global__ __launch_bounds__(miosqp::setup_models::THREADS) void k_setup_models_large_auto(const SetupModel *__restrict__ tab) {
+  extern __shared__ double sm_lds[];
+  const SetupModel &m = tab[blockIdx.x];
+  if (threadIdx.x == 0) setup_models_reset_ctrl(m.ctrl);
+  SetupExecDevice x;
+  miosqp::setup_models::body_large_auto(m.io, m.au, sm_lds, x);
 }

@@ -222,17 +222,27 @@ MIOSQP_HD inline bool refactor(const IO &io, const Auto &au, double *Lp, const d
   return true;
 }
 
-// The choice of rho (body_auto, a model with au.on): RHO_ONCE_ITERS iterations of the CPU restatement's admm_step from
-// x = z = y = 0 on the first factor, the rule of rho_estimate, and where it moves rho the factor again.  Returns false
-// after a bad pivot of the second factor; `rho` is the rho in use afterwards.
+// How the probing iterations read Abar.  by_var(r, i) is the read of a thread that owns variable i and walks the
+// constraint rows r, by_con(r, i) that of a thread that owns row r and walks the variables: the same value either way.
+// Here both come from the dense copy in LDS; the large launch (setup_models_large_body.hpp) reads f_Ad and f_Atd.
+struct AbarLds {
+  const double *Ad;
+  int lda;
+  MIOSQP_HD double by_var(int r, int i) const { return Ad[(size_t)r * lda + i]; }
+  MIOSQP_HD double by_con(int r, int i) const { return Ad[(size_t)r * lda + i]; }
+};
+
+// The probe and the rule of the choice of rho: RHO_ONCE_ITERS iterations of the CPU restatement's admm_step from
+// x = z = y = 0 on the first factor (L^-1 on the triangle, 1 / d in dv), then the rule of rho_estimate.  Returns the
+// chosen rho (the same value on every thread) and fills Record::rho_est and Record::rho.
 //   The KKT solve in reduced form: with S = Pbar + sigma I + rho Abar^T Abar = L D L^T,
 //     x~ = L^-T D^-1 L^-1 (sigma x - q + Abar^T (rho z - y)),   nu = rho (Abar x~ - z) + y,
 //   and admm_step's z~ = z + (nu - y) / rho is, with that nu, Abar x~: THAT identity is used, z~ = Abar x~ is formed
 //   directly and nu never is.  Every sum runs on one thread in ascending index order.
-template <class X>
-MIOSQP_HD inline bool choose_rho(const IO &io, const Auto &au, double *Lp, const double *Ad, double *tmp, double *dv,
-                                 double *pv, X &x, double &rho) {
-  const int n = io.n, M = io.M, NT = THREADS, lda = n | 1;
+template <class AB, class X>
+MIOSQP_HD inline double probe_rule(const IO &io, const Auto &au, const AB &Ab, double *Lp, double *tmp, double *dv, double *pv,
+                                   X &x) {
+  const int n = io.n, M = io.M, NT = THREADS;
   const double rho0 = io.rho, rho0_inv = 1.0 / rho0, sigma = io.sigma, alpha = au.alpha;
   double *xs = pv, *zs = xs + n, *ys = zs + M, *ax = ys + M, *sc = ax + M;  // x, z, y, Abar x, scalars
   double *rhs = tmp, *w = tmp + n, *xt = tmp;  // (the two row buffers of phase 4 are free; x~ takes the place of the rhs)
@@ -251,7 +261,7 @@ MIOSQP_HD inline bool choose_rho(const IO &io, const Auto &au, double *Lp, const
     x.par([&](int tid) {
       for (int i = tid; i < n; i += NT) {
         double acc = sigma * xs[i] - au.q[i];
-        for (int r = 0; r < M; r++) acc = fma(Ad[(size_t)r * lda + i], rho0 * zs[r] - ys[r], acc);
+        for (int r = 0; r < M; r++) acc = fma(Ab.by_var(r, i), rho0 * zs[r] - ys[r], acc);
         rhs[i] = acc;
       }
     });
@@ -275,9 +285,8 @@ MIOSQP_HD inline bool choose_rho(const IO &io, const Auto &au, double *Lp, const
     // z~ = Abar x~; relaxation, projection and the dual step of admm_step (row r and variable i belong to one thread)
     x.par([&](int tid) {
       for (int r = tid; r < M; r += NT) {
-        const double *Ar = Ad + (size_t)r * lda;
         double zt = 0.0;
-        for (int i = 0; i < n; i++) zt = fma(Ar[i], xt[i], zt);
+        for (int i = 0; i < n; i++) zt = fma(Ab.by_con(r, i), xt[i], zt);
         const double zr = alpha * zt + (1.0 - alpha) * zs[r];
         const double v = zr + rho0_inv * ys[r];
         const double zn = fmin(fmax(v, io.l[r]), io.u[r]);
@@ -291,9 +300,8 @@ MIOSQP_HD inline bool choose_rho(const IO &io, const Auto &au, double *Lp, const
   double *Px = tmp, *Aty = tmp + n;
   x.par([&](int tid) {
     for (int r = tid; r < M; r += NT) {
-      const double *Ar = Ad + (size_t)r * lda;
       double s = 0.0;
-      for (int i = 0; i < n; i++) s = fma(Ar[i], xs[i], s);
+      for (int i = 0; i < n; i++) s = fma(Ab.by_con(r, i), xs[i], s);
       ax[r] = s;
     }
     for (int i = tid; i < n; i += NT) {
@@ -301,7 +309,7 @@ MIOSQP_HD inline bool choose_rho(const IO &io, const Auto &au, double *Lp, const
       for (int t = io.pb_ptr[i]; t < io.pb_ptr[i + 1]; t++) s = fma(io.pb_val[t], xs[io.pb_idx[t]], s);
       Px[i] = s;
       double a = 0.0;
-      for (int r = 0; r < M; r++) a = fma(Ad[(size_t)r * lda + i], ys[r], a);
+      for (int r = 0; r < M; r++) a = fma(Ab.by_var(r, i), ys[r], a);
       Aty[i] = a;
     }
   });
@@ -329,7 +337,16 @@ MIOSQP_HD inline bool choose_rho(const IO &io, const Auto &au, double *Lp, const
     io.rec->rho_est = r;
     io.rec->rho = sc[1];
   });
-  rho = sc[1];  // (the same value on every thread)
+  return sc[1];
+}
+
+// The choice of rho (body_auto, a model with au.on): probe_rule on the dense Abar in LDS, and where the rule moves rho
+// the factor again.  Returns false after a bad pivot of the second factor; `rho` is the rho in use afterwards.
+template <class X>
+MIOSQP_HD inline bool choose_rho(const IO &io, const Auto &au, double *Lp, const double *Ad, double *tmp, double *dv,
+                                 double *pv, X &x, double &rho) {
+  const double rho0 = io.rho;
+  rho = probe_rule(io, au, AbarLds{Ad, io.n | 1}, Lp, tmp, dv, pv, x);
   if (rho == rho0) return true;  // the first factor stands
   return refactor(io, au, Lp, Ad, tmp, dv, x, rho);
 }

@@ -47,9 +47,11 @@ inline bool eligible_shape_auto(int n, int M) {
 
 // A model beyond n + M = 192 (miosqp_qp_setup_models_large) comes out as the engine miosqp_qp_setup builds with coop = 0,
 // resident = 0, fold = 1, pers = 0: settings that ask for another form keep it out.  rho is fixed: choosing it for such
-// a model inside the launch is not built.
-inline bool eligible_settings_large(const Args &a) {
-  return a.rho_auto == 0 && a.setup_on_device != 1 && a.fold != 0 && a.coop != 1 && a.resident != 1 && a.pers <= 0;
+// a model inside the launch is the opt-in of miosqp_qp_setup_models_large_auto (large_rho_auto: rho_auto = 1 is taken
+// too; its size rule is eligible_shape_large_auto).
+inline bool eligible_settings_large(const Args &a, bool large_rho_auto = false) {
+  return (a.rho_auto == 0 || (large_rho_auto && a.rho_auto == 1)) && a.setup_on_device != 1 && a.fold != 0 && a.coop != 1 &&
+         a.resident != 1 && a.pers <= 0;
 }
 
 // The launch writes the dense copies of Abar and Pbar entry by entry where the per-model set-up sums what a matrix stores
@@ -62,9 +64,10 @@ inline bool csc_strictly_ascending(int cols, const int32_t *ptr, const int32_t *
 }
 
 // 0, or the error code with `err` naming the model's position.  large (miosqp_qp_setup_models_large): a model that the
-// small launch does not take for its SIZE is judged by the rules of the large one.
+// small launch does not take for its SIZE is judged by the rules of the large one.  large_rho_auto
+// (miosqp_qp_setup_models_large_auto): such a model with rho_auto = 1 is taken where the probing iterations' vectors fit.
 inline int check_args(int32_t B, const Args *a, const void *out, const void *stats, std::string &err,
-                      bool rho_auto_in_launch = false, bool large = false) {
+                      bool rho_auto_in_launch = false, bool large = false, bool large_rho_auto = false) {
   const std::string who = "setup_models: ";
   if (B < 1) {
     err = who + "B must be at least 1";
@@ -108,11 +111,16 @@ inline int check_args(int32_t B, const Args *a, const void *out, const void *sta
               std::to_string(LDS_LIMIT / 1024) + " KB of LDS (n <= 198) and n + M <= " + std::to_string(MAX_NM_LARGE) + at;
         return ERR_UNSUPPORTED;
       }
-      if (m.rho_auto != 0) {
+      if (m.rho_auto != 0 && !large_rho_auto) {
         err = who + "rho_auto = 1 beyond n + M = " + std::to_string(MAX_NM) + ": the large launch builds a fixed rho only" + at;
         return ERR_UNSUPPORTED;
       }
-      if (!eligible_settings_large(m)) {
+      if (m.rho_auto != 0 && !eligible_shape_large_auto(m.n, m.M)) {
+        err = who + "rho_auto = 1 beyond the large launch that chooses rho: the packed triangle of n variables and the "
+                    "probing iterations' n + 3 M + 8 doubles within " + std::to_string(LDS_LIMIT / 1024) + " KB of LDS (n <= 197)" + at;
+        return ERR_UNSUPPORTED;
+      }
+      if (!eligible_settings_large(m, large_rho_auto)) {
         err = who + "the large launch does not take this model: it builds the engine of coop = 0, resident = 0, fold = 1, "
                     "pers = 0 on the host's set-up path (setup_on_device != 1)" + at;
         return ERR_UNSUPPORTED;
@@ -131,7 +139,7 @@ inline int check_args(int32_t B, const Args *a, const void *out, const void *sta
 }
 
 constexpr int FORM_SMALL = 0;  // k_setup_models / k_setup_models_auto
-constexpr int FORM_LARGE = 1;  // k_setup_models_large
+constexpr int FORM_LARGE = 1;  // k_setup_models_large / k_setup_models_large_auto
 
 struct Shape {
   int n = 0, M = 0;
@@ -227,7 +235,7 @@ inline Plan plan(const std::vector<Shape> &sh, size_t entry_bytes) {
       at += one[k];
     }
     if (sh[b].form == FORM_LARGE) {
-      const size_t lds = lds_doubles_large(sh[b].n, sh[b].M) * sizeof(double);
+      const size_t lds = (sh[b].rho_auto ? lds_doubles_large_auto(sh[b].n, sh[b].M) : lds_doubles_large(sh[b].n, sh[b].M)) * sizeof(double);
       if (lds > P.lds_bytes_large) P.lds_bytes_large = lds;
       P.n_large++;
     } else {

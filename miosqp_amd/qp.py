@@ -249,6 +249,14 @@ def setup_models_eligible_large(n, m, settings):
     return bool(_lib.load().miosqp_qp_setup_models_eligible_large(int(n), int(m), C.byref(s)))
 
 
+def setup_models_eligible_large_auto(n, m, settings):
+    """Does the large launch of setup_models(..., large=True, large_auto=True) take a model of n variables and m rows under
+    these settings and this environment: what setup_models_eligible_large asks, with rho="auto" taken where the probing
+    iterations' vectors fit the LDS beside the triangle (n <= 197)?  (miosqp_qp_setup_models_eligible_large_auto)"""
+    s = settings if isinstance(settings, _lib.Settings) else _settings_from_kwargs(settings)
+    return bool(_lib.load().miosqp_qp_setup_models_eligible_large_auto(int(n), int(m), C.byref(s)))
+
+
 def setup_models_shape(n, m):
     """The size rules of setup_models alone, whatever settings and environment say: 1 a shape of the existing launch
     (n + M <= 192), 2 a shape of the large launch (n <= 198, n + M <= 2048), 0 neither (miosqp_qp_setup_models_shape)"""
@@ -260,7 +268,7 @@ def setup_groups_live():
     return int(_lib.load().miosqp_qp_setup_groups_live())
 
 
-def setup_models(models, rho_auto_in_launch=False, large=False):
+def setup_models(models, rho_auto_in_launch=False, large=False, large_auto=False):
     """The set-up of several DIFFERENT small models in ONE launch (miosqp_qp_setup_models): the dense part of every
     model -- Schur complement, LDL^T, triangular inverse, product form, explicit inverse, its guard -- by one workgroup
     per model; the engines share one stream, one device arena and one pinned slab.
@@ -274,6 +282,10 @@ def setup_models(models, rho_auto_in_launch=False, large=False):
     OSQP.setup(..., coop=0, resident=0, fold=1) builds (product form, no explicit inverse; tree_form_large answers 3 for
     it where it does for that engine).  One group, one upload, at most two launches (stats.launches).  Such a model with
     rho="auto" is refused.
+
+    large_auto=True (read with large=True; miosqp_qp_setup_models_large_auto): a large model with rho="auto" is taken too
+    (setup_models_eligible_large_auto); the workgroup that builds it chooses rho as the small launch does, on the triangle
+    in LDS with Abar read from L2, and every product is that of the same model at a fixed rho equal to the chosen one.
 
     models: dicts with P, q, A, l, u (as OSQP.setup takes them), settings (a dict of OSQP.setup's keywords), and
     optionally i_idx with m_orig (set_integer_rows is applied) and root = (l_root, u_root, eps_int_feas, eps_lin)
@@ -316,7 +328,8 @@ def setup_models(models, rho_auto_in_launch=False, large=False):
     hs = (C.c_void_p * max(B, 1))()
     stats = _lib.SetupModelsStats()
     if large:
-        _check(lib.miosqp_qp_setup_models_large(B, desc, hs, C.byref(stats), 1 if rho_auto_in_launch else 0), "setup_models")
+        entry = lib.miosqp_qp_setup_models_large_auto if large_auto else lib.miosqp_qp_setup_models_large
+        _check(entry(B, desc, hs, C.byref(stats), 1 if rho_auto_in_launch else 0), "setup_models")
     else:
         entry = lib.miosqp_qp_setup_models_auto if rho_auto_in_launch else lib.miosqp_qp_setup_models
         _check(entry(B, desc, hs, C.byref(stats)), "setup_models")
