@@ -678,6 +678,22 @@ int miosqp_qp_setup_models_large_auto(int32_t B, const miosqp_setup_model *model
  * (n <= 197; every (n, M) miosqp_qp_tree_form_large takes with 256 leaf places is still among them); with rho_auto = 0 the
  * answer is miosqp_qp_setup_models_eligible_large's. */
 int miosqp_qp_setup_models_eligible_large_auto(int32_t n, int32_t M, const miosqp_qp_settings *settings);
+/* Any of the four entries above (chosen by `flags`: no bit is miosqp_qp_setup_models) with the host's share of a model's
+ * preparation moved into the call (opt-in): the Ruiz equilibration (settings->scaling passes) and the packed rows of the
+ * panel and of the two symmetric matrices.  The upload holds the RAW problem (the CSC of P as given and of A, q, l, u)
+ * and the four pointer arrays of the packed structures, which the host makes from histograms of the row indices; ONE
+ * more launch ahead of the set-up launch(es) on the group's stream, one workgroup of 256 threads per model
+ * (k_prepare_models, prepare_models_body.hpp), packs the rows, runs the passes in place and derives D, E, c, their
+ * inverses, the scaled q and the panel's values.  Everything it writes is bit for bit what the host writes (maxima,
+ * correctly rounded 1 / sqrt, products, and one sum formed by one thread in ascending order), hence so is every product
+ * of the set-up launches, and an engine that comes out is indistinguishable from one of the same call without this entry:
+ * the host's mirrors of the scaled problem and of the rows are filled from the one download behind the launches.  Checks,
+ * refusals and eligibility are those of the entry the flags name; stats->launches counts the additional launch. */
+#define MIOSQP_SETUP_MODELS_RHO_AUTO 1       /* miosqp_qp_setup_models_auto / rho_auto_in_launch of the large entries */
+#define MIOSQP_SETUP_MODELS_LARGE 2          /* miosqp_qp_setup_models_large */
+#define MIOSQP_SETUP_MODELS_LARGE_RHO_AUTO 4 /* miosqp_qp_setup_models_large_auto (implies MIOSQP_SETUP_MODELS_LARGE) */
+int miosqp_qp_setup_models_prepared(int32_t B, const miosqp_setup_model *models, miosqp_qp_engine **out,
+                                    miosqp_setup_models_stats *stats, int32_t flags);
 /* the SIZE rules alone, whatever the settings and the environment say: 1 a shape of miosqp_qp_setup_models (n + M <= 192),
  * 2 a shape of the large launch of miosqp_qp_setup_models_large (n <= 198, n + M <= 2048), 0 neither */
 int miosqp_qp_setup_models_shape(int32_t n, int32_t M);

@@ -192,6 +192,8 @@ SYMBOLS = {
                                                     C.POINTER(SetupModelsStats), C.c_int32]),
     "miosqp_qp_setup_models_eligible_large_auto": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(Settings)]),
     "miosqp_qp_setup_models_shape": (C.c_int, [C.c_int32, C.c_int32]),
+    "miosqp_qp_setup_models_prepared": (C.c_int, [C.c_int32, C.POINTER(SetupModel), C.POINTER(C.c_void_p), C.POINTER(SetupModelsStats),
+                                                  C.c_int32]),
     "miosqp_qp_debug_panel": (C.c_int, [C.c_void_p, C.c_int32, dp, C.c_int64, C.POINTER(C.c_int64)]),
     "miosqp_qp_setup_models_eligible": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(Settings)]),
     "miosqp_qp_setup_groups_live": (C.c_int, []),

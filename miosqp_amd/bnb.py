@@ -1811,7 +1811,8 @@ def _setup_models_own_reason(be, data, qp_settings, rho_auto_in_launch=False, la
     return None
 
 
-def setup_models(problems, settings, qp_settings, info=None, backend=None, rho_auto=None, large=None, large_rho_auto=None):
+def setup_models(problems, settings, qp_settings, info=None, backend=None, rho_auto=None, large=None, large_rho_auto=None,
+                 prepare=None):
     """Set up several DIFFERENT MIQP models -- each with its own P and A -- with ONE launch for the dense set-up of all of
     them (`qp.setup_models`, miosqp_qp_setup_models: one workgroup per model builds the Schur complement, its LDL^T, the
     triangular inverse, the product form, the explicit inverse and its guard; the engines share one stream, one device
@@ -1854,6 +1855,17 @@ def setup_models(problems, settings, qp_settings, info=None, backend=None, rho_a
     backend without the entry (the CPU oracle), is set up in place, the rule named in info["own"].  Opt-in; measured in
     profiles/setup_models_large_rho_auto.txt.  Any other value: ValueError.
 
+    prepare: None -- the host equilibrates every model of the call and packs its rows, as `MIOSQP.setup` does (about half
+    of the call's time per model).  "device" -- the models that the call's launches take hand their RAW problem to the
+    device, and one more launch ahead of the others (miosqp_qp_setup_models_prepared, k_prepare_models: one workgroup per
+    model) does both: the rows by variable, by constraint and of the two symmetric matrices, the Ruiz passes in place, D, E,
+    c, their inverses, the scaled q, the panel's values.  It composes with the three keywords above.  Everything it writes
+    is bit for bit the host's (maxima, correctly rounded 1 / sqrt, products, one sum by one thread in ascending order), so
+    every product of the set-up launches and every tree is that of the same call without the keyword, whatever the length
+    of the list and the position in it.  A model that no launch takes is set up by `MIOSQP.setup` as before; a backend
+    without the entry (the CPU oracle) ignores the keyword.  Opt-in; measured in profiles/setup_models_prepare.txt (a call
+    of ONE model loses: one more launch against a millisecond of host work).  Any other value: ValueError.
+
     ValueError before anything is queued, with the positions named: an empty list, a wrong number of settings, l > u, a P
     of the wrong shape.  A pivot that is not positive raises what `MIOSQP.setup` raises, with the position added; nothing
     of the call is left behind.
@@ -1861,8 +1873,10 @@ def setup_models(problems, settings, qp_settings, info=None, backend=None, rho_a
     info: a dict that is filled with batched (positions), own ({position: why}), launches, device_time, arena_bytes,
     host_time (seconds of the call outside the library's one), rho (the rho in use per position), forms
     ({'small': .., 'large': ..}: the batched models per launch) and rho_auto_large (the positions whose rho the large
-    launch chose)."""
+    launch chose) and prepare (the positions that were prepared on the device)."""
     t_call = time()
+    if prepare is not None and not (isinstance(prepare, str) and prepare == 'device'):
+        raise ValueError('setup_models: prepare must be None or "device", not %r' % (prepare,))
     if rho_auto not in (None, 'device'):
         raise ValueError('setup_models: rho_auto must be None or "device", not %r' % (rho_auto,))
     if large is not None and not (isinstance(large, str) and large == 'device'):
@@ -1907,6 +1921,7 @@ def setup_models(problems, settings, qp_settings, info=None, backend=None, rho_a
     own, batched = {}, []
     forms = dict(small=0, large=0)
     rho_auto_large = []
+    prepared = []
     for k in range(B):
         why = _setup_models_own_reason(be, datas[k], qp_settings[k], rho_auto == 'device', large == 'device',
                                        large == 'device' and large_rho_auto == 'device')
@@ -1939,6 +1954,9 @@ def setup_models(problems, settings, qp_settings, info=None, backend=None, rho_a
                     kw['large'] = True
                 if rho_auto_large:
                     kw['large_auto'] = True
+                if prepare == 'device' and hasattr(be, 'setup_models_prepared'):
+                    kw['prepare'] = True
+                    prepared = list(batched)
                 solvers, stats = be.setup_models(desc, **kw)
             except RuntimeError as ex:
                 import re
@@ -1966,5 +1984,6 @@ def setup_models(problems, settings, qp_settings, info=None, backend=None, rho_a
     if info is not None:
         rho = [float(m.work.solver.rho()) for m in out]
         info.update(batched=list(batched), own=dict(own), launches=launches, device_time=device_time, arena_bytes=arena_bytes,
-                    host_time=(time() - t_call) - lib_time, rho=rho, forms=forms, rho_auto_large=rho_auto_large)
+                    host_time=(time() - t_call) - lib_time, rho=rho, forms=forms, rho_auto_large=rho_auto_large,
+                    prepare=prepared)
     return out

@@ -261,6 +261,7 @@ struct CoopNode {
 #include "kernels_lockstep_sb.inc"  // strong and reliability branching in the lock-step trees: x at the integer positions, the children's gather, judge and bounds
 #include "host_lockstep_sb.inc"  // ... and its step in host_lockstep.inc's wave loop (C ABI miosqp_qp_solve_trees_lockstep_sb)
 #include "kernels_setup_models.inc"  // the dense set-up of many small models in one launch (k_setup_models)
+#include "kernels_prepare_models.inc"  // equilibration and packed rows of many models in one launch (k_prepare_models)
 #include "host_setup_models.inc"  // ... and its host side: the group, the arena, the engines (C ABI miosqp_qp_setup_models)
 #include "host_models.inc"  // what the one-launch tree entries share; trees of different models in one launch (C ABI miosqp_qp_tree_form, miosqp_qp_solve_trees_models)
 
@@ -2328,6 +2329,17 @@ int miosqp_qp_setup_models_eligible_large(int32_t n, int32_t M, const miosqp_qp_
 int miosqp_qp_setup_models_large_auto(int32_t B, const miosqp_setup_model *models, miosqp_qp_engine **out,
                                       miosqp_setup_models_stats *stats, int32_t rho_auto_in_launch) {
   return setup_models_run(B, models, out, stats, rho_auto_in_launch != 0, true, true);
+}
+
+int miosqp_qp_setup_models_prepared(int32_t B, const miosqp_setup_model *models, miosqp_qp_engine **out,
+                                    miosqp_setup_models_stats *stats, int32_t flags) {
+  if (flags & ~(MIOSQP_SETUP_MODELS_RHO_AUTO | MIOSQP_SETUP_MODELS_LARGE | MIOSQP_SETUP_MODELS_LARGE_RHO_AUTO)) {
+    g_err = "setup_models: unknown flag bits";
+    return MIOSQP_EARG;
+  }
+  const bool lra = (flags & MIOSQP_SETUP_MODELS_LARGE_RHO_AUTO) != 0;
+  return setup_models_run(B, models, out, stats, (flags & MIOSQP_SETUP_MODELS_RHO_AUTO) != 0,
+                          lra || (flags & MIOSQP_SETUP_MODELS_LARGE) != 0, lra, true);
 }
 
 int miosqp_qp_setup_models_eligible_large_auto(int32_t n, int32_t M, const miosqp_qp_settings *s) {

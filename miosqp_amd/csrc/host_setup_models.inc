@@ -135,10 +135,13 @@ bool setup_models_large_env_ok() {
 // its size is built by k_setup_models_large, a second launch of the same call, as the engine miosqp_qp_setup builds with
 // coop = 0, resident = 0, fold = 1, pers = 0; the table holds the small models first.  large_rho_auto
 // (miosqp_qp_setup_models_large_auto): large models with rho_auto = 1 are taken, and when there is one the large launch
-// is k_setup_models_large_auto.
+// is k_setup_models_large_auto.  prepare (miosqp_qp_setup_models_prepared): the raw problem goes up and k_prepare_models,
+// one more launch ahead of the others, builds what scale_problem and pack_factor_rows build on the host otherwise; the
+// host's mirrors (e->sc, e->fa) are filled from the download behind the launches.
 int setup_models_run(int32_t B, const miosqp_setup_model *ms, miosqp_qp_engine **out, miosqp_setup_models_stats *stats,
-                     bool rho_auto_in_launch, bool large = false, bool large_rho_auto = false) {
+                     bool rho_auto_in_launch, bool large = false, bool large_rho_auto = false, bool prepare = false) {
   namespace sm = miosqp::setup_models;
+  namespace pm = miosqp::prepare_models;
   static_assert(sizeof(Ctrl) <= sm::CTRL_BYTES, "Ctrl fits its place in the arena and the slab");
   // ---- refused before anything is queued ----
   {
@@ -235,20 +238,61 @@ int setup_models_run(int32_t B, const miosqp_setup_model *ms, miosqp_qp_engine *
     if (e->st.check_termination <= 0 || e->st.check_termination > e->st.max_iter) e->st.check_termination = e->st.max_iter;
     if (form[(size_t)b] == sm::FORM_LARGE) e->st.coop = 0;  // (the engine that comes out is not the cooperative grid's)
     e->setup_on_device = false;
-    miosqp::scale_problem(m.n, m.M, m.Pp, m.Pi, m.Px, m.Ap, m.Ai, m.Ax, m.q, m.settings->scaling, e->sc);
+    if (!prepare) miosqp::scale_problem(m.n, m.M, m.Pp, m.Pi, m.Px, m.Ap, m.Ai, m.Ax, m.q, m.settings->scaling, e->sc);
     miosqp::Factor &f = e->fa;  // the rows; Linv / LinvT stay empty on the host, as where the device keeps them
     f.n = m.n; f.M = m.M; f.rho = m.settings->rho; f.sigma = m.settings->sigma;
     f.ld = (m.n + 15) & ~15;
-    miosqp::pack_factor_rows(e->sc, m.Pp, m.Pi, m.Px, f.rho, f);
+    if (!prepare) {
+      miosqp::pack_factor_rows(e->sc, m.Pp, m.Pi, m.Px, f.rho, f);
+    } else {
+      // the integer half of both: the patterns of the scaled problem's mirror (P's upper triangle, A) and the pointer arrays
+      // of the four packed structures; the values and the column indices of the rows come back with the download
+      miosqp::Scaled &sc = e->sc;
+      sc.n = m.n; sc.M = m.M;
+      sc.Pp.assign((size_t)m.n + 1, 0);
+      sc.Pi.clear();
+      int64_t ndiag = 0;
+      for (int j = 0; j < m.n; j++) {
+        sc.Pp[(size_t)j] = (int)sc.Pi.size();
+        for (int p = m.Pp[j]; p < m.Pp[j + 1]; p++)
+          if (m.Pi[p] <= j) {
+            sc.Pi.push_back(m.Pi[p]);
+            ndiag += m.Pi[p] == j;
+          }
+      }
+      sc.Pp[(size_t)m.n] = (int)sc.Pi.size();
+      sc.Ap.assign(m.Ap, m.Ap + m.n + 1);
+      sc.Ai.assign(m.Ai, m.Ai + m.Ap[m.n]);
+      f.panel_by_var.rows = m.n; f.panel_by_var.cols = m.M;
+      f.panel_by_con.rows = m.M; f.panel_by_con.cols = m.n;
+      f.Pbar.rows = f.Pbar.cols = f.Praw.rows = f.Praw.cols = m.n;
+      f.panel_by_var.ptr.resize((size_t)m.n + 1);
+      f.panel_by_con.ptr.resize((size_t)m.M + 1);
+      f.Pbar.ptr.resize((size_t)m.n + 1);
+      int64_t up = 0;
+      pm::prepare_pointers(m.n, m.M, m.Pp, m.Pi, m.Ap, m.Ai, f.panel_by_var.ptr.data(), f.panel_by_con.ptr.data(), f.Pbar.ptr.data(), &up);
+      f.Praw.ptr = f.Pbar.ptr;
+      f.panel_by_var.nnz = f.panel_by_con.nnz = f.nnz_panel = m.Ap[m.n];
+      f.Pbar.nnz = f.Praw.nnz = 2 * up - ndiag;
+      const size_t nv = (size_t)f.panel_by_var.ptr[(size_t)m.n], nc = (size_t)f.panel_by_con.ptr[(size_t)m.M], np = (size_t)f.Pbar.ptr[(size_t)m.n];
+      f.panel_by_var.idx.resize(nv); f.panel_by_var.val.resize(nv); f.At_val.resize(nv);
+      f.panel_by_con.idx.resize(nc); f.panel_by_con.val.resize(nc); f.A_val.resize(nc);
+      f.Pbar.idx.resize(np); f.Pbar.val.resize(np); f.Praw.idx.resize(np); f.Praw.val.resize(np);
+    }
     f.nnz_tail = (int64_t)m.n * (m.n - 1) / 2;
     e->nnzA = m.Ap[m.n];
     e->A_raw.assign(m.Ax, m.Ax + m.Ap[m.n]);
     e->nnzPtriu = (int64_t)e->sc.Pi.size();
     sh[(size_t)b] = sm::Shape{m.n, m.M, f.panel_by_var.idx.size(), f.panel_by_con.idx.size(), f.Pbar.idx.size(), f.Praw.idx.size(),
                               m.settings->rho_auto ? 1 : 0, form[(size_t)b]};
+    if (prepare) {
+      sh[(size_t)b].prepare = 1;
+      sh[(size_t)b].nnzP = (size_t)m.Pp[m.n];
+      sh[(size_t)b].nnzA = (size_t)m.Ap[m.n];
+    }
   }
-  const sm::Plan P = sm::plan(sh, sizeof(SetupModel));
-  tick("host: equilibration + packed rows");
+  const sm::Plan P = sm::plan(sh, sizeof(SetupModel), sizeof(pm::IO));
+  tick(prepare ? "host: patterns + row pointers" : "host: equilibration + packed rows");
   // ---- the group: one stream, one arena (zero-filled on that stream, ahead of the upload), one pinned slab ----
   grp = new SetupGroup();
   grp->device = device;
@@ -284,24 +328,34 @@ int setup_models_run(int32_t B, const miosqp_setup_model *ms, miosqp_qp_engine *
     const miosqp_qp_settings *st = m.settings;
     const int n = m.n, M = m.M;
     stage_vec(hs, s, sm::PV_PTR, f.panel_by_var.ptr.data(), f.panel_by_var.ptr.size());
-    stage_vec(hs, s, sm::PV_IDX, f.panel_by_var.idx.data(), f.panel_by_var.idx.size());
-    stage_vec(hs, s, sm::PV_L, f.panel_by_var.val.data(), f.panel_by_var.val.size());
-    stage_vec(hs, s, sm::PV_AT, f.At_val.data(), f.At_val.size());
     stage_vec(hs, s, sm::PC_PTR, f.panel_by_con.ptr.data(), f.panel_by_con.ptr.size());
-    stage_vec(hs, s, sm::PC_IDX, f.panel_by_con.idx.data(), f.panel_by_con.idx.size());
-    stage_vec(hs, s, sm::PC_L, f.panel_by_con.val.data(), f.panel_by_con.val.size());
-    stage_vec(hs, s, sm::PC_A, f.A_val.data(), f.A_val.size());
     stage_vec(hs, s, sm::PB_PTR, f.Pbar.ptr.data(), f.Pbar.ptr.size());
-    stage_vec(hs, s, sm::PB_IDX, f.Pbar.idx.data(), f.Pbar.idx.size());
-    stage_vec(hs, s, sm::PB_VAL, f.Pbar.val.data(), f.Pbar.val.size());
     stage_vec(hs, s, sm::PR_PTR, f.Praw.ptr.data(), f.Praw.ptr.size());
-    stage_vec(hs, s, sm::PR_IDX, f.Praw.idx.data(), f.Praw.idx.size());
-    stage_vec(hs, s, sm::PR_VAL, f.Praw.val.data(), f.Praw.val.size());
-    stage_vec(hs, s, sm::D_, e->sc.D.data(), (size_t)n);
-    stage_vec(hs, s, sm::DINV, e->sc.Dinv.data(), (size_t)n);
-    stage_vec(hs, s, sm::E_, e->sc.E.data(), (size_t)M);
-    stage_vec(hs, s, sm::EINV, e->sc.Einv.data(), (size_t)M);
-    stage_vec(hs, s, sm::Q, e->sc.q.data(), (size_t)n);
+    if (!prepare) {
+      stage_vec(hs, s, sm::PV_IDX, f.panel_by_var.idx.data(), f.panel_by_var.idx.size());
+      stage_vec(hs, s, sm::PV_L, f.panel_by_var.val.data(), f.panel_by_var.val.size());
+      stage_vec(hs, s, sm::PV_AT, f.At_val.data(), f.At_val.size());
+      stage_vec(hs, s, sm::PC_IDX, f.panel_by_con.idx.data(), f.panel_by_con.idx.size());
+      stage_vec(hs, s, sm::PC_L, f.panel_by_con.val.data(), f.panel_by_con.val.size());
+      stage_vec(hs, s, sm::PC_A, f.A_val.data(), f.A_val.size());
+      stage_vec(hs, s, sm::PB_IDX, f.Pbar.idx.data(), f.Pbar.idx.size());
+      stage_vec(hs, s, sm::PB_VAL, f.Pbar.val.data(), f.Pbar.val.size());
+      stage_vec(hs, s, sm::PR_IDX, f.Praw.idx.data(), f.Praw.idx.size());
+      stage_vec(hs, s, sm::PR_VAL, f.Praw.val.data(), f.Praw.val.size());
+      stage_vec(hs, s, sm::D_, e->sc.D.data(), (size_t)n);
+      stage_vec(hs, s, sm::DINV, e->sc.Dinv.data(), (size_t)n);
+      stage_vec(hs, s, sm::E_, e->sc.E.data(), (size_t)M);
+      stage_vec(hs, s, sm::EINV, e->sc.Einv.data(), (size_t)M);
+      stage_vec(hs, s, sm::Q, e->sc.q.data(), (size_t)n);
+    } else {  // the raw problem
+      const size_t nnzP = (size_t)m.Pp[n], nnzA = (size_t)m.Ap[n];
+      memcpy(hs + s.raw[sm::RAW_PP].off, m.Pp, sizeof(int32_t) * ((size_t)n + 1));
+      if (nnzP) memcpy(hs + s.raw[sm::RAW_PI].off, m.Pi, sizeof(int32_t) * nnzP);
+      if (nnzP) memcpy(hs + s.raw[sm::RAW_PX].off, m.Px, sizeof(double) * nnzP);
+      memcpy(hs + s.raw[sm::RAW_AP].off, m.Ap, sizeof(int32_t) * ((size_t)n + 1));
+      if (nnzA) memcpy(hs + s.raw[sm::RAW_AI].off, m.Ai, sizeof(int32_t) * nnzA);
+      if (nnzA) memcpy(hs + s.raw[sm::RAW_AX].off, m.Ax, sizeof(double) * nnzA);
+    }
     stage_vec(hs, s, sm::QRAW, m.q, (size_t)n);
     stage_vec(hs, s, sm::RAW, m.l, (size_t)M);
     memcpy(hs + s.part[sm::RAW].off + sizeof(double) * M, m.u, sizeof(double) * M);
@@ -362,6 +416,25 @@ int setup_models_run(int32_t B, const miosqp_setup_model *ms, miosqp_qp_engine *
     au.alpha = d.alpha;
     au.q = d.q; au.pv_At = d.pv_At;
     au.pv_L = arena_at<double>(dv, s, sm::PV_L); au.pc_L = arena_at<double>(dv, s, sm::PC_L);
+    if (prepare) {  // entry b of k_prepare_models' table
+      pm::IO &pi = reinterpret_cast<pm::IO *>(hs + P.ptab_off)[b];
+      pi.n = n; pi.M = M; pi.passes = st->scaling; pi.rho = st->rho;
+      pi.Pp = reinterpret_cast<const int *>(dv + s.raw[sm::RAW_PP].off); pi.Pi = reinterpret_cast<const int *>(dv + s.raw[sm::RAW_PI].off);
+      pi.Px = reinterpret_cast<const double *>(dv + s.raw[sm::RAW_PX].off);
+      pi.Ap = reinterpret_cast<const int *>(dv + s.raw[sm::RAW_AP].off); pi.Ai = reinterpret_cast<const int *>(dv + s.raw[sm::RAW_AI].off);
+      pi.Ax = reinterpret_cast<const double *>(dv + s.raw[sm::RAW_AX].off);
+      pi.qraw = d.qraw;
+      pi.pv_ptr = d.pv_ptr; pi.pc_ptr = d.pc_ptr; pi.pb_ptr = d.pb_ptr; pi.pr_ptr = d.pr_ptr;
+      pi.pv_idx = arena_at<int>(dv, s, sm::PV_IDX); pi.pc_idx = arena_at<int>(dv, s, sm::PC_IDX);
+      pi.pb_idx = arena_at<int>(dv, s, sm::PB_IDX); pi.pr_idx = arena_at<int>(dv, s, sm::PR_IDX);
+      pi.pv_L = arena_at<double>(dv, s, sm::PV_L); pi.pv_At = arena_at<double>(dv, s, sm::PV_AT);
+      pi.pc_L = arena_at<double>(dv, s, sm::PC_L); pi.pc_A = arena_at<double>(dv, s, sm::PC_A);
+      pi.pb_val = arena_at<double>(dv, s, sm::PB_VAL); pi.pr_val = arena_at<double>(dv, s, sm::PR_VAL);
+      pi.D = arena_at<double>(dv, s, sm::D_); pi.Dinv = arena_at<double>(dv, s, sm::DINV);
+      pi.E = arena_at<double>(dv, s, sm::E_); pi.Einv = arena_at<double>(dv, s, sm::EINV);
+      pi.q = arena_at<double>(dv, s, sm::Q);
+      pi.sc = reinterpret_cast<pm::Scalars *>(dv + s.scal.off);
+    }
     // the engine joins the group: its pool is the rest of its slice, its stream the group's, its events its own
     e->pool_base = dv + s.part[sm::RESERVE].off;
     e->pool_cap = s.part[sm::RESERVE].bytes;
@@ -402,6 +475,9 @@ int setup_models_run(int32_t B, const miosqp_setup_model *ms, miosqp_qp_engine *
   miosqp_qp_engine *e0 = eng[0];
   SMCHK(hipEventRecord(e0->ev0, grp->stream));
   SMCHK(hipMemcpyAsync(dv, hs, P.up_bytes, hipMemcpyHostToDevice, grp->stream));
+  if (prepare)
+    hipLaunchKernelGGL(k_prepare_models, dim3((unsigned)B), dim3(pm::THREADS), P.lds_bytes_prepare, grp->stream,
+                       reinterpret_cast<const pm::IO *>(dv + P.ptab_off));
   if (P.n_small && any_auto)
     hipLaunchKernelGGL(k_setup_models_auto, dim3((unsigned)P.n_small), dim3(sm::THREADS), P.lds_bytes, grp->stream,
                        reinterpret_cast<const SetupModel *>(dv));
@@ -415,12 +491,15 @@ int setup_models_run(int32_t B, const miosqp_setup_model *ms, miosqp_qp_engine *
     hipLaunchKernelGGL(k_setup_models_large, dim3((unsigned)P.n_large), dim3(sm::THREADS), P.lds_bytes_large, grp->stream,
                        reinterpret_cast<const SetupModel *>(dv) + P.n_small);
   SMCHK(hipGetLastError());
-  SMCHK(hipMemcpyAsync(hs + P.pin_rec, dv + P.rec_off, P.rec_bytes, hipMemcpyDeviceToHost, grp->stream));
+  if (prepare)  // (the rows and scalings the device wrote, with the records behind them: one copy)
+    SMCHK(hipMemcpyAsync(hs + P.pin_prep, dv + P.prep_off, P.prep_bytes + P.rec_bytes, hipMemcpyDeviceToHost, grp->stream));
+  else
+    SMCHK(hipMemcpyAsync(hs + P.pin_rec, dv + P.rec_off, P.rec_bytes, hipMemcpyDeviceToHost, grp->stream));
   SMCHK(hipEventRecord(e0->ev1, grp->stream));
   SMCHK(hipStreamSynchronize(grp->stream));
   float ms_dev = 0;
   SMCHK(hipEventElapsedTime(&ms_dev, e0->ev0, e0->ev1));
-  tick(P.n_large ? "upload, set-up launches, records back" : any_auto ? "upload, k_setup_models_auto, records back" : "upload, k_setup_models, records back");
+  tick(prepare ? "upload, k_prepare_models, set-up launches, rows and records back" : P.n_large ? "upload, set-up launches, records back" : any_auto ? "upload, k_setup_models_auto, records back" : "upload, k_setup_models, records back");
   const sm::Record *rec = reinterpret_cast<const sm::Record *>(hs + P.pin_rec);
   for (int b = 0; b < B; b++)
     if (rec[b].bad_pivot) {
@@ -434,6 +513,51 @@ int setup_models_run(int32_t B, const miosqp_setup_model *ms, miosqp_qp_engine *
       g_err += ")";
       return fail(MIOSQP_EFACTOR);
     }
+  // ---- prepared on the device: the host's mirrors of the scaled problem and of the rows, from the download (the panel's
+  //      values are those at the rho the launch built with; c and cinv go to Dev before any chunk is captured) ----
+  if (prepare) {
+    for (int b = 0; b < B; b++) {
+      miosqp_qp_engine *e = eng[(size_t)b];
+      const sm::Slot &s = P.slot[(size_t)b];
+      miosqp::Scaled &sc = e->sc;
+      miosqp::Factor &f = e->fa;
+      const size_t n = (size_t)e->n, M = (size_t)e->M;
+      auto back = [&](int part, void *dst, size_t bytes) {
+        if (bytes) memcpy(dst, hs + P.pin_prep + (s.part[part].off - P.prep_off), bytes);
+      };
+      const size_t I = sizeof(int), F = sizeof(double);
+      back(sm::PV_IDX, f.panel_by_var.idx.data(), I * f.panel_by_var.idx.size());
+      back(sm::PV_L, f.panel_by_var.val.data(), F * f.panel_by_var.val.size());
+      back(sm::PV_AT, f.At_val.data(), F * f.At_val.size());
+      back(sm::PC_IDX, f.panel_by_con.idx.data(), I * f.panel_by_con.idx.size());
+      back(sm::PC_L, f.panel_by_con.val.data(), F * f.panel_by_con.val.size());
+      back(sm::PC_A, f.A_val.data(), F * f.A_val.size());
+      back(sm::PB_IDX, f.Pbar.idx.data(), I * f.Pbar.idx.size());
+      back(sm::PB_VAL, f.Pbar.val.data(), F * f.Pbar.val.size());
+      back(sm::PR_IDX, f.Praw.idx.data(), I * f.Praw.idx.size());
+      back(sm::PR_VAL, f.Praw.val.data(), F * f.Praw.val.size());
+      sc.D.resize(n); sc.Dinv.resize(n); sc.E.resize(M); sc.Einv.resize(M); sc.q.resize(n);
+      back(sm::D_, sc.D.data(), F * n);
+      back(sm::DINV, sc.Dinv.data(), F * n);
+      back(sm::E_, sc.E.data(), F * M);
+      back(sm::EINV, sc.Einv.data(), F * M);
+      back(sm::Q, sc.q.data(), F * n);
+      const pm::Scalars *ps = reinterpret_cast<const pm::Scalars *>(hs + P.pin_prep + (s.scal.off - P.prep_off));
+      sc.c = ps->c;
+      sc.cinv = ps->cinv;
+      e->d.c = sc.c;
+      e->d.cinv = sc.cinv;
+      // the scaled CSC: a column of P's upper triangle opens its row of Pbar, a column of A is its row by variable
+      sc.Px.resize(sc.Pi.size());
+      sc.Ax.resize(sc.Ai.size());
+      for (size_t j = 0; j < n; j++) {
+        const size_t cp = (size_t)(sc.Pp[j + 1] - sc.Pp[j]), ca = (size_t)(sc.Ap[j + 1] - sc.Ap[j]);
+        if (cp) memcpy(&sc.Px[(size_t)sc.Pp[j]], &f.Pbar.val[(size_t)f.Pbar.ptr[j]], F * cp);
+        if (ca) memcpy(&sc.Ax[(size_t)sc.Ap[j]], &f.At_val[(size_t)f.panel_by_var.ptr[j]], F * ca);
+      }
+    }
+    tick("host: mirrors from the download");
+  }
   // ---- rho chosen in the launch: the host's mirror follows (st, Dev, the factor's rho and the panel's values, formed
   //      with the expression the kernel used, which is build_factor(reuse_rows)'s) ----
   for (int b = 0; b < B; b++) {
@@ -556,7 +680,7 @@ int setup_models_run(int32_t B, const miosqp_setup_model *ms, miosqp_qp_engine *
   for (int b = 0; b < B; b++) out[b] = eng[(size_t)b];
   const double wall_s = wall() - t_begin;
   stats->models = B;
-  stats->launches = (P.n_small ? 1 : 0) + (P.n_large ? 1 : 0);
+  stats->launches = (P.n_small ? 1 : 0) + (P.n_large ? 1 : 0) + (prepare ? 1 : 0);
   stats->device_mallocs = (int32_t)(g_made_device_mallocs - made0[0]);  // (with what the engines' own pools took, if anything)
   stats->host_mallocs = (int32_t)(g_made_host_mallocs - made0[1]);
   stats->streams = (int32_t)(g_made_streams - made0[2]);

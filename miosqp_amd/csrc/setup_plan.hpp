@@ -10,6 +10,7 @@
 
 #include "setup_models_body.hpp"  // eligible_shape, lds_doubles, Record (plain C++ too)
 #include "setup_models_large_body.hpp"  // eligible_shape_large, lds_doubles_large: the launch for models beyond n + M = 192
+#include "prepare_models_body.hpp"  // lds_doubles of k_prepare_models, Scalars
 
 namespace miosqp {
 namespace setup_models {
@@ -147,6 +148,8 @@ struct Shape {
                                             // constraint, Pbar, Praw
   int rho_auto = 0;                         // 1: the launch chooses this model's rho (LDS for the probing iterations)
   int form = FORM_SMALL;                    // which launch builds it (FORM_LARGE: no W, no Kc, the large LDS rule)
+  int prepare = 0;                          // 1: k_prepare_models builds the packed rows and the scalings from the raw problem
+  size_t nnzP = 0, nnzA = 0;                // prepare: entries of P as given and of A (the raw CSC goes up instead of the rows)
 };
 
 // the arrays of one model, in the order they lie in the arena
@@ -163,6 +166,10 @@ enum Part {
   NPARTS
 };
 constexpr int FIRST_PRODUCT = LINV, FIRST_ITERATE = L_;
+// the raw problem of a model that k_prepare_models prepares: uploaded in place of the packed rows
+enum RawPart { RAW_PP, RAW_PI, RAW_PX, RAW_AP, RAW_AI, RAW_AX, NRAW };
+// of the parts before FIRST_PRODUCT a prepared model still uploads these; the others the device writes
+inline bool prepared_uploads(int k) { return k == PV_PTR || k == PC_PTR || k == PB_PTR || k == PR_PTR || k == QRAW || k == RAW; }
 
 struct Span {
   size_t off = 0, bytes = 0;  // from the arena's base
@@ -174,6 +181,8 @@ struct Slot {
   size_t entry = 0;  // its place in the table: small models first, then the large ones, each in the caller's order
   // the pinned slab: h_in (in_cap doubles), h_out (out_cap doubles), h_ctrl, h_ctrl2 (two control blocks)
   size_t pin_in = 0, pin_out = 0, pin_ctrl = 0, pin_ctrl2 = 0, in_cap = 0, out_cap = 0;
+  Span raw[NRAW];  // a prepared model: its raw CSC in the upload; no bytes otherwise
+  Span scal;       // ... and the scalars of its equilibration (c, cinv) among the device-written parts
 };
 
 // [ table | uploaded arrays of every model | products, iterates, reserve of every model | records ]: the first two parts
@@ -189,6 +198,14 @@ struct Plan {
   size_t lds_bytes = 0;            // dynamic LDS of the launch: the largest model's
   size_t n_small = 0, n_large = 0; // table entries [0, n_small) go to the small launch, [n_small, n_small + n_large) to the large one
   size_t lds_bytes_large = 0;      // dynamic LDS of the large launch
+  // With prepared models the arena is [ table | table of k_prepare_models | uploaded | device-written rows and scalings
+  // of the prepared models | records | products, iterates, reserve ]: the fourth and fifth part come back in ONE copy
+  // (the host's mirrors are filled from it) and land in the slab at pin_prep, the records behind them at pin_rec.
+  size_t n_prepare = 0;
+  size_t ptab_off = 0, ptab_bytes = 0;
+  size_t prep_off = 0, prep_bytes = 0;
+  size_t pin_prep = 0;
+  size_t lds_bytes_prepare = 0;    // dynamic LDS of k_prepare_models
 };
 
 inline size_t round_up(size_t v, size_t to) { return (v + to - 1) / to * to; }
@@ -219,20 +236,37 @@ inline void part_bytes(const Shape &s, size_t (&by)[NPARTS]) {
   by[RESERVE] = arr(n, I) + arr(n * ldf, F) + arr(n, F) + arr(3 * N + 8, F) + arr(8, F) + 4096;
 }
 
-inline Plan plan(const std::vector<Shape> &sh, size_t entry_bytes) {
+inline Plan plan(const std::vector<Shape> &sh, size_t entry_bytes, size_t prepare_entry_bytes = 0) {
   Plan P;
   const size_t B = sh.size();
   P.slot.resize(B);
   P.table_bytes = round_up(B * entry_bytes, ALIGN);
   size_t at = P.table_bytes;
+  for (size_t b = 0; b < B; b++) P.n_prepare += sh[b].prepare ? 1 : 0;
+  if (P.n_prepare) {  // (one entry per model of the call, by position: the launch reads those of the prepared ones)
+    P.ptab_off = at;
+    P.ptab_bytes = round_up(B * prepare_entry_bytes, ALIGN);
+    at += P.ptab_bytes;
+  }
   std::vector<size_t> by((size_t)NPARTS * B);
   for (size_t b = 0; b < B; b++) {
     size_t one[NPARTS];
     part_bytes(sh[b], one);
     for (int k = 0; k < NPARTS; k++) by[b * NPARTS + k] = one[k];
     for (int k = 0; k < FIRST_PRODUCT; k++) {
+      if (sh[b].prepare && !prepared_uploads(k)) continue;
       P.slot[b].part[k] = Span{at, one[k]};
       at += one[k];
+    }
+    if (sh[b].prepare) {
+      const size_t n1 = (size_t)sh[b].n + 1, I = sizeof(int32_t), F = sizeof(double);
+      const size_t raw[NRAW] = {arr(n1, I), arr(sh[b].nnzP, I), arr(sh[b].nnzP, F), arr(n1, I), arr(sh[b].nnzA, I), arr(sh[b].nnzA, F)};
+      for (int k = 0; k < NRAW; k++) {
+        P.slot[b].raw[k] = Span{at, raw[k]};
+        at += raw[k];
+      }
+      const size_t lds = prepare_models::lds_doubles(sh[b].n, sh[b].M) * sizeof(double);
+      if (lds > P.lds_bytes_prepare) P.lds_bytes_prepare = lds;
     }
     if (sh[b].form == FORM_LARGE) {
       const size_t lds = (sh[b].rho_auto ? lds_doubles_large_auto(sh[b].n, sh[b].M) : lds_doubles_large(sh[b].n, sh[b].M)) * sizeof(double);
@@ -246,15 +280,34 @@ inline Plan plan(const std::vector<Shape> &sh, size_t entry_bytes) {
   }
   for (size_t b = 0, s = 0, l = P.n_small; b < B; b++) P.slot[b].entry = sh[b].form == FORM_LARGE ? l++ : s++;
   P.up_bytes = at;
+  if (P.n_prepare) {
+    P.prep_off = at;
+    for (size_t b = 0; b < B; b++) {
+      if (!sh[b].prepare) continue;
+      for (int k = 0; k < FIRST_PRODUCT; k++) {
+        if (prepared_uploads(k)) continue;
+        P.slot[b].part[k] = Span{at, by[b * NPARTS + k]};
+        at += by[b * NPARTS + k];
+      }
+      P.slot[b].scal = Span{at, ALIGN};
+      at += ALIGN;
+    }
+    P.prep_bytes = at - P.prep_off;
+    P.rec_off = at;
+    P.rec_bytes = round_up(B * sizeof(Record), ALIGN);
+    at += P.rec_bytes;
+  }
   for (size_t b = 0; b < B; b++)
     for (int k = FIRST_PRODUCT; k < NPARTS; k++) {
       P.slot[b].part[k] = Span{at, by[b * NPARTS + k]};
       at += by[b * NPARTS + k];
     }
-  P.rec_off = at;
-  P.rec_bytes = round_up(B * sizeof(Record), ALIGN);
+  if (!P.n_prepare) {
+    P.rec_off = at;
+    P.rec_bytes = round_up(B * sizeof(Record), ALIGN);
+    at += P.rec_bytes;
+  }
   for (size_t b = 0; b < B; b++) P.slot[b].rec = P.rec_off + b * sizeof(Record);
-  at += P.rec_bytes;
   P.total_bytes = at;
   // the slab: while the call runs it holds the upload's image; afterwards the same bytes are the engines' staging
   size_t pin = 0;
@@ -273,6 +326,10 @@ inline Plan plan(const std::vector<Shape> &sh, size_t entry_bytes) {
     pin += round_up(2 * CTRL_BYTES, ALIGN);
   }
   P.pin_rec = round_up(pin > P.up_bytes ? pin : P.up_bytes, ALIGN);
+  if (P.n_prepare) {  // (the download is one copy: rows and scalings, then the records)
+    P.pin_prep = P.pin_rec;
+    P.pin_rec = P.pin_prep + P.prep_bytes;
+  }
   P.pin_bytes = P.pin_rec + P.rec_bytes;
   return P;
 }

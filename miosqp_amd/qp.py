@@ -268,7 +268,7 @@ def setup_groups_live():
     return int(_lib.load().miosqp_qp_setup_groups_live())
 
 
-def setup_models(models, rho_auto_in_launch=False, large=False, large_auto=False):
+def setup_models(models, rho_auto_in_launch=False, large=False, large_auto=False, prepare=False):
     """The set-up of several DIFFERENT small models in ONE launch (miosqp_qp_setup_models): the dense part of every
     model -- Schur complement, LDL^T, triangular inverse, product form, explicit inverse, its guard -- by one workgroup
     per model; the engines share one stream, one device arena and one pinned slab.
@@ -286,6 +286,11 @@ def setup_models(models, rho_auto_in_launch=False, large=False, large_auto=False
     large_auto=True (read with large=True; miosqp_qp_setup_models_large_auto): a large model with rho="auto" is taken too
     (setup_models_eligible_large_auto); the workgroup that builds it chooses rho as the small launch does, on the triangle
     in LDS with Abar read from L2, and every product is that of the same model at a fixed rho equal to the chosen one.
+
+    prepare=True (miosqp_qp_setup_models_prepared, with the three keywords above as its flag bits): the raw problem goes
+    up and one more launch ahead of the others (k_prepare_models, one workgroup per model) equilibrates it and packs the
+    rows, where the host does both otherwise (about as long per model as everything else of the call together); what
+    it writes is bit for bit the host's, and so is every engine.  stats.launches counts the additional launch.
 
     models: dicts with P, q, A, l, u (as OSQP.setup takes them), settings (a dict of OSQP.setup's keywords), and
     optionally i_idx with m_orig (set_integer_rows is applied) and root = (l_root, u_root, eps_int_feas, eps_lin)
@@ -327,7 +332,10 @@ def setup_models(models, rho_auto_in_launch=False, large=False, large_auto=False
         shapes.append((n, m, s))
     hs = (C.c_void_p * max(B, 1))()
     stats = _lib.SetupModelsStats()
-    if large:
+    if prepare:
+        flags = (1 if rho_auto_in_launch else 0) | (2 if large else 0) | (4 if large and large_auto else 0)
+        _check(lib.miosqp_qp_setup_models_prepared(B, desc, hs, C.byref(stats), flags), "setup_models")
+    elif large:
         entry = lib.miosqp_qp_setup_models_large_auto if large_auto else lib.miosqp_qp_setup_models_large
         _check(entry(B, desc, hs, C.byref(stats), 1 if rho_auto_in_launch else 0), "setup_models")
     else:
@@ -339,6 +347,12 @@ def setup_models(models, rho_auto_in_launch=False, large=False, large_auto=False
         g._h, g.n, g.m, g.settings = C.c_void_p(hs[k]), n, m, s
         out.append(g)
     return out, stats
+
+
+def setup_models_prepared(models, **kw):
+    """setup_models(models, prepare=True, ...): equilibration and packed rows by a launch of the call
+    (miosqp_qp_setup_models_prepared)"""
+    return setup_models(models, prepare=True, **kw)
 
 
 class DevicePtr(object):
