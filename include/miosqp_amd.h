@@ -473,6 +473,52 @@ int miosqp_qp_solve_trees_models_large(int32_t B, miosqp_qp_engine *const *engin
                                        const int32_t *max_iter_bb, int32_t leaf_cap, double *const *x_out,
                                        miosqp_tree_info *info, miosqp_models_stats *stats);
 
+/* ---- ... with round and fix inside the one-launch trees (opt-in) ----------------------------------------
+ * The primal heuristic of Workspace.primal_heuristic / Workspace.round_and_fix (miosqp_amd/bnb.py) inside the tree launch:
+ * a tree counts the nodes it is about to branch, and on every rf_every-th of them (the first included), after the node's
+ * own rounding heuristic has updated the incumbent and pruned, the workgroup solves rf_candidates copies of the node with
+ * every integer row fixed to min(max(floor(x_i + theta_k), lo), hi), theta_k = (k + 1) / (rf_candidates + 1), lo / hi the
+ * node's bounds, x the node's clamped solution -- warm-started from the node, at most rf_max_iter iterations each, the
+ * node's termination test.  A candidate with an x (solved or at its cap) whose rounded point keeps the ROOT's rows within
+ * eps_abs is feasible; the feasible candidate of lowest objective below the incumbent's, ties to the lowest k, becomes the
+ * incumbent (its value is the device's sum) and the list is pruned; then the node branches as without the heuristic.
+ * The semantics are those of miosqp_qp_round_and_fix and miosqp_qp_solve_trees_lockstep_rf; the kernels are k_tree_rf,
+ * k_tree_rf_m and k_tree_rf_r_m (miosqp_amd/csrc/kernels_tree.inc), which need no LDS beyond their plain forms: every
+ * engine those take is taken.  There is no one-wavefront form with the heuristic: n + M <= 64 runs in the workgroup form.
+ * info->osqp_iter counts the nodes' iterations only; the heuristic's are in the record below. */
+typedef struct miosqp_tree_rf_info {
+  int32_t calls;       /* firings of the heuristic (what rf_stats['calls'] counts) */
+  int32_t candidates;  /* candidates solved: calls x rf_candidates */
+  int32_t feasible;    /* candidates with an x whose rounded point keeps the root's rows */
+  int32_t improved;    /* firings that replaced the incumbent */
+  int32_t osqp_iter;   /* ADMM iterations of all candidates */
+  int32_t form;        /* the launch that ran the tree: 1 wave, 2 group, 3 reduced, 4 group with round and fix, 5 reduced with it */
+  int32_t pad0, pad1;
+} miosqp_tree_rf_info;
+
+/* miosqp_qp_solve_trees with the heuristic in every tree (Workspace.primal_heuristic): rf_candidates in 1..32,
+ * rf_max_iter >= 1, rf_every >= 1 (MIOSQP_EARG otherwise, before anything is queued); rf_info B records, per instance. */
+int miosqp_qp_solve_trees_rf(miosqp_qp_engine *e, int32_t B, const double *q, const double *l, const double *u,
+                             const double *x0, const double *y0, const double *upper0, const double *x_inc0,
+                             int32_t tree_explor_rule, int32_t max_iter_bb, int32_t rf_candidates, int32_t rf_max_iter,
+                             int32_t rf_every, double *x_out, miosqp_tree_info *info, miosqp_tree_rf_info *rf_info);
+
+/* miosqp_qp_solve_trees_models_large with the heuristic per model (Workspace.primal_heuristic): rf_candidates[b] in
+ * 0..32 -- 0: the heuristic is off for model b, which goes into the launch it goes into without this entry and gets that
+ * result bit for bit --, rf_max_iter[b] >= 1, rf_every[b] >= 1 (read for every model; MIOSQP_EARG naming the model
+ * otherwise, before anything is queued).  The models with the heuristic form up to two more launches behind the other
+ * three: the workgroup form (forms 1 and 2 of miosqp_qp_tree_form) and the reduced form (form 3); such a model gets bit
+ * for bit what miosqp_qp_solve_trees_rf(engines[b], 1, ...) gives it where that entry takes it.  leaf_cap: 0 keeps the
+ * reduced forms out (an engine of miosqp_qp_tree_form 0 is MIOSQP_EUNSUPPORTED, as in miosqp_qp_solve_trees_models), else
+ * at least 2.  rf_info[b]: the counters and the launch that ran model b (zeros and form 1..3 with the heuristic off).
+ * stats: models_wave, models_group and pad count the models of the three plain launches; launches may be 5. */
+int miosqp_qp_solve_trees_models_rf(int32_t B, miosqp_qp_engine *const *engines, const double *const *q, const double *const *l,
+                                    const double *const *u, const double *const *x0, const double *const *y0,
+                                    const double *upper0, const double *const *x_inc0, const int32_t *tree_explor_rule,
+                                    const int32_t *max_iter_bb, int32_t leaf_cap, const int32_t *rf_candidates,
+                                    const int32_t *rf_max_iter, const int32_t *rf_every, double *const *x_out,
+                                    miosqp_tree_info *info, miosqp_tree_rf_info *rf_info, miosqp_models_stats *stats);
+
 /* ---- polishes of DIFFERENT models in one launch -------------------------------------------------------
  * The polish of the "own P and A per MIQP" pattern: the reference sets up, solves and polishes one model per MIQP
  * (miosqp/solver.py:174-212 per model; `polish` reaches OSQP through qp_settings, miosqp/workspace.py:67-68), and

@@ -37,6 +37,11 @@ class TreeInfo(C.Structure):
                 ("device_time", C.c_double), ("run_time", C.c_double)]
 
 
+class TreeRfInfo(C.Structure):
+    _fields_ = [("calls", C.c_int32), ("candidates", C.c_int32), ("feasible", C.c_int32), ("improved", C.c_int32),
+                ("osqp_iter", C.c_int32), ("form", C.c_int32), ("pad0", C.c_int32), ("pad1", C.c_int32)]
+
+
 class ModelsStats(C.Structure):
     _fields_ = [("launches", C.c_int32), ("models_wave", C.c_int32), ("models_group", C.c_int32), ("pad", C.c_int32),
                 ("lds_bytes", C.c_int64), ("device_time", C.c_double), ("run_time", C.c_double)]
@@ -176,6 +181,11 @@ SYMBOLS = {
     "miosqp_qp_tree_form_large": (C.c_int, [C.c_void_p, C.c_int32]),
     "miosqp_qp_solve_trees_models_large": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), dpp, dpp, dpp, dpp, dpp, dp, dpp, ip, ip,
                                                      C.c_int32, dpp, C.POINTER(TreeInfo), C.POINTER(ModelsStats)]),
+    "miosqp_qp_solve_trees_rf": (C.c_int, [C.c_void_p, C.c_int32, dp, dp, dp, dp, dp, dp, dp, C.c_int32, C.c_int32, C.c_int32,
+                                           C.c_int32, C.c_int32, dp, C.POINTER(TreeInfo), C.POINTER(TreeRfInfo)]),
+    "miosqp_qp_solve_trees_models_rf": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), dpp, dpp, dpp, dpp, dpp, dp, dpp, ip, ip,
+                                                  C.c_int32, ip, ip, ip, dpp, C.POINTER(TreeInfo), C.POINTER(TreeRfInfo),
+                                                  C.POINTER(ModelsStats)]),
     "miosqp_qp_polish_models": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), dpp, dpp, dpp, dpp, dpp, C.c_double, dp, ip, ip, dpp,
                                           dpp, C.POINTER(C.c_void_p), C.POINTER(PolishRepairInfo), C.POINTER(PolishModelsStats)]),
     "miosqp_qp_polish_models_fits": (C.c_int, [C.c_void_p]),

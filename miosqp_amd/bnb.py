@@ -124,12 +124,13 @@ def polish_repair_setting(settings):
     return int(it)
 
 
-def one_launch_trees_ok(work):
+def one_launch_trees_ok(work, rf=False):
     """would `solve_many` (and `solve_models`) try the one-launch trees for this workspace: the entry point is there, the
-    settings are the plain search's, and the engine has not declined before"""
+    settings are the plain search's, and the engine has not declined before.  rf=True (heuristic="device"): the same
+    question with primal_heuristic 1 allowed, for the entry that runs round and fix inside the launch"""
     st, data = work.settings, work.data
     return hasattr(work.solver, 'solve_trees') and st.get('device_tree', True) and st['branching_rule'] == 0 \
-        and not work.rf['on'] \
+        and (not work.rf['on'] or (rf and hasattr(work.solver, 'solve_trees_rf'))) \
         and st['tree_explor_rule'] in (0, 1, 2, 3) and data.n_int > 0 and 'eps_abs' in work.qp_settings \
         and st.get('device_digest', True) and not getattr(work, '_no_trees', False)
 
@@ -1248,7 +1249,7 @@ class MIOSQP(object):
                 res['polished'] = True
         return results
 
-    def solve_many(self, instances, polish=False, lockstep=None, ahead=8):
+    def solve_many(self, instances, polish=False, lockstep=None, ahead=8, *, heuristic=None):
         """B MIQPs on this model's factorisation, solved TOGETHER: instance k is what
         `update_vectors(q=, l=, u=)` [+ `set_x0(x0)`] + `solve()` would solve (the reference's MPC pattern,
         /root/reference/miosqp/solver.py:174-212, examples/power_converter/power_converter.py:467-476), for a list of
@@ -1317,9 +1318,22 @@ class MIOSQP(object):
         the setting polish_incumbent, which polishes the incumbent of `solve`, stays refused here.  polish="device" is
         `polish_many(..., large=True)`: a problem beyond one workgroup (everything the lock-step driver takes) is
         polished by `OSQP.polish_many_large` in one launch instead of the host's restatement per instance.  Any other
-        value raises ValueError."""
+        value raises ValueError.
+
+        heuristic=None (the default): as above -- with primal_heuristic 1 the one-launch trees step aside.
+        heuristic="device": with primal_heuristic 1 and otherwise the one-launch trees' settings (branching_rule 0,
+        tree_explor_rule 0-3, device_tree, the device digest, an engine whose `tree_form()` is not 0) the one-launch
+        attempt is made with round and fix INSIDE every tree (`OSQP.solve_trees_rf`, miosqp_qp_solve_trees_rf): per
+        tree the decisions of its sequential solve, `Workspace.primal_heuristic` on every rf_every-th node about to
+        branch, rf_candidates capped solves by the tree's own workgroup, a winner's value being the device's sum (1e-9
+        relative, as under lockstep="device").  One workgroup per instance, also for n + M <= 64.  Trees that overflow,
+        and a decline, go on as `lockstep` says.  `work.trees_rf` holds per instance calls, candidates, feasible,
+        improved, osqp_iter as `rf_stats` defines them; the model's own `rf_stats` and `rf_nodes` are not touched.  With
+        primal_heuristic 0 the keyword changes nothing; a backend without the entry (the CPU oracle) ignores it; any
+        other value raises ValueError before any launch.  Whether it pays is measured in DESIGN 3h."""
         if not (polish is False or polish is True or (isinstance(polish, str) and polish == "device")):
             raise ValueError('solve_many: polish must be False, True or "device"')
+        _heuristic_keyword(heuristic, 'solve_many')
         work, data, st = self.work, self.work.data, self.work.settings
         require_plain_search(st, "solve_many", rule=False, heuristic=False)
         B = len(instances)
@@ -1327,6 +1341,8 @@ class MIOSQP(object):
             return []
         n, m, M = data.n, data.m, data.m + data.n_int
         ok_engine = one_launch_trees_ok(work)
+        in_launch_rf = (heuristic == "device" and bool(work.rf['on']) and one_launch_trees_ok(work, rf=True)
+                        and hasattr(work.solver, 'tree_form') and work.solver.tree_form() != 0)
         Q, L, U = self._instance_vectors(instances)
         up = np.full(B, np.inf); XI = np.zeros((B, n)); any_inc = False
         for k, inst in enumerate(instances):
@@ -1337,15 +1353,22 @@ class MIOSQP(object):
         out = [None] * B
         redo = list(range(B))
         declined = True  # the one-launch path: absent, switched off, or it returned None
-        if ok_engine:
+        if ok_engine or in_launch_rf:
             t0 = time()
-            r = work.solver.solve_trees(Q, L, U, np.zeros((B, n)), np.zeros((B, M)), up, XI if any_inc else None,
-                                        st['tree_explor_rule'], st['max_iter_bb'])
+            if in_launch_rf:
+                r = work.solver.solve_trees_rf(Q, L, U, np.zeros((B, n)), np.zeros((B, M)), up, XI if any_inc else None,
+                                               st['tree_explor_rule'], st['max_iter_bb'], work.rf['K'],
+                                               work.rf['max_iter'], work.rf['every'])
+            else:
+                r = work.solver.solve_trees(Q, L, U, np.zeros((B, n)), np.zeros((B, M)), up, XI if any_inc else None,
+                                            st['tree_explor_rule'], st['max_iter_bb'])
             if r is None:
                 work._no_trees = True
             else:
-                X, infos = r
+                X, infos = r[0], r[1]
                 work.trees_info = infos  # per instance, as work.tree_info
+                if in_launch_rf:
+                    work.trees_rf = [_rf_counters(c) for c in r[2]]
                 dt = time() - t0
                 redo = []
                 declined = False
@@ -1457,16 +1480,30 @@ class MIOSQP(object):
         self.work.set_x0(x0)
 
 
+def _rf_counters(rec):
+    """the counters of round and fix inside a one-launch tree (TreeRfInfo) as a dict with the keys of rf_stats"""
+    return dict(calls=int(rec.calls), candidates=int(rec.candidates), feasible=int(rec.feasible),
+                improved=int(rec.improved), osqp_iter=int(rec.osqp_iter))
+
+
 _BEYOND_ONE_LAUNCH = 'tree_form 0: beyond the one-launch trees'
 
 
-def _models_own_reason(work, declined_counts=True):
+def _heuristic_keyword(heuristic, who):
+    """the keyword `heuristic` of solve_many / solve_models, checked: None or "device" """
+    if heuristic is not None and not (isinstance(heuristic, str) and heuristic == "device"):
+        raise ValueError('%s: heuristic must be None or "device"' % who)
+    return heuristic
+
+
+def _models_own_reason(work, declined_counts=True, rf=False):
     """why `solve_models` leaves a model to its own `solve_many` (None: it goes into the launch); declined_counts=False
-    looks past an earlier decline of the one-launch trees (an engine beyond them declines `solve_many`'s own attempt)"""
+    looks past an earlier decline of the one-launch trees (an engine beyond them declines `solve_many`'s own attempt);
+    rf=True (heuristic="device") looks past primal_heuristic 1 on a backend that runs it inside the launch"""
     if not declined_counts and getattr(work, '_no_trees', False):
         work._no_trees = False
         try:
-            return _models_own_reason(work)
+            return _models_own_reason(work, rf=rf)
         finally:
             work._no_trees = True
     st = work.settings
@@ -1476,13 +1513,13 @@ def _models_own_reason(work, declined_counts=True):
         return 'device_tree off'
     if st['branching_rule'] != 0:
         return 'branching_rule %d' % st['branching_rule']
-    if work.rf['on']:
+    if work.rf['on'] and not (rf and hasattr(work.solver, 'solve_trees_rf')):
         return 'primal_heuristic on'
     if work.data.n_int == 0:
         return 'n_int == 0'
     if getattr(work, '_no_trees', False):
         return 'the one-launch trees declined this model before'
-    if not one_launch_trees_ok(work):
+    if not one_launch_trees_ok(work, rf=rf):
         return 'settings beyond the one-launch trees'
     try:
         require_plain_search(st, "solve_models", rule=False, heuristic=False)
@@ -1625,7 +1662,7 @@ def polish_models(models, instances, results, tau=None, repair_iter=20, guess="h
 
 
 def solve_models(models, instances=None, info=None, polish=False, polish_guess="host", large=None, leaf_cap=256,
-                 polish_large=None):
+                 polish_large=None, *, heuristic=None):
     """One MIQP on each of several DIFFERENT set-up models -- each with its own P, A, shapes and settings --, the trees
     of all of them in ONE call of the library (`qp.solve_trees_models`, miosqp_qp_solve_trees_models: at most two
     launches, workgroup or wavefront b runs model b).  It replaces the loop `models[k].solve_many([instances[k]])`: one
@@ -1671,9 +1708,20 @@ def solve_models(models, instances=None, info=None, polish=False, polish_guess="
     in one more launch (result k is then what `models[k].polish_many(.., large=True)` makes of the tree's x).  Read
     only with polish=True; any other value raises ValueError before any launch.
 
+    heuristic=None (the default): as above.  heuristic="device": a model that stays out ONLY for 'primal_heuristic on'
+    goes into the call (`qp.solve_trees_models(..., rf=...)`, miosqp_qp_solve_trees_models_rf) and runs with round and
+    fix inside its tree, in up to two more launches: the workgroup form (which takes the wave-sized models too) and,
+    with large="device", the reduced form.  Result k is then what `models[k].solve_many([instances[k]],
+    heuristic="device")[0]` returns, bit for bit in the workgroup form; a reduced-form tree is that of the CPU oracle
+    backend with the heuristic, as above.  Models with the heuristic off get what the call without the keyword gives
+    them, bit for bit.  Composes with polish=True.  A backend without the entry (the CPU oracle) ignores the keyword;
+    any other value raises ValueError before any launch.
+
     info: a dict that is filled with launched (positions), own ({position: why}), forms ({'wave': .., 'group': ..}; with
-    large="device" also 'reduced'), launches, device_time (seconds) and overflow (positions); with polish=True also what
-    `polish_models` reports."""
+    large="device" also 'reduced'; with heuristic="device" also 'group_rf' and 'reduced_rf'), launches, device_time
+    (seconds) and overflow (positions); with heuristic="device" also rf ({position: counters} of the models that ran with
+    round and fix inside the launch, keys as `rf_stats`); with polish=True also what `polish_models` reports."""
+    _heuristic_keyword(heuristic, 'solve_models')
     if not (polish is False or polish is True):
         raise ValueError('solve_models: polish must be False or True')
     if large is not None and not (isinstance(large, str) and large == "device"):
@@ -1708,20 +1756,28 @@ def solve_models(models, instances=None, info=None, polish=False, polish_guess="
     own = {}
     launched = []
     any_large = False
+    in_rf = heuristic == "device"
+    rf_par = {}  # position: (rf_candidates, rf_max_iter, rf_every) of the models that run round and fix in the launch
     for k, mdl in enumerate(models):
-        why = _models_own_reason(mdl.work)
+        look = dict(rf=True) if in_rf else {}  # (without the keyword the question is asked as it always was)
+        why = _models_own_reason(mdl.work, **look)
         if (large == "device" and why is not None and hasattr(mdl.work.solver, 'tree_form_large')
-                and _models_own_reason(mdl.work, declined_counts=False) == _BEYOND_ONE_LAUNCH
+                and _models_own_reason(mdl.work, declined_counts=False, **look) == _BEYOND_ONE_LAUNCH
                 and mdl.work.solver.tree_form_large(leaf_cap) == 3):
             why = None
             any_large = True
         if why is None:
             launched.append(k)
+            if in_rf and mdl.work.rf['on']:
+                rf_par[k] = (mdl.work.rf['K'], mdl.work.rf['max_iter'], mdl.work.rf['every'])
         else:
             own[k] = why
     out = [None] * B
     overflow = []
     forms = dict(wave=0, group=0, reduced=0) if large == "device" else dict(wave=0, group=0)
+    if in_rf:
+        forms.update(group_rf=0, reduced_rf=0)
+    rf_out = {}
     launches, device_time = 0, 0.0
     if launched:
         from miosqp_amd import qp
@@ -1735,20 +1791,30 @@ def solve_models(models, instances=None, info=None, polish=False, polish_guess="
             [np.zeros(len(vec[k][1])) for k in launched], [np.inf if inc[k] is None else inc[k][0] for k in launched],
             [None if inc[k] is None else inc[k][1] for k in launched],
             [models[k].work.settings['tree_explor_rule'] for k in launched],
-            [models[k].work.settings['max_iter_bb'] for k in launched], **(dict(leaf_cap=leaf_cap) if any_large else {}))
+            [models[k].work.settings['max_iter_bb'] for k in launched], **(dict(leaf_cap=leaf_cap) if any_large else {}),
+            **(dict(rf=[rf_par.get(k) for k in launched]) if rf_par else {}))
         dt = time() - t0
         if r is None:  # (an engine declined after all: every model on its own)
             for k in launched:
                 own[k] = 'the library declined the call'
             launched = []
         else:
-            X, infos, stats = r
+            X, infos, stats = r[:3]
             forms = dict(wave=int(stats.models_wave), group=int(stats.models_group))
             if large == "device":
                 forms['reduced'] = int(stats.pad)
+            if in_rf:
+                forms.update(group_rf=0, reduced_rf=0)
+            if rf_par:
+                for j, k in enumerate(launched):
+                    if k in rf_par:
+                        forms['reduced_rf' if r[3][j].form == 5 else 'group_rf'] += 1
+                        rf_out[k] = _rf_counters(r[3][j])
             launches, device_time = int(stats.launches), float(stats.device_time)
             for j, k in enumerate(launched):
                 models[k].work.trees_info = [infos[j]]
+                if k in rf_out:
+                    models[k].work.trees_rf = [rf_out[k]]
                 if infos[j].overflow:
                     overflow.append(k)
                     continue
@@ -1759,6 +1825,8 @@ def solve_models(models, instances=None, info=None, polish=False, polish_guess="
     if info is not None:
         info.update(launched=list(launched), own=dict(own), forms=forms, launches=launches, device_time=device_time,
                     overflow=list(overflow))
+        if in_rf:
+            info['rf'] = rf_out
     if polish:
         polish_models(models, instances, out, guess=polish_guess, info=info, large=polish_large)
     return out

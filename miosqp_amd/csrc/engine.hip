@@ -46,6 +46,7 @@
 #include "polish_models_plan.hpp"  // polishes of different models in one launch: argument checks and arena layout (plain C++; host_polish_models.inc drives it)
 #include "polish_models_large_plan.hpp"  // ... of different LARGER models: fit rule, workgroups and arena layout with the slabs (plain C++; host_polish_models_large.inc drives it)
 #include "tree_reduced_body.hpp"  // the one-launch trees' relaxation in reduced form (k_tree_r_m): LDS rule and the phases of an iteration (plain C++; also run on the CPU under tests/)
+#include "tree_rf_logic.hpp"  // round and fix inside the one-launch trees (k_tree_rf*): when it fires, the fixed value, the pick (plain C++; also run on the CPU under tests/)
 #include "models_plan.hpp"  // trees of different models in one launch: argument checks and arena layout (plain C++; host_models.inc drives it)
 #include "lockstep_refill.hpp"  // which tree goes into which free column when the columns are refilled between chunks (plain C++; host_refill.inc drives it)
 
@@ -272,7 +273,7 @@ namespace {
 // the dynamic-LDS ceiling of a kernel is a property of (process, device, kernel): raised to the chip's 160 KB once instead of
 // at every set-up (the call costs ~40 us, a fifth of a small problem's set-up)
 hipError_t lds_limit_once(const void *fn, int which) {
-  static bool done[19][64] = {};  // (one row per kernel: 0 .. 13 as before, 14: k_setup_models, 15: k_setup_models_auto, 16: k_tree_r_m, 17: k_setup_models_large, 18: k_setup_models_large_auto)
+  static bool done[22][64] = {};  // (one row per kernel: 0 .. 13 as before, 14: k_setup_models, 15: k_setup_models_auto, 16: k_tree_r_m, 17: k_setup_models_large, 18: k_setup_models_large_auto, 19: k_tree_rf, 20: k_tree_rf_m, 21: k_tree_rf_r_m)
   int dev = 0;
   hipError_t rc = hipGetDevice(&dev);
   if (rc != hipSuccess) return rc;
@@ -2105,9 +2106,12 @@ int miosqp_qp_solve_tree(miosqp_qp_engine *e, const double *l, const double *u, 
   return 0;
 }
 
-int miosqp_qp_solve_trees(miosqp_qp_engine *e, int32_t B, const double *q, const double *l, const double *u,
-                          const double *x0, const double *y0, const double *upper0, const double *x_inc0,
-                          int32_t tree_explor_rule, int32_t max_iter_bb, double *x_out, miosqp_tree_info *info) {
+// miosqp_qp_solve_trees, and with rf_info miosqp_qp_solve_trees_rf: the same staging and copies, k_tree_rf in place of
+// k_tree / k_tree_w, the counters of round and fix per instance beside the outcomes
+static int trees_run(miosqp_qp_engine *e, int32_t B, const double *q, const double *l, const double *u, const double *x0,
+                     const double *y0, const double *upper0, const double *x_inc0, int32_t tree_explor_rule,
+                     int32_t max_iter_bb, double *x_out, miosqp_tree_info *info, int32_t rf_candidates = 0,
+                     int32_t rf_max_iter = 0, int32_t rf_every = 0, miosqp_tree_rf_info *rf_info = nullptr) {
   if (!e || B < 1 || !q || !l || !u || !x0 || !y0 || !upper0 || !x_out || !info || max_iter_bb < 1 || tree_explor_rule < 0 ||
       tree_explor_rule > 3)
     return MIOSQP_EARG;
@@ -2119,7 +2123,7 @@ int miosqp_qp_solve_trees(miosqp_qp_engine *e, int32_t B, const double *q, const
   const int n = e->n, M = e->M, p = e->d.n_int;
   const size_t blk = 3 * (size_t)M + n;
   int tree_sp_off = -1;
-  const size_t lds = tree_lds_bytes(e, &tree_sp_off);
+  size_t lds = tree_lds_bytes(e, &tree_sp_off);
   if (!e->fold || lds > 160 * 1024 || p < 1) {
     g_err = "solve_trees: only for problems whose product-form factor, iterates and leaf list fit 160 KB of LDS";
     return MIOSQP_EUNSUPPORTED;
@@ -2129,10 +2133,15 @@ int miosqp_qp_solve_trees(miosqp_qp_engine *e, int32_t B, const double *q, const
   const double t0 = wall();
   bool wave = false;  // as miosqp_qp_solve_tree
   if (int rcw = tree_wave_prepare(e, &wave)) return rcw;
-  if (!wave) HIPCHK(lds_limit_once((const void *)k_tree, 1));
+  if (rf_info) {  // (k_tree_rf also runs the wave-sized engines: sized for the engine as tree_wave_prepare left it)
+    lds = tree_lds_bytes(e, &tree_sp_off);
+    HIPCHK(lds_limit_once((const void *)k_tree_rf, 19));
+  } else if (!wave) {
+    HIPCHK(lds_limit_once((const void *)k_tree, 1));
+  }
   if (B > e->tb_cap) {  // (a larger batch takes new arrays; the old ones stay with the pool until cleanup)
     const size_t cap = (size_t)std::max(B, 2 * e->tb_cap);
-    int rc = pool_reserve(e, cap * ((size_t)TREE_CAP * (2 * (size_t)p + n + M) + blk + 3 * (size_t)n + 16) * sizeof(double) + 4096);
+    int rc = pool_reserve(e, cap * ((size_t)TREE_CAP * (2 * (size_t)p + n + M) + blk + 3 * (size_t)n + 20) * sizeof(double) + 4096);
     if (!rc) rc = dalloc(e, &e->tb_q, cap * n);
     if (!rc) rc = dalloc(e, &e->tb_qraw, cap * n);
     if (!rc) rc = dalloc(e, &e->tb_raw, cap * blk);
@@ -2143,6 +2152,7 @@ int miosqp_qp_solve_trees(miosqp_qp_engine *e, int32_t B, const double *q, const
     if (!rc) rc = dalloc(e, &e->tb_inc, cap * n);
     if (!rc) rc = dalloc(e, &e->tb_upper, cap);
     if (!rc) rc = dalloc(e, &e->tb_out, cap);
+    if (!rc) rc = dalloc(e, &e->tb_rf, cap);
     if (rc) return rc;
     e->tb_cap = (int)cap;
   }
@@ -2185,6 +2195,12 @@ int miosqp_qp_solve_trees(miosqp_qp_engine *e, int32_t B, const double *q, const
   ta.sp_off = tree_sp_off;
   ta.batch = 1;
   ta.upper_b = e->tb_upper;
+  if (rf_info) {
+    ta.rf_K = rf_candidates;
+    ta.rf_max_iter = rf_max_iter;
+    ta.rf_every = rf_every;
+    ta.rf_out = e->tb_rf;
+  }
   Dev db = e->d;  // instance 0's arrays; workgroup b moves on from there (tree_instance)
   db.q = e->tb_q;
   db.qraw = e->tb_qraw;
@@ -2193,10 +2209,16 @@ int miosqp_qp_solve_trees(miosqp_qp_engine *e, int32_t B, const double *q, const
   db.raw_x = e->tb_raw + 2 * (size_t)M;
   db.raw_y = e->tb_raw + 2 * (size_t)M + n;
   db.prof = nullptr;
-  if (wave) hipLaunchKernelGGL(k_tree_w, dim3(B), dim3(TW), 0, e->stream, db, ta);
+  // (with round and fix the workgroup form also takes the wave-sized models: tree_lds_bytes sized it for the engine as it stands)
+  if (rf_info) hipLaunchKernelGGL(k_tree_rf, dim3(B), dim3(RES_THREADS), lds, e->stream, db, ta);
+  else if (wave) hipLaunchKernelGGL(k_tree_w, dim3(B), dim3(TW), 0, e->stream, db, ta);
   else hipLaunchKernelGGL(k_tree, dim3(B), dim3(RES_THREADS), lds, e->stream, db, ta);
   if (e->tb_hout.size() < (size_t)B) e->tb_hout.resize(B);
   HIPCHK(hipMemcpyAsync(e->tb_hout.data(), e->tb_out, sizeof(TreeOut) * B, hipMemcpyDeviceToHost, e->stream));
+  if (rf_info) {
+    if (e->tb_hrf.size() < (size_t)B) e->tb_hrf.resize(B);
+    HIPCHK(hipMemcpyAsync(e->tb_hrf.data(), e->tb_rf, sizeof(TreeRfOut) * B, hipMemcpyDeviceToHost, e->stream));
+  }
   HIPCHK(hipMemcpyAsync(h_inc, e->tb_inc, sizeof(double) * (size_t)B * n, hipMemcpyDeviceToHost, e->stream));
   HIPCHK(hipEventRecord(e->ev1, e->stream));
   HIPCHK(hipStreamSynchronize(e->stream));
@@ -2220,10 +2242,33 @@ int miosqp_qp_solve_trees(miosqp_qp_engine *e, int32_t B, const double *q, const
     if (o.found) memcpy(x_out + (size_t)b * n, h_inc + (size_t)b * n, sizeof(double) * n);
     else if (have) memcpy(x_out + (size_t)b * n, x_inc0 + (size_t)b * n, sizeof(double) * n);
     iters += o.osqp_iter;
+    if (rf_info) {
+      const TreeRfOut &r = e->tb_hrf[b];
+      rf_info[b] = miosqp_tree_rf_info{r.calls, r.candidates, r.feasible, r.improved, r.osqp_iter, 4, 0, 0};
+    }
   }
   e->loop_ms += ms;
   e->loop_iters += iters;
   return 0;
+}
+
+int miosqp_qp_solve_trees(miosqp_qp_engine *e, int32_t B, const double *q, const double *l, const double *u,
+                          const double *x0, const double *y0, const double *upper0, const double *x_inc0,
+                          int32_t tree_explor_rule, int32_t max_iter_bb, double *x_out, miosqp_tree_info *info) {
+  return trees_run(e, B, q, l, u, x0, y0, upper0, x_inc0, tree_explor_rule, max_iter_bb, x_out, info);
+}
+
+int miosqp_qp_solve_trees_rf(miosqp_qp_engine *e, int32_t B, const double *q, const double *l, const double *u,
+                             const double *x0, const double *y0, const double *upper0, const double *x_inc0,
+                             int32_t tree_explor_rule, int32_t max_iter_bb, int32_t rf_candidates, int32_t rf_max_iter,
+                             int32_t rf_every, double *x_out, miosqp_tree_info *info, miosqp_tree_rf_info *rf_info) {
+  std::string err;
+  if (int rc = miosqp::models::check_rf(1, &rf_candidates, &rf_max_iter, &rf_every, rf_info, 1, "solve_trees_rf", err)) {
+    g_err = err;
+    return rc;
+  }
+  return trees_run(e, B, q, l, u, x0, y0, upper0, x_inc0, tree_explor_rule, max_iter_bb, x_out, info, rf_candidates, rf_max_iter,
+                   rf_every, rf_info);
 }
 
 int miosqp_qp_tree_form(miosqp_qp_engine *e) {
@@ -2254,6 +2299,16 @@ int miosqp_qp_solve_trees_models_large(int32_t B, miosqp_qp_engine *const *engin
                                        const int32_t *max_iter_bb, int32_t leaf_cap, double *const *x_out,
                                        miosqp_tree_info *info, miosqp_models_stats *stats) {
   return models_run(B, engines, q, l, u, x0, y0, upper0, x_inc0, tree_explor_rule, max_iter_bb, x_out, info, stats, true, leaf_cap);
+}
+
+int miosqp_qp_solve_trees_models_rf(int32_t B, miosqp_qp_engine *const *engines, const double *const *q, const double *const *l,
+                                    const double *const *u, const double *const *x0, const double *const *y0,
+                                    const double *upper0, const double *const *x_inc0, const int32_t *tree_explor_rule,
+                                    const int32_t *max_iter_bb, int32_t leaf_cap, const int32_t *rf_candidates,
+                                    const int32_t *rf_max_iter, const int32_t *rf_every, double *const *x_out,
+                                    miosqp_tree_info *info, miosqp_tree_rf_info *rf_info, miosqp_models_stats *stats) {
+  return models_run(B, engines, q, l, u, x0, y0, upper0, x_inc0, tree_explor_rule, max_iter_bb, x_out, info, stats, leaf_cap != 0,
+                    leaf_cap, true, rf_candidates, rf_max_iter, rf_every, rf_info);
 }
 
 int miosqp_qp_debug_iterate(miosqp_qp_engine *e, int32_t k, double *x, double *z, double *y) {

@@ -68,8 +68,10 @@ struct miosqp_qp_engine {
   double *tb_q = nullptr, *tb_qraw = nullptr, *tb_raw = nullptr, *tb_lo = nullptr, *tb_hi = nullptr, *tb_x = nullptr, *tb_y = nullptr,
          *tb_inc = nullptr, *tb_upper = nullptr;
   TreeOut *tb_out = nullptr;
+  TreeRfOut *tb_rf = nullptr;  // miosqp_qp_solve_trees_rf: the counters of round and fix, per instance
   std::vector<double> tb_host;   // staging: [raw block | inc | upper] in, [inc] out
   std::vector<TreeOut> tb_hout;
+  std::vector<TreeRfOut> tb_hrf;
   // miosqp_qp_solve_trees_models with this engine first: the call's arena (from this engine's pool) and the pinned mirror
   // of its staged part, capacities in doubles
   double *mm_dev = nullptr, *mm_host = nullptr;

@@ -18,6 +18,12 @@ struct TreeOut {
   double upper, lower_glob;
 };
 
+// what rf_stats counts, for one tree with round and fix inside (Workspace.primal_heuristic)
+struct TreeRfOut {
+  int calls, candidates, feasible, improved;
+  int osqp_iter, pad0, pad1, pad2;
+};
+
 struct TreeArgs {
   int rule, max_nodes, max_iter, check_every, TG1, TG2;
   double upper0;
@@ -37,6 +43,10 @@ struct TreeArgs {
   // offset (doubles) of the LDS copy of Abar^T's packed rows, or -1 -- it is there exactly when sp_off is; and which rows of
   // Abar the iteration reads where no LDS copy is: 1 the dense copies (f_Atd, f_Ad), 0 the packed panels (pv_At, pc_A)
   int leaf_cap, pv_off, r_dense;
+  // k_tree_rf, k_tree_rf_m, k_tree_rf_r_m (round and fix inside the tree, kernels_tree_rf_block.inc): candidates per call
+  // (0: never fires), their iteration cap, every how many branching nodes; the tree's counters (per instance in a batch)
+  int rf_K, rf_max_iter, rf_every;
+  TreeRfOut *rf_out;
 };
 
 // workgroup b of a batched launch: the per-instance pointers of Dev and TreeArgs moved to instance b (the staging block
@@ -59,6 +69,12 @@ __device__ __forceinline__ void tree_instance(Dev &d, TreeArgs &ta) {
   ta.inc_x += b * n;
   ta.out += b;
   ta.upper0 = ta.upper_b[b];
+}
+
+// ... and the instance's round-and-fix counters (k_tree_rf)
+__device__ __forceinline__ void tree_instance_rf(Dev &d, TreeArgs &ta) {
+  if (ta.batch) ta.rf_out += blockIdx.x;
+  tree_instance(d, ta);
 }
 
 __host__ __device__ inline size_t tree_lds_doubles(int n, int M, bool wform) {
@@ -141,6 +157,28 @@ __global__ __launch_bounds__(RES_THREADS) void k_tree_m(const TreeModel *__restr
   const TreeArgs &ta = tab[blockIdx.x].ta;
 #include "kernels_tree_body.inc"  // the body of k_tree
 }
+
+// ------------------------------------------------------------------------------------------
+// The same trees with ROUND AND FIX inside (primal_heuristic 1; miosqp_qp_solve_trees_rf, miosqp_qp_solve_trees_models_rf):
+// the body under TREE_RF -- on every rf_every-th node that is about to branch the workgroup solves rf_K rounded-and-fixed
+// copies of the node, capped at rf_max_iter iterations, and adopts the best one that beats the incumbent
+// (kernels_tree_rf_block.inc, tree_rf_logic.hpp).  No LDS beyond k_tree's: the node's xf, yf wait in its place of the
+// leaf store.  Sizes n + M <= 64 run here as well (the workgroup form takes them; there is no wavefront form).
+// ------------------------------------------------------------------------------------------
+#define TREE_RF 1
+__global__ __launch_bounds__(RES_THREADS) void k_tree_rf(Dev d, TreeArgs ta) {
+  extern __shared__ __attribute__((aligned(16))) double sm[];
+  tree_instance_rf(d, ta);
+#include "kernels_tree_body.inc"  // the body of k_tree, with round and fix
+}
+
+__global__ __launch_bounds__(RES_THREADS) void k_tree_rf_m(const TreeModel *__restrict__ tab) {
+  extern __shared__ __attribute__((aligned(16))) double sm[];
+  const Dev &d = tab[blockIdx.x].d;
+  const TreeArgs &ta = tab[blockIdx.x].ta;
+#include "kernels_tree_body.inc"  // the body of k_tree, with round and fix
+}
+#undef TREE_RF
 #undef TREE_LIST_CAP
 
 // ------------------------------------------------------------------------------------------
@@ -236,6 +274,16 @@ __global__ __launch_bounds__(RES_THREADS) void k_tree_r_m(const TreeModel *__res
   const TreeArgs &ta = tab[blockIdx.x].ta;
 #include "kernels_tree_body.inc"  // the body of k_tree, with the three pieces of the reduced form
 }
+
+// ... with round and fix inside (see k_tree_rf)
+#define TREE_RF 1
+__global__ __launch_bounds__(RES_THREADS) void k_tree_rf_r_m(const TreeModel *__restrict__ tab) {
+  extern __shared__ __attribute__((aligned(16))) double sm[];
+  const Dev &d = tab[blockIdx.x].d;
+  const TreeArgs &ta = tab[blockIdx.x].ta;
+#include "kernels_tree_body.inc"  // the body of k_tree_r_m, with round and fix
+}
+#undef TREE_RF
 #undef TREE_REDUCED
 #undef TREE_LIST_CAP
 

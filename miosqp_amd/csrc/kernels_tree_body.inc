@@ -1,6 +1,7 @@
-// part of kernels_tree.inc (included there INSIDE k_tree, k_tree_m and k_tree_r_m, nowhere else): the one body of the
-// kernels.  TREE_LIST_CAP: the leaf list's capacity; TREE_REDUCED (k_tree_r_m): the carve-up, the factor load and the call
-// that runs the relaxation are those of the reduced form -- nothing else differs.
+// part of kernels_tree.inc (included there INSIDE k_tree, k_tree_m, k_tree_r_m and their forms with round and fix, nowhere
+// else): the one body of the kernels.  TREE_LIST_CAP: the leaf list's capacity; TREE_REDUCED (k_tree_r_m): the carve-up, the factor load and the call
+// that runs the relaxation are those of the reduced form -- nothing else differs.  TREE_RF (k_tree_rf, k_tree_rf_m,
+// k_tree_rf_r_m): round and fix on the nodes that are about to branch (kernels_tree_rf_block.inc) -- nothing else differs.
 // In scope: `sm` (the dynamic LDS block), `d` (Dev) and `ta` (TreeArgs) with final pointers -- kernel arguments moved to
 // the block's instance (k_tree), or references to the block's entry of a table in device memory (k_tree_m).  Everything
 // per block -- shapes, the LDS carve-up, sp_off, lane groupings, search settings, tolerances -- is read from them.
@@ -36,6 +37,7 @@
   int *iiL = reinterpret_cast<int *>(sm + cv.iiL);
 #endif
   // sc[0] upper, sc[1] action, sc[2] slot, sc[3] status, sc[4] lower, sc[5] heur_obj, sc[6] nextvar, sc[7] child0, sc[8] child1
+  // (TREE_RF: sc[15] the candidate just judged is the best so far)
   const double rinv = d.rho_inv, sigma = d.sigma;
   const int unsolved = MIOSQP_QP_UNSOLVED;
   (void)unsolved;
@@ -70,6 +72,9 @@
   for (int j = tid; j < M; j += RES_THREADS) ta.lf_y[j] = d.raw_y[j];
   int count = 1, nfree = TREE_LIST_CAP - 1, nodes = 0, osqp_iter = 0, max_leaves = 1, overflow = 0, found = 0;
   double lower_glob = -1.0 / 0.0;
+#ifdef TREE_RF  // round and fix (kernels_tree_rf_block.inc): nodes that were about to branch, and what rf_stats counts
+  int rf_nodes = 0, rf_calls = 0, rf_cand = 0, rf_feas = 0, rf_impr = 0, rf_iter = 0;
+#endif
   if (tid == 0) {
     order[0] = 0;
     lf_depth[0] = 0;
@@ -290,6 +295,21 @@
         }
         found = 1;
       }
+#ifdef TREE_RF
+      // Workspace.primal_heuristic sits here, between the node's own pruning and its branching: thread 0's block is
+      // closed around it (the whole workgroup solves the candidates) and opened again with its values
+      sc[0] = upper;
+      sc[1] = (double)action;
+      sc[4] = lower;
+      sc[6] = (double)nextvar;
+    }
+#include "kernels_tree_rf_block.inc"
+    if (tid == 0) {
+      double upper = sc[0];
+      const int action = (int)sc[1] & 4;  // (the block has written the node's own incumbent)
+      const double lower = sc[4];
+      const int nextvar = (int)sc[6];
+#endif
       int c0 = -1, c1 = -1;
       if (action & 4) {
         if (nfree < 2 || count + 2 > TREE_LIST_CAP) {
@@ -368,4 +388,12 @@
     o->found = found;
     o->upper = sc[0];
     o->lower_glob = lower_glob;
+#ifdef TREE_RF
+    TreeRfOut *r = ta.rf_out;
+    r->calls = rf_calls;
+    r->candidates = rf_cand;
+    r->feasible = rf_feas;
+    r->improved = rf_impr;
+    r->osqp_iter = rf_iter;
+#endif
   }

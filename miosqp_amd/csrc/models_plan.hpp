@@ -62,8 +62,40 @@ inline int check_args(int32_t B, const void *const *engines, const int *M, const
 
 struct Shape {
   int n, M, p;  // variables, rows (general + integer), integer variables
-  int form;     // 1: one wavefront, 2: one workgroup, 3: one workgroup in reduced form (miosqp_qp_solve_trees_models_large)
+  int form;     // 1: one wavefront, 2: one workgroup, 3: one workgroup in reduced form (miosqp_qp_solve_trees_models_large);
+                // with round and fix inside (miosqp_qp_solve_trees_models_rf) 4: one workgroup, 5: the reduced form
 };
+
+constexpr size_t RF_DOUBLES = 4;  // room of one round-and-fix record (TreeRfOut: 32 bytes)
+
+inline bool reduced_form(int form) { return form == 3 || form == 5; }
+
+// what miosqp_qp_solve_trees_models_rf checks beyond check_args: per model the candidates per call (0: the heuristic is
+// off for that model), their iteration cap and every how many branching nodes.  K_min: 0 there, 1 for
+// miosqp_qp_solve_trees_rf (one model, `who` names the entry).
+inline int check_rf(int32_t B, const int32_t *rf_candidates, const int32_t *rf_max_iter, const int32_t *rf_every,
+                    const void *rf_info, int K_min, const std::string &who, std::string &err) {
+  if (!rf_candidates || !rf_max_iter || !rf_every || !rf_info) {
+    err = who + ": a NULL argument";
+    return ERR_ARG;
+  }
+  for (int b = 0; b < B; b++) {
+    const std::string of = " of model " + std::to_string(b);
+    if (rf_candidates[b] < K_min || rf_candidates[b] > 32) {
+      err = who + ": rf_candidates " + std::to_string(rf_candidates[b]) + of + " is outside " + std::to_string(K_min) + "..32";
+      return ERR_ARG;
+    }
+    if (rf_max_iter[b] < 1) {
+      err = who + ": rf_max_iter" + of + " must be at least 1";
+      return ERR_ARG;
+    }
+    if (rf_every[b] < 1) {
+      err = who + ": rf_every" + of + " must be at least 1";
+      return ERR_ARG;
+    }
+  }
+  return 0;
+}
 
 // what miosqp_qp_solve_trees_models_large checks beyond check_args: the leaf list of the reduced form needs room for the
 // two children of the root's branching
@@ -80,6 +112,7 @@ struct Slot {
   int entry;
   size_t raw, qraw;  // l | u | x0 | y0 (3 M + n), the raw cost (n): uploaded
   size_t inc, out;   // incumbent (n), outcome (OUT_DOUBLES): uploaded and downloaded
+  size_t rf;         // the round-and-fix record (rf_doubles, behind the outcome; 0 without one): uploaded and downloaded
   size_t q;          // the scaled cost (n)
   size_t lf_lo, lf_hi, lf_x, lf_y;  // the leaf store: cap x p, cap x p, cap x n, cap x M
 };
@@ -87,11 +120,13 @@ struct Slot {
 // [ table | raw, qraw of every model | inc, out of every model | q and leaf store of every model ]: the first three parts
 // go up in ONE copy, the third comes back in ONE copy.  The table holds the one-wavefront models first (the launch over
 // them reads entries [0, n1)), then the workgroup models (entries [n1, n1 + n2)), then the models of the reduced form
-// (entries [n1 + n2, n1 + n2 + n3)), each group in the caller's order.  The leaf store of a model has `tree_cap` places,
-// that of a reduced-form model `leaf_cap_r`.
+// (entries [n1 + n2, n1 + n2 + n3)), then the two groups with round and fix inside -- workgroup (n4 entries), reduced form
+// (n5 entries) --, each group in the caller's order.  The leaf store of a model has `tree_cap` places, that of a
+// reduced-form model `leaf_cap_r`.  rf_doubles > 0 (miosqp_qp_solve_trees_models_rf): every model's outcome is followed by
+// a round-and-fix record of that many doubles; with 0, and no model of form 4 or 5, the layout is what it was without them.
 struct Plan {
   std::vector<Slot> slot;
-  int n1 = 0, n2 = 0, n3 = 0;
+  int n1 = 0, n2 = 0, n3 = 0, n4 = 0, n5 = 0;
   size_t table_doubles = 0;
   size_t up_doubles = 0;               // what the host stages and uploads: [0, up_doubles)
   size_t down_off = 0, down_doubles = 0;  // what comes back
@@ -100,13 +135,14 @@ struct Plan {
 
 inline size_t round_up(size_t v, size_t to) { return (v + to - 1) / to * to; }
 
-inline Plan plan(const std::vector<Shape> &sh, size_t entry_bytes, size_t tree_cap, size_t leaf_cap_r = 0) {
+inline Plan plan(const std::vector<Shape> &sh, size_t entry_bytes, size_t tree_cap, size_t leaf_cap_r = 0, size_t rf_doubles = 0) {
   Plan P;
   const size_t B = sh.size();
   P.slot.resize(B);
-  for (const Shape &s : sh) (s.form == 1 ? P.n1 : s.form == 3 ? P.n3 : P.n2)++;
-  int k1 = 0, k2 = P.n1, k3 = P.n1 + P.n2;
-  for (size_t b = 0; b < B; b++) P.slot[b].entry = sh[b].form == 1 ? k1++ : sh[b].form == 3 ? k3++ : k2++;
+  for (const Shape &s : sh) (s.form == 1 ? P.n1 : s.form == 3 ? P.n3 : s.form == 4 ? P.n4 : s.form == 5 ? P.n5 : P.n2)++;
+  int k1 = 0, k2 = P.n1, k3 = P.n1 + P.n2, k4 = k3 + P.n3, k5 = k4 + P.n4;
+  for (size_t b = 0; b < B; b++)
+    P.slot[b].entry = sh[b].form == 1 ? k1++ : sh[b].form == 3 ? k3++ : sh[b].form == 4 ? k4++ : sh[b].form == 5 ? k5++ : k2++;
   P.table_doubles = round_up((B * entry_bytes + 7) / 8, 32);
   size_t at = P.table_doubles;
   for (size_t b = 0; b < B; b++) {
@@ -123,13 +159,15 @@ inline Plan plan(const std::vector<Shape> &sh, size_t entry_bytes, size_t tree_c
     at += (size_t)sh[b].n;
     P.slot[b].out = at;
     at += OUT_DOUBLES;
+    P.slot[b].rf = rf_doubles ? at : 0;
+    at += rf_doubles;
   }
   P.down_doubles = at - P.down_off;
   P.up_doubles = at;
   at = round_up(at, 32);
   for (size_t b = 0; b < B; b++) {
     const size_t n = (size_t)sh[b].n, M = (size_t)sh[b].M, p = (size_t)sh[b].p;
-    const size_t cap = sh[b].form == 3 ? leaf_cap_r : tree_cap;
+    const size_t cap = reduced_form(sh[b].form) ? leaf_cap_r : tree_cap;
     P.slot[b].q = at;
     at += round_up(n, 2);
     P.slot[b].lf_lo = at;
@@ -152,7 +190,7 @@ inline int check_arena(const Plan &P, const std::vector<Shape> &sh, size_t tree_
   if (P.total_doubles <= limit_doubles) return 0;
   size_t b = 0;
   for (; b + 1 < sh.size(); b++) {
-    const size_t cap = sh[b].form == 3 ? leaf_cap_r : tree_cap;
+    const size_t cap = reduced_form(sh[b].form) ? leaf_cap_r : tree_cap;
     if (P.slot[b].lf_y + cap * (size_t)sh[b].M > limit_doubles) break;
   }
   err = "solve_trees_models_large: the arena of the call (" + std::to_string(P.total_doubles * sizeof(double)) +

@@ -79,7 +79,7 @@ def _f64(a, size, name):
     return a
 
 
-def solve_trees_models(solvers, q, l, u, x0, y0, upper0, x_inc0, rules, max_iter_bb, leaf_cap=None):
+def solve_trees_models(solvers, q, l, u, x0, y0, upper0, x_inc0, rules, max_iter_bb, leaf_cap=None, rf=None):
     """One MIQP on each of B DIFFERENT engines, every tree in one launch per kernel form (miosqp_qp_solve_trees_models):
     model b is what `solvers[b].solve_trees(q[b][None], ...)` solves, bit for bit.  Lists of per-model arrays (q, x0: n_b;
     l, u, y0: M_b), upper0: B incumbent values (inf: none), x_inc0: per model an array or None, rules / max_iter_bb: per
@@ -90,8 +90,18 @@ def solve_trees_models(solvers, q, l, u, x0, y0, upper0, x_inc0, rules, max_iter
     leaf_cap (None: the call above, exactly): an int >= 2 sends the call to miosqp_qp_solve_trees_models_large, which also
     takes engines whose `tree_form_large(leaf_cap)` is 3 -- the reduced form for models beyond one workgroup's product
     form, with a leaf list of leaf_cap places -- in a third launch; stats.pad then counts them.  Engines of forms 1 and 2
-    get what the call without leaf_cap gives them, bit for bit."""
+    get what the call without leaf_cap gives them, bit for bit.
+
+    rf (None: the calls above, exactly): one entry per model, None (round and fix off for that model: it goes into the
+    launch it goes into without `rf`, with that result bit for bit) or (rf_candidates 1..32, rf_max_iter >= 1,
+    rf_every >= 1) -- the call goes to miosqp_qp_solve_trees_models_rf, where such a model runs with
+    `Workspace.primal_heuristic` inside its tree, as `solvers[b].solve_trees_rf(q[b][None], ...)` runs it, in up to two
+    more launches (the workgroup form, which takes the wave-sized models too, and with leaf_cap the reduced form).
+    Returns ([x_b], [TreeInfo], stats, [TreeRfInfo]): per model calls, candidates, feasible, improved, osqp_iter and form
+    (1 wave, 2 group, 3 reduced, 4 group with round and fix, 5 reduced with it)."""
     B = len(solvers)
+    if rf is not None and len(rf) != B:
+        raise ValueError("solve_trees_models: one entry per model in every list")
     if leaf_cap is not None and int(leaf_cap) < 2:
         raise ValueError("solve_trees_models: leaf_cap must be at least 2")
     if not (len(q) == len(l) == len(u) == len(x0) == len(y0) == len(upper0) == len(x_inc0) == len(rules) == len(max_iter_bb) == B):
@@ -118,7 +128,16 @@ def solve_trees_models(solvers, q, l, u, x0, y0, upper0, x_inc0, rules, max_iter
     infos = (_lib.TreeInfo * max(B, 1))()
     stats = _lib.ModelsStats()
     hs = (C.c_void_p * max(B, 1))(*[s._h.value for s in solvers])
-    if leaf_cap is None:
+    rfs = None
+    if rf is not None:
+        par = np.array([(0, 1, 1) if r is None else tuple(int(v) for v in r) for r in rf], dtype=np.int32).reshape(B, 3)
+        rk, ri, re = (np.ascontiguousarray(par[:, c]) for c in range(3))
+        rfs = (_lib.TreeRfInfo * max(B, 1))()
+        rc = lib.miosqp_qp_solve_trees_models_rf(B, hs, ptrs(q), ptrs(l), ptrs(u), ptrs(x0), ptrs(y0), _lib.as_d(up), ptrs(xin),
+                                                 _lib.as_i(rl), _lib.as_i(mi), 0 if leaf_cap is None else int(leaf_cap),
+                                                 _lib.as_i(rk), _lib.as_i(ri), _lib.as_i(re), ptrs(x), infos, rfs,
+                                                 C.byref(stats))
+    elif leaf_cap is None:
         rc = lib.miosqp_qp_solve_trees_models(B, hs, ptrs(q), ptrs(l), ptrs(u), ptrs(x0), ptrs(y0), _lib.as_d(up), ptrs(xin),
                                               _lib.as_i(rl), _lib.as_i(mi), ptrs(x), infos, C.byref(stats))
     else:
@@ -130,6 +149,8 @@ def solve_trees_models(solvers, q, l, u, x0, y0, upper0, x_inc0, rules, max_iter
     _check(rc, "solve_trees_models")
     if rc == 1:
         raise ValueError("Lower bound must be lower than or equal to upper bound (%s)" % _lib.last_error())
+    if rfs is not None:
+        return x, list(infos)[:B], stats, list(rfs)[:B]
     return x, list(infos)[:B], stats
 
 
@@ -700,6 +721,38 @@ class OSQP(object):
         if rc == 1:
             raise ValueError("Lower bound must be lower than or equal to upper bound")
         return x, list(infos)
+
+    def solve_trees_rf(self, q, l, u, x0, y0, upper0, x_inc0, tree_explor_rule, max_iter_bb, rf_candidates, rf_max_iter,
+                       rf_every):
+        """`solve_trees` with round and fix inside every tree (miosqp_qp_solve_trees_rf, `Workspace.primal_heuristic`):
+        on every rf_every-th node a tree is about to branch (the first included) its workgroup solves rf_candidates
+        rounded-and-fixed copies of the node, at most rf_max_iter iterations each, and adopts the best feasible one below
+        the incumbent.  One workgroup per instance, also for n + M <= 64.  rf_candidates in 1..32, rf_max_iter >= 1,
+        rf_every >= 1 (RuntimeError with the library's text otherwise).  Returns (x B x n, [TreeInfo], [TreeRfInfo]) --
+        TreeInfo.osqp_iter counts the nodes' iterations, TreeRfInfo has calls, candidates, feasible, improved, osqp_iter
+        per instance -- or None when the engine does not cover this size."""
+        q = np.ascontiguousarray(q, dtype=np.float64)
+        B = q.shape[0]
+        l, u = np.ascontiguousarray(l, dtype=np.float64), np.ascontiguousarray(u, dtype=np.float64)
+        x0, y0 = np.ascontiguousarray(x0, dtype=np.float64), np.ascontiguousarray(y0, dtype=np.float64)
+        if q.shape != (B, self.n) or x0.shape != (B, self.n) or l.shape != (B, self.m) or u.shape != (B, self.m) or y0.shape != (B, self.m):
+            raise ValueError("solve_trees_rf: instance-major arrays (B x n, B x M)")
+        up = np.minimum(np.ascontiguousarray(upper0, dtype=np.float64).reshape(B), 1.7e308)
+        xin = None if x_inc0 is None else np.ascontiguousarray(x_inc0, dtype=np.float64).reshape(B, self.n)
+        x = np.zeros((B, self.n))
+        infos = (_lib.TreeInfo * B)()
+        rfs = (_lib.TreeRfInfo * B)()
+        max_iter_bb = 2 ** 31 - 1 if not np.isfinite(max_iter_bb) else int(min(int(max_iter_bb), 2 ** 31 - 1))
+        rc = self._lib.miosqp_qp_solve_trees_rf(self._h, B, _lib.as_d(q), _lib.as_d(l), _lib.as_d(u), _lib.as_d(x0),
+                                                _lib.as_d(y0), _lib.as_d(up), None if xin is None else _lib.as_d(xin),
+                                                int(tree_explor_rule), max_iter_bb, int(rf_candidates), int(rf_max_iter),
+                                                int(rf_every), _lib.as_d(x), infos, rfs)
+        if rc == -5:
+            return None
+        _check(rc, "solve_trees_rf")
+        if rc == 1:
+            raise ValueError("Lower bound must be lower than or equal to upper bound")
+        return x, list(infos), list(rfs)
 
     def tree_form(self):
         """Which one-launch tree kernel takes this engine (miosqp_qp_tree_form): 0 none -- `solve_trees` would return
