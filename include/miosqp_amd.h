@@ -519,6 +519,58 @@ int miosqp_qp_solve_trees_models_rf(int32_t B, miosqp_qp_engine *const *engines,
                                     const int32_t *rf_max_iter, const int32_t *rf_every, double *const *x_out,
                                     miosqp_tree_info *info, miosqp_tree_rf_info *rf_info, miosqp_models_stats *stats);
 
+/* ---- ... with strong or reliability branching inside the one-launch trees (opt-in) ----------------------
+ * The branching rules 1 and 2 of Workspace.select_branching (miosqp_amd/bnb.py) inside the tree launch: a node that is
+ * about to branch builds its fractional set with eps_int_feas and, as candidates, the sb_candidates positions of largest
+ * |x - rint(x)| (ties to the lower position, ascending) -- under rule 2 among the positions with fewer than
+ * sb_reliability observations in one direction only.  Its workgroup then solves the 2K children, K down and then K up,
+ * one after the other: the node with ONE integer row changed (down: u = floor(x_c), up: l = ceil(x_c)), warm-started
+ * from the node, at most sb_max_iter iterations, the node's termination test; a child with an x (solved or at its cap)
+ * has the objective of its clamped x as its value.  Scores are max(gain, sb_eps) * max(gain, sb_eps) with a gain of
+ * 1e30 for a child without a value, the first maximum wins.  Rule 1 branches on that candidate (one fractional position:
+ * nothing is solved).  Rule 2 keeps pseudo-costs PER TREE, starting empty: the children's gains are recorded in
+ * candidate order, down then up; a node made by a branching records its own solve's gain when it has an x, before it is
+ * judged; the position is the first maximum over ALL fractional positions, scored by strong branching where solved and
+ * by pseudo-costs (numpy's pairwise mean for positions without observations) otherwise.  The semantics are those of
+ * miosqp_qp_strong_branch and miosqp_qp_solve_trees_lockstep_sb; the kernels are k_tree_sb, k_tree_sb_m and
+ * k_tree_sb_r_m (miosqp_amd/csrc/kernels_tree.inc), which need no LDS beyond their plain forms: every engine those take
+ * is taken.  There is no one-wavefront form with a rule: n + M <= 64 runs in the workgroup form.  info->osqp_iter counts
+ * the nodes' iterations only; the children's are in the record below. */
+typedef struct miosqp_tree_sb_info {
+  int32_t calls;      /* strong-branching calls (what sb_stats['calls'] counts) */
+  int32_t children;   /* children solved: 2 x candidates per call */
+  int32_t osqp_iter;  /* ADMM iterations of all children */
+  int32_t form;       /* the launch that ran the tree: 1 wave, 2 group, 3 reduced, 6 group with the rule, 7 reduced with it */
+  int32_t pad0, pad1, pad2, pad3;
+} miosqp_tree_sb_info;
+
+/* miosqp_qp_solve_trees with the rule in every tree (Workspace.select_branching): branching_rule 1 or 2, sb_candidates in
+ * 1..32, sb_max_iter >= 1, sb_reliability >= 0, sb_eps > 0 (MIOSQP_EARG otherwise, before anything is queued); sb_info B
+ * records, per instance. */
+int miosqp_qp_solve_trees_sb(miosqp_qp_engine *e, int32_t B, const double *q, const double *l, const double *u,
+                             const double *x0, const double *y0, const double *upper0, const double *x_inc0,
+                             int32_t tree_explor_rule, int32_t max_iter_bb, int32_t branching_rule, int32_t sb_candidates,
+                             int32_t sb_max_iter, int32_t sb_reliability, double sb_eps, double *x_out, miosqp_tree_info *info,
+                             miosqp_tree_sb_info *sb_info);
+
+/* miosqp_qp_solve_trees_models_large with the rule per model (Workspace.select_branching): branching_rule[b] in 0..2 --
+ * 0: "none", model b branches on the most fractional position, goes into the launch it goes into without this entry
+ * and gets that result bit for bit (its other four values are not read) --, else sb_candidates[b] in 1..32,
+ * sb_max_iter[b] >= 1, sb_reliability[b] >= 0, sb_eps[b] > 0 (MIOSQP_EARG naming the model otherwise, before anything is
+ * queued).  The models with a rule form up to two more launches behind the others: the workgroup form (forms 1 and 2 of
+ * miosqp_qp_tree_form) and the reduced form (form 3); such a model gets bit for bit what
+ * miosqp_qp_solve_trees_sb(engines[b], 1, ...) gives it where that entry takes it.  leaf_cap: 0 keeps the reduced forms
+ * out (an engine of miosqp_qp_tree_form 0 is MIOSQP_EUNSUPPORTED), else at least 2.  sb_info[b]: the counters and the
+ * launch that ran model b (zeros and form 1..3 without a rule).  stats: models_wave, models_group and pad count the
+ * models of the three plain launches; launches may be 5. */
+int miosqp_qp_solve_trees_models_sb(int32_t B, miosqp_qp_engine *const *engines, const double *const *q, const double *const *l,
+                                    const double *const *u, const double *const *x0, const double *const *y0,
+                                    const double *upper0, const double *const *x_inc0, const int32_t *tree_explor_rule,
+                                    const int32_t *max_iter_bb, int32_t leaf_cap, const int32_t *branching_rule,
+                                    const int32_t *sb_candidates, const int32_t *sb_max_iter, const int32_t *sb_reliability,
+                                    const double *sb_eps, double *const *x_out, miosqp_tree_info *info,
+                                    miosqp_tree_sb_info *sb_info, miosqp_models_stats *stats);
+
 /* ---- polishes of DIFFERENT models in one launch -------------------------------------------------------
  * The polish of the "own P and A per MIQP" pattern: the reference sets up, solves and polishes one model per MIQP
  * (miosqp/solver.py:174-212 per model; `polish` reaches OSQP through qp_settings, miosqp/workspace.py:67-68), and

@@ -42,6 +42,11 @@ class TreeRfInfo(C.Structure):
                 ("osqp_iter", C.c_int32), ("form", C.c_int32), ("pad0", C.c_int32), ("pad1", C.c_int32)]
 
 
+class TreeSbInfo(C.Structure):
+    _fields_ = [("calls", C.c_int32), ("children", C.c_int32), ("osqp_iter", C.c_int32), ("form", C.c_int32),
+                ("pad0", C.c_int32), ("pad1", C.c_int32), ("pad2", C.c_int32), ("pad3", C.c_int32)]
+
+
 class ModelsStats(C.Structure):
     _fields_ = [("launches", C.c_int32), ("models_wave", C.c_int32), ("models_group", C.c_int32), ("pad", C.c_int32),
                 ("lds_bytes", C.c_int64), ("device_time", C.c_double), ("run_time", C.c_double)]
@@ -185,6 +190,12 @@ SYMBOLS = {
                                            C.c_int32, C.c_int32, dp, C.POINTER(TreeInfo), C.POINTER(TreeRfInfo)]),
     "miosqp_qp_solve_trees_models_rf": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), dpp, dpp, dpp, dpp, dpp, dp, dpp, ip, ip,
                                                   C.c_int32, ip, ip, ip, dpp, C.POINTER(TreeInfo), C.POINTER(TreeRfInfo),
+                                                  C.POINTER(ModelsStats)]),
+    "miosqp_qp_solve_trees_sb": (C.c_int, [C.c_void_p, C.c_int32, dp, dp, dp, dp, dp, dp, dp, C.c_int32, C.c_int32, C.c_int32,
+                                           C.c_int32, C.c_int32, C.c_int32, C.c_double, dp, C.POINTER(TreeInfo),
+                                           C.POINTER(TreeSbInfo)]),
+    "miosqp_qp_solve_trees_models_sb": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), dpp, dpp, dpp, dpp, dpp, dp, dpp, ip, ip,
+                                                  C.c_int32, ip, ip, ip, ip, dp, dpp, C.POINTER(TreeInfo), C.POINTER(TreeSbInfo),
                                                   C.POINTER(ModelsStats)]),
     "miosqp_qp_polish_models": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), dpp, dpp, dpp, dpp, dpp, C.c_double, dp, ip, ip, dpp,
                                           dpp, C.POINTER(C.c_void_p), C.POINTER(PolishRepairInfo), C.POINTER(PolishModelsStats)]),

@@ -124,12 +124,16 @@ def polish_repair_setting(settings):
     return int(it)
 
 
-def one_launch_trees_ok(work, rf=False):
+def one_launch_trees_ok(work, rf=False, sb=False):
     """would `solve_many` (and `solve_models`) try the one-launch trees for this workspace: the entry point is there, the
     settings are the plain search's, and the engine has not declined before.  rf=True (heuristic="device"): the same
-    question with primal_heuristic 1 allowed, for the entry that runs round and fix inside the launch"""
+    question with primal_heuristic 1 allowed, for the entry that runs round and fix inside the launch.  sb=True
+    (branching="device"): the same question with branching_rule 1 and 2 allowed -- without the heuristic --, for the entry
+    that runs strong / reliability branching inside the launch"""
     st, data = work.settings, work.data
-    return hasattr(work.solver, 'solve_trees') and st.get('device_tree', True) and st['branching_rule'] == 0 \
+    rule_ok = st['branching_rule'] == 0 or (sb and st['branching_rule'] in (1, 2) and not work.rf['on']
+                                            and hasattr(work.solver, 'solve_trees_sb'))
+    return hasattr(work.solver, 'solve_trees') and st.get('device_tree', True) and rule_ok \
         and (not work.rf['on'] or (rf and hasattr(work.solver, 'solve_trees_rf'))) \
         and st['tree_explor_rule'] in (0, 1, 2, 3) and data.n_int > 0 and 'eps_abs' in work.qp_settings \
         and st.get('device_digest', True) and not getattr(work, '_no_trees', False)
@@ -1249,7 +1253,7 @@ class MIOSQP(object):
                 res['polished'] = True
         return results
 
-    def solve_many(self, instances, polish=False, lockstep=None, ahead=8, *, heuristic=None):
+    def solve_many(self, instances, polish=False, lockstep=None, ahead=8, *, heuristic=None, branching=None):
         """B MIQPs on this model's factorisation, solved TOGETHER: instance k is what
         `update_vectors(q=, l=, u=)` [+ `set_x0(x0)`] + `solve()` would solve (the reference's MPC pattern,
         /root/reference/miosqp/solver.py:174-212, examples/power_converter/power_converter.py:467-476), for a list of
@@ -1330,10 +1334,27 @@ class MIOSQP(object):
         and a decline, go on as `lockstep` says.  `work.trees_rf` holds per instance calls, candidates, feasible,
         improved, osqp_iter as `rf_stats` defines them; the model's own `rf_stats` and `rf_nodes` are not touched.  With
         primal_heuristic 0 the keyword changes nothing; a backend without the entry (the CPU oracle) ignores it; any
-        other value raises ValueError before any launch.  Whether it pays is measured in DESIGN 3h."""
+        other value raises ValueError before any launch.  Whether it pays is measured in DESIGN 3h.
+
+        branching=None (the default): as above -- with branching_rule 1 or 2 the one-launch trees step aside.
+        branching="device": with branching_rule 1 or 2, primal_heuristic 0 and otherwise the one-launch trees' settings
+        the one-launch attempt is made with the rule INSIDE every tree (`OSQP.solve_trees_sb`, miosqp_qp_solve_trees_sb):
+        per tree the decisions of its sequential solve, every node that branches choosing its position as
+        `Workspace.select_branching` does -- sb_candidates, sb_max_iter, sb_reliability, sb_eps as `solve` reads them,
+        the 2K children solved by the tree's own workgroup, pseudo-costs per tree, starting empty; a child's value is
+        the device's sum.  One workgroup per instance, also for n + M <= 64.  Trees that overflow, and a decline, go on
+        as `lockstep` says.  `work.trees_sb` holds per instance calls, children, osqp_iter as `sb_stats` defines them;
+        the model's own `sb_stats`, `pc_sum` and `pc_cnt` are not touched.  With the rule AND primal_heuristic 1 the
+        one-launch trees step aside as before, whatever `heuristic` says.  With branching_rule 0 the keyword changes
+        nothing; a backend without the entry (the CPU oracle) ignores it; any other value raises ValueError before any
+        launch.  The rules do not shrink these trees by much.  Measured (profiles/solve_trees_sb.txt): against
+        the same call without the keyword 1.2-1.6 x at one instance, 6-10 x at 8 and 88-167 x at 256 instances of
+        (40,60,20) and (50,100,10); against branching_rule 0 in the one-launch trees it LOSES everywhere, 0.13-0.52 x
+        the MIQPs/s."""
         if not (polish is False or polish is True or (isinstance(polish, str) and polish == "device")):
             raise ValueError('solve_many: polish must be False, True or "device"')
         _heuristic_keyword(heuristic, 'solve_many')
+        _branching_keyword(branching, 'solve_many')
         work, data, st = self.work, self.work.data, self.work.settings
         require_plain_search(st, "solve_many", rule=False, heuristic=False)
         B = len(instances)
@@ -1342,6 +1363,8 @@ class MIOSQP(object):
         n, m, M = data.n, data.m, data.m + data.n_int
         ok_engine = one_launch_trees_ok(work)
         in_launch_rf = (heuristic == "device" and bool(work.rf['on']) and one_launch_trees_ok(work, rf=True)
+                        and hasattr(work.solver, 'tree_form') and work.solver.tree_form() != 0)
+        in_launch_sb = (branching == "device" and st['branching_rule'] in (1, 2) and one_launch_trees_ok(work, sb=True)
                         and hasattr(work.solver, 'tree_form') and work.solver.tree_form() != 0)
         Q, L, U = self._instance_vectors(instances)
         up = np.full(B, np.inf); XI = np.zeros((B, n)); any_inc = False
@@ -1353,9 +1376,14 @@ class MIOSQP(object):
         out = [None] * B
         redo = list(range(B))
         declined = True  # the one-launch path: absent, switched off, or it returned None
-        if ok_engine or in_launch_rf:
+        if ok_engine or in_launch_rf or in_launch_sb:
             t0 = time()
-            if in_launch_rf:
+            if in_launch_sb:
+                sb = work.sb
+                r = work.solver.solve_trees_sb(Q, L, U, np.zeros((B, n)), np.zeros((B, M)), up, XI if any_inc else None,
+                                               st['tree_explor_rule'], st['max_iter_bb'], sb['rule'], sb['K'],
+                                               sb['max_iter'], sb['reliability'], sb['eps'])
+            elif in_launch_rf:
                 r = work.solver.solve_trees_rf(Q, L, U, np.zeros((B, n)), np.zeros((B, M)), up, XI if any_inc else None,
                                                st['tree_explor_rule'], st['max_iter_bb'], work.rf['K'],
                                                work.rf['max_iter'], work.rf['every'])
@@ -1367,7 +1395,9 @@ class MIOSQP(object):
             else:
                 X, infos = r[0], r[1]
                 work.trees_info = infos  # per instance, as work.tree_info
-                if in_launch_rf:
+                if in_launch_sb:
+                    work.trees_sb = [_sb_counters(c) for c in r[2]]
+                elif in_launch_rf:
                     work.trees_rf = [_rf_counters(c) for c in r[2]]
                 dt = time() - t0
                 redo = []
@@ -1486,6 +1516,12 @@ def _rf_counters(rec):
                 improved=int(rec.improved), osqp_iter=int(rec.osqp_iter))
 
 
+def _sb_counters(rec):
+    """the counters of strong / reliability branching inside a one-launch tree (TreeSbInfo) as a dict with the keys of
+    sb_stats minus the time"""
+    return dict(calls=int(rec.calls), children=int(rec.children), osqp_iter=int(rec.osqp_iter))
+
+
 _BEYOND_ONE_LAUNCH = 'tree_form 0: beyond the one-launch trees'
 
 
@@ -1496,14 +1532,23 @@ def _heuristic_keyword(heuristic, who):
     return heuristic
 
 
-def _models_own_reason(work, declined_counts=True, rf=False):
+def _branching_keyword(branching, who):
+    """the keyword `branching` of solve_many / solve_models, checked: None or "device" """
+    if branching is not None and not (isinstance(branching, str) and branching == "device"):
+        raise ValueError('%s: branching must be None or "device"' % who)
+    return branching
+
+
+def _models_own_reason(work, declined_counts=True, rf=False, sb=False):
     """why `solve_models` leaves a model to its own `solve_many` (None: it goes into the launch); declined_counts=False
     looks past an earlier decline of the one-launch trees (an engine beyond them declines `solve_many`'s own attempt);
-    rf=True (heuristic="device") looks past primal_heuristic 1 on a backend that runs it inside the launch"""
+    rf=True (heuristic="device") looks past primal_heuristic 1 on a backend that runs it inside the launch; sb=True
+    (branching="device") looks past branching_rule 1 and 2 on a backend that runs them inside the launch -- not together
+    with primal_heuristic 1, which has its own reason"""
     if not declined_counts and getattr(work, '_no_trees', False):
         work._no_trees = False
         try:
-            return _models_own_reason(work, rf=rf)
+            return _models_own_reason(work, rf=rf, sb=sb)
         finally:
             work._no_trees = True
     st = work.settings
@@ -1512,14 +1557,17 @@ def _models_own_reason(work, declined_counts=True, rf=False):
     if not st.get('device_tree', True):
         return 'device_tree off'
     if st['branching_rule'] != 0:
-        return 'branching_rule %d' % st['branching_rule']
+        if not (sb and st['branching_rule'] in (1, 2) and hasattr(work.solver, 'solve_trees_sb')):
+            return 'branching_rule %d' % st['branching_rule']
+        if work.rf['on']:
+            return 'branching_rule %d together with primal_heuristic on' % st['branching_rule']
     if work.rf['on'] and not (rf and hasattr(work.solver, 'solve_trees_rf')):
         return 'primal_heuristic on'
     if work.data.n_int == 0:
         return 'n_int == 0'
     if getattr(work, '_no_trees', False):
         return 'the one-launch trees declined this model before'
-    if not one_launch_trees_ok(work, rf=rf):
+    if not one_launch_trees_ok(work, rf=rf, sb=sb):
         return 'settings beyond the one-launch trees'
     try:
         require_plain_search(st, "solve_models", rule=False, heuristic=False)
@@ -1662,7 +1710,7 @@ def polish_models(models, instances, results, tau=None, repair_iter=20, guess="h
 
 
 def solve_models(models, instances=None, info=None, polish=False, polish_guess="host", large=None, leaf_cap=256,
-                 polish_large=None, *, heuristic=None):
+                 polish_large=None, *, heuristic=None, branching=None):
     """One MIQP on each of several DIFFERENT set-up models -- each with its own P, A, shapes and settings --, the trees
     of all of them in ONE call of the library (`qp.solve_trees_models`, miosqp_qp_solve_trees_models: at most two
     launches, workgroup or wavefront b runs model b).  It replaces the loop `models[k].solve_many([instances[k]])`: one
@@ -1717,11 +1765,27 @@ def solve_models(models, instances=None, info=None, polish=False, polish_guess="
     them, bit for bit.  Composes with polish=True.  A backend without the entry (the CPU oracle) ignores the keyword;
     any other value raises ValueError before any launch.
 
+    branching=None (the default): as above.  branching="device": a model that stays out ONLY for 'branching_rule 1' or
+    'branching_rule 2' goes into the call (`qp.solve_trees_models(..., sb=...)`, miosqp_qp_solve_trees_models_sb) and
+    chooses its branching positions as `Workspace.select_branching` does inside its tree, in up to two more launches: the
+    workgroup form (which takes the wave-sized models too) and, with large="device", the reduced form.  Result k is then
+    what `models[k].solve_many([instances[k]], branching="device")[0]` returns, bit for bit in the workgroup form; a
+    reduced-form tree is that of the CPU oracle backend with the rule, as above.  Models with branching_rule 0 get what
+    the call without the keyword gives them, bit for bit.  A model with the rule AND primal_heuristic 1 stays on its own
+    path, whatever `heuristic` says ('branching_rule %d together with primal_heuristic on').  The model's own `sb_stats`,
+    `pc_sum` and `pc_cnt` are left as they were; `work.trees_sb` gets the tree's counters.  Composes with polish=True
+    and heuristic="device" (the models with the heuristic and the models with a rule then go in two calls of the
+    library).  A backend without the entry (the CPU oracle) ignores the keyword; any other value raises ValueError
+    before any launch.
+
     info: a dict that is filled with launched (positions), own ({position: why}), forms ({'wave': .., 'group': ..}; with
-    large="device" also 'reduced'; with heuristic="device" also 'group_rf' and 'reduced_rf'), launches, device_time
-    (seconds) and overflow (positions); with heuristic="device" also rf ({position: counters} of the models that ran with
-    round and fix inside the launch, keys as `rf_stats`); with polish=True also what `polish_models` reports."""
+    large="device" also 'reduced'; with heuristic="device" also 'group_rf' and 'reduced_rf'; with branching="device"
+    also 'group_sb' and 'reduced_sb'), launches, device_time (seconds) and overflow (positions); with heuristic="device"
+    also rf ({position: counters} of the models that ran with round and fix inside the launch, keys as `rf_stats`); with
+    branching="device" also sb ({position: dict(calls, children, osqp_iter)} of the models that ran with a rule inside
+    the launch); with polish=True also what `polish_models` reports."""
     _heuristic_keyword(heuristic, 'solve_models')
+    _branching_keyword(branching, 'solve_models')
     if not (polish is False or polish is True):
         raise ValueError('solve_models: polish must be False or True')
     if large is not None and not (isinstance(large, str) and large == "device"):
@@ -1757,9 +1821,13 @@ def solve_models(models, instances=None, info=None, polish=False, polish_guess="
     launched = []
     any_large = False
     in_rf = heuristic == "device"
+    in_sb = branching == "device"
     rf_par = {}  # position: (rf_candidates, rf_max_iter, rf_every) of the models that run round and fix in the launch
+    sb_par = {}  # position: (rule, sb_candidates, sb_max_iter, sb_reliability, sb_eps) of the models that run their rule there
     for k, mdl in enumerate(models):
-        look = dict(rf=True) if in_rf else {}  # (without the keyword the question is asked as it always was)
+        look = dict(rf=True) if in_rf else {}  # (without the keywords the question is asked as it always was)
+        if in_sb:
+            look['sb'] = True
         why = _models_own_reason(mdl.work, **look)
         if (large == "device" and why is not None and hasattr(mdl.work.solver, 'tree_form_large')
                 and _models_own_reason(mdl.work, declined_counts=False, **look) == _BEYOND_ONE_LAUNCH
@@ -1768,7 +1836,10 @@ def solve_models(models, instances=None, info=None, polish=False, polish_guess="
             any_large = True
         if why is None:
             launched.append(k)
-            if in_rf and mdl.work.rf['on']:
+            if in_sb and mdl.work.sb['rule'] != 0:
+                sb = mdl.work.sb
+                sb_par[k] = (sb['rule'], sb['K'], sb['max_iter'], sb['reliability'], sb['eps'])
+            elif in_rf and mdl.work.rf['on']:
                 rf_par[k] = (mdl.work.rf['K'], mdl.work.rf['max_iter'], mdl.work.rf['every'])
         else:
             own[k] = why
@@ -1777,48 +1848,72 @@ def solve_models(models, instances=None, info=None, polish=False, polish_guess="
     forms = dict(wave=0, group=0, reduced=0) if large == "device" else dict(wave=0, group=0)
     if in_rf:
         forms.update(group_rf=0, reduced_rf=0)
-    rf_out = {}
+    if in_sb:
+        forms.update(group_sb=0, reduced_sb=0)
+    rf_out, sb_out = {}, {}
     launches, device_time = 0, 0.0
     if launched:
         from miosqp_amd import qp
         inc = {}
         for k in launched:
             inc[k] = models[k]._instance_incumbent(instances[k], *vec[k])
-        t0 = time()
-        r = qp.solve_trees_models(
-            [models[k].work.solver for k in launched], [vec[k][0] for k in launched], [vec[k][1] for k in launched],
-            [vec[k][2] for k in launched], [np.zeros(models[k].work.data.n) for k in launched],
-            [np.zeros(len(vec[k][1])) for k in launched], [np.inf if inc[k] is None else inc[k][0] for k in launched],
-            [None if inc[k] is None else inc[k][1] for k in launched],
-            [models[k].work.settings['tree_explor_rule'] for k in launched],
-            [models[k].work.settings['max_iter_bb'] for k in launched], **(dict(leaf_cap=leaf_cap) if any_large else {}),
-            **(dict(rf=[rf_par.get(k) for k in launched]) if rf_par else {}))
-        dt = time() - t0
-        if r is None:  # (an engine declined after all: every model on its own)
-            for k in launched:
-                own[k] = 'the library declined the call'
-            launched = []
+        # one call of the library; two when models with the heuristic and models with a rule are both in the list (an
+        # entry of the library takes one of the two): the models with a rule then form the second call.  forms,
+        # launches, device_time, launched and overflow are summed over the calls and put in list order: with the one
+        # call of every list without both kinds, they are what that call reports, as before
+        if rf_par and sb_par:
+            with_rule = [k for k in launched if k in sb_par]
+            others = [k for k in launched if k not in sb_par]
+            calls = [(others, dict(rf=rf_par)), (with_rule, dict(sb=sb_par))]
+        elif rf_par:
+            calls = [(list(launched), dict(rf=rf_par))]
+        elif sb_par:
+            calls = [(list(launched), dict(sb=sb_par))]
         else:
+            calls = [(list(launched), {})]
+        done = []
+        for group, extra in calls:
+            kw = {name: [par.get(k) for k in group] for name, par in extra.items()}
+            t0 = time()
+            r = qp.solve_trees_models(
+                [models[k].work.solver for k in group], [vec[k][0] for k in group], [vec[k][1] for k in group],
+                [vec[k][2] for k in group], [np.zeros(models[k].work.data.n) for k in group],
+                [np.zeros(len(vec[k][1])) for k in group], [np.inf if inc[k] is None else inc[k][0] for k in group],
+                [None if inc[k] is None else inc[k][1] for k in group],
+                [models[k].work.settings['tree_explor_rule'] for k in group],
+                [models[k].work.settings['max_iter_bb'] for k in group], **(dict(leaf_cap=leaf_cap) if any_large else {}), **kw)
+            dt = time() - t0
+            if r is None:  # (an engine declined after all: every model on its own)
+                for k in group:
+                    own[k] = 'the library declined the call'
+                continue
             X, infos, stats = r[:3]
-            forms = dict(wave=int(stats.models_wave), group=int(stats.models_group))
+            forms['wave'] += int(stats.models_wave)
+            forms['group'] += int(stats.models_group)
             if large == "device":
-                forms['reduced'] = int(stats.pad)
-            if in_rf:
-                forms.update(group_rf=0, reduced_rf=0)
-            if rf_par:
-                for j, k in enumerate(launched):
-                    if k in rf_par:
-                        forms['reduced_rf' if r[3][j].form == 5 else 'group_rf'] += 1
-                        rf_out[k] = _rf_counters(r[3][j])
-            launches, device_time = int(stats.launches), float(stats.device_time)
-            for j, k in enumerate(launched):
+                forms['reduced'] += int(stats.pad)
+            for j, k in enumerate(group):
+                if 'rf' in kw and k in rf_par:
+                    forms['reduced_rf' if r[3][j].form == 5 else 'group_rf'] += 1
+                    rf_out[k] = _rf_counters(r[3][j])
+                if 'sb' in kw and k in sb_par:
+                    forms['reduced_sb' if r[3][j].form == 7 else 'group_sb'] += 1
+                    sb_out[k] = _sb_counters(r[3][j])
+            launches += int(stats.launches)
+            device_time += float(stats.device_time)
+            for j, k in enumerate(group):
+                done.append(k)
                 models[k].work.trees_info = [infos[j]]
                 if k in rf_out:
                     models[k].work.trees_rf = [rf_out[k]]
+                if k in sb_out:
+                    models[k].work.trees_sb = [sb_out[k]]
                 if infos[j].overflow:
                     overflow.append(k)
                     continue
-                out[k] = models[k]._tree_result(infos[j], X[j], np.inf if inc[k] is None else inc[k][0], dt / len(launched))
+                out[k] = models[k]._tree_result(infos[j], X[j], np.inf if inc[k] is None else inc[k][0], dt / len(group))
+        launched = sorted(done)
+        overflow.sort()
     for k in range(B):
         if out[k] is None:
             out[k] = models[k].solve_many([instances[k]])[0]
@@ -1827,6 +1922,8 @@ def solve_models(models, instances=None, info=None, polish=False, polish_guess="
                     overflow=list(overflow))
         if in_rf:
             info['rf'] = rf_out
+        if in_sb:
+            info['sb'] = sb_out
     if polish:
         polish_models(models, instances, out, guess=polish_guess, info=info, large=polish_large)
     return out

@@ -47,6 +47,7 @@
 #include "polish_models_large_plan.hpp"  // ... of different LARGER models: fit rule, workgroups and arena layout with the slabs (plain C++; host_polish_models_large.inc drives it)
 #include "tree_reduced_body.hpp"  // the one-launch trees' relaxation in reduced form (k_tree_r_m): LDS rule and the phases of an iteration (plain C++; also run on the CPU under tests/)
 #include "tree_rf_logic.hpp"  // round and fix inside the one-launch trees (k_tree_rf*): when it fires, the fixed value, the pick (plain C++; also run on the CPU under tests/)
+#include "tree_sb_logic.hpp"  // strong / reliability branching inside the one-launch trees (k_tree_sb*): candidates, scores, pseudo-costs, the pick (plain C++; also run on the CPU under tests/)
 #include "models_plan.hpp"  // trees of different models in one launch: argument checks and arena layout (plain C++; host_models.inc drives it)
 #include "lockstep_refill.hpp"  // which tree goes into which free column when the columns are refilled between chunks (plain C++; host_refill.inc drives it)
 
@@ -273,7 +274,7 @@ namespace {
 // the dynamic-LDS ceiling of a kernel is a property of (process, device, kernel): raised to the chip's 160 KB once instead of
 // at every set-up (the call costs ~40 us, a fifth of a small problem's set-up)
 hipError_t lds_limit_once(const void *fn, int which) {
-  static bool done[22][64] = {};  // (one row per kernel: 0 .. 13 as before, 14: k_setup_models, 15: k_setup_models_auto, 16: k_tree_r_m, 17: k_setup_models_large, 18: k_setup_models_large_auto, 19: k_tree_rf, 20: k_tree_rf_m, 21: k_tree_rf_r_m)
+  static bool done[25][64] = {};  // (one row per kernel: 0 .. 13 as before, 14: k_setup_models, 15: k_setup_models_auto, 16: k_tree_r_m, 17: k_setup_models_large, 18: k_setup_models_large_auto, 19: k_tree_rf, 20: k_tree_rf_m, 21: k_tree_rf_r_m, 22: k_tree_sb, 23: k_tree_sb_m, 24: k_tree_sb_r_m)
   int dev = 0;
   hipError_t rc = hipGetDevice(&dev);
   if (rc != hipSuccess) return rc;
@@ -2106,12 +2107,22 @@ int miosqp_qp_solve_tree(miosqp_qp_engine *e, const double *l, const double *u, 
   return 0;
 }
 
+// the settings of strong / reliability branching for one engine's trees (miosqp_qp_solve_trees_sb), and where the
+// counters go
+struct TreesSb {
+  int32_t rule, K, max_iter, reliability;
+  double eps;
+  miosqp_tree_sb_info *info;
+};
+
 // miosqp_qp_solve_trees, and with rf_info miosqp_qp_solve_trees_rf: the same staging and copies, k_tree_rf in place of
-// k_tree / k_tree_w, the counters of round and fix per instance beside the outcomes
+// k_tree / k_tree_w, the counters of round and fix per instance beside the outcomes; with sb miosqp_qp_solve_trees_sb in
+// the same way: k_tree_sb, and the work areas of strong / reliability branching per instance
 static int trees_run(miosqp_qp_engine *e, int32_t B, const double *q, const double *l, const double *u, const double *x0,
                      const double *y0, const double *upper0, const double *x_inc0, int32_t tree_explor_rule,
                      int32_t max_iter_bb, double *x_out, miosqp_tree_info *info, int32_t rf_candidates = 0,
-                     int32_t rf_max_iter = 0, int32_t rf_every = 0, miosqp_tree_rf_info *rf_info = nullptr) {
+                     int32_t rf_max_iter = 0, int32_t rf_every = 0, miosqp_tree_rf_info *rf_info = nullptr,
+                     const TreesSb *sb = nullptr) {
   if (!e || B < 1 || !q || !l || !u || !x0 || !y0 || !upper0 || !x_out || !info || max_iter_bb < 1 || tree_explor_rule < 0 ||
       tree_explor_rule > 3)
     return MIOSQP_EARG;
@@ -2136,6 +2147,9 @@ static int trees_run(miosqp_qp_engine *e, int32_t B, const double *q, const doub
   if (rf_info) {  // (k_tree_rf also runs the wave-sized engines: sized for the engine as tree_wave_prepare left it)
     lds = tree_lds_bytes(e, &tree_sp_off);
     HIPCHK(lds_limit_once((const void *)k_tree_rf, 19));
+  } else if (sb) {  // (k_tree_sb takes the wave-sized engines in the same way)
+    lds = tree_lds_bytes(e, &tree_sp_off);
+    HIPCHK(lds_limit_once((const void *)k_tree_sb, 22));
   } else if (!wave) {
     HIPCHK(lds_limit_once((const void *)k_tree, 1));
   }
@@ -2155,6 +2169,15 @@ static int trees_run(miosqp_qp_engine *e, int32_t B, const double *q, const doub
     if (!rc) rc = dalloc(e, &e->tb_rf, cap);
     if (rc) return rc;
     e->tb_cap = (int)cap;
+  }
+  if (sb && (B > e->tb_sb_cap || p != e->tb_sb_p)) {  // (its own capacity: a call without the rule pays nothing for it)
+    const size_t cap = (size_t)std::max(B, B > e->tb_sb_cap ? 2 * e->tb_sb_cap : e->tb_sb_cap);
+    int rc = dalloc(e, &e->tb_sbw, cap * miosqp::tree_sb::work_doubles(p));
+    if (!rc) rc = dalloc(e, &e->tb_sbpc, cap * (size_t)TREE_CAP * miosqp::tree_sb::PC_DOUBLES);
+    if (!rc) rc = dalloc(e, &e->tb_sb, cap);
+    if (rc) return rc;
+    e->tb_sb_cap = (int)cap;
+    e->tb_sb_p = p;
   }
   // one staging vector: [raw blocks | q | incumbents | upper] in
   const size_t nin = (size_t)B * (blk + 2 * (size_t)n + 1);
@@ -2201,6 +2224,16 @@ static int trees_run(miosqp_qp_engine *e, int32_t B, const double *q, const doub
     ta.rf_every = rf_every;
     ta.rf_out = e->tb_rf;
   }
+  if (sb) {
+    ta.sb_rule = sb->rule;
+    ta.sb_K = sb->K;
+    ta.sb_max_iter = sb->max_iter;
+    ta.sb_rel = sb->reliability;
+    ta.sb_eps = sb->eps;
+    ta.sb_work = e->tb_sbw;
+    ta.sb_pc = e->tb_sbpc;
+    ta.sb_out = e->tb_sb;
+  }
   Dev db = e->d;  // instance 0's arrays; workgroup b moves on from there (tree_instance)
   db.q = e->tb_q;
   db.qraw = e->tb_qraw;
@@ -2211,6 +2244,7 @@ static int trees_run(miosqp_qp_engine *e, int32_t B, const double *q, const doub
   db.prof = nullptr;
   // (with round and fix the workgroup form also takes the wave-sized models: tree_lds_bytes sized it for the engine as it stands)
   if (rf_info) hipLaunchKernelGGL(k_tree_rf, dim3(B), dim3(RES_THREADS), lds, e->stream, db, ta);
+  else if (sb) hipLaunchKernelGGL(k_tree_sb, dim3(B), dim3(RES_THREADS), lds, e->stream, db, ta);
   else if (wave) hipLaunchKernelGGL(k_tree_w, dim3(B), dim3(TW), 0, e->stream, db, ta);
   else hipLaunchKernelGGL(k_tree, dim3(B), dim3(RES_THREADS), lds, e->stream, db, ta);
   if (e->tb_hout.size() < (size_t)B) e->tb_hout.resize(B);
@@ -2218,6 +2252,10 @@ static int trees_run(miosqp_qp_engine *e, int32_t B, const double *q, const doub
   if (rf_info) {
     if (e->tb_hrf.size() < (size_t)B) e->tb_hrf.resize(B);
     HIPCHK(hipMemcpyAsync(e->tb_hrf.data(), e->tb_rf, sizeof(TreeRfOut) * B, hipMemcpyDeviceToHost, e->stream));
+  }
+  if (sb) {
+    if (e->tb_hsb.size() < (size_t)B) e->tb_hsb.resize(B);
+    HIPCHK(hipMemcpyAsync(e->tb_hsb.data(), e->tb_sb, sizeof(TreeSbOut) * B, hipMemcpyDeviceToHost, e->stream));
   }
   HIPCHK(hipMemcpyAsync(h_inc, e->tb_inc, sizeof(double) * (size_t)B * n, hipMemcpyDeviceToHost, e->stream));
   HIPCHK(hipEventRecord(e->ev1, e->stream));
@@ -2246,6 +2284,10 @@ static int trees_run(miosqp_qp_engine *e, int32_t B, const double *q, const doub
       const TreeRfOut &r = e->tb_hrf[b];
       rf_info[b] = miosqp_tree_rf_info{r.calls, r.candidates, r.feasible, r.improved, r.osqp_iter, 4, 0, 0};
     }
+    if (sb) {
+      const TreeSbOut &r = e->tb_hsb[b];
+      sb->info[b] = miosqp_tree_sb_info{r.calls, r.children, r.osqp_iter, 6, 0, 0, 0, 0};
+    }
   }
   e->loop_ms += ms;
   e->loop_iters += iters;
@@ -2269,6 +2311,21 @@ int miosqp_qp_solve_trees_rf(miosqp_qp_engine *e, int32_t B, const double *q, co
   }
   return trees_run(e, B, q, l, u, x0, y0, upper0, x_inc0, tree_explor_rule, max_iter_bb, x_out, info, rf_candidates, rf_max_iter,
                    rf_every, rf_info);
+}
+
+int miosqp_qp_solve_trees_sb(miosqp_qp_engine *e, int32_t B, const double *q, const double *l, const double *u,
+                             const double *x0, const double *y0, const double *upper0, const double *x_inc0,
+                             int32_t tree_explor_rule, int32_t max_iter_bb, int32_t branching_rule, int32_t sb_candidates,
+                             int32_t sb_max_iter, int32_t sb_reliability, double sb_eps, double *x_out, miosqp_tree_info *info,
+                             miosqp_tree_sb_info *sb_info) {
+  std::string err;
+  if (int rc = miosqp::models::check_sb(1, &branching_rule, &sb_candidates, &sb_max_iter, &sb_reliability, &sb_eps, sb_info, 1,
+                                        "solve_trees_sb", err)) {
+    g_err = err;
+    return rc;
+  }
+  const TreesSb sb{branching_rule, sb_candidates, sb_max_iter, sb_reliability, sb_eps, sb_info};
+  return trees_run(e, B, q, l, u, x0, y0, upper0, x_inc0, tree_explor_rule, max_iter_bb, x_out, info, 0, 0, 0, nullptr, &sb);
 }
 
 int miosqp_qp_tree_form(miosqp_qp_engine *e) {
@@ -2309,6 +2366,18 @@ int miosqp_qp_solve_trees_models_rf(int32_t B, miosqp_qp_engine *const *engines,
                                     miosqp_tree_info *info, miosqp_tree_rf_info *rf_info, miosqp_models_stats *stats) {
   return models_run(B, engines, q, l, u, x0, y0, upper0, x_inc0, tree_explor_rule, max_iter_bb, x_out, info, stats, leaf_cap != 0,
                     leaf_cap, true, rf_candidates, rf_max_iter, rf_every, rf_info);
+}
+
+int miosqp_qp_solve_trees_models_sb(int32_t B, miosqp_qp_engine *const *engines, const double *const *q, const double *const *l,
+                                    const double *const *u, const double *const *x0, const double *const *y0,
+                                    const double *upper0, const double *const *x_inc0, const int32_t *tree_explor_rule,
+                                    const int32_t *max_iter_bb, int32_t leaf_cap, const int32_t *branching_rule,
+                                    const int32_t *sb_candidates, const int32_t *sb_max_iter, const int32_t *sb_reliability,
+                                    const double *sb_eps, double *const *x_out, miosqp_tree_info *info,
+                                    miosqp_tree_sb_info *sb_info, miosqp_models_stats *stats) {
+  const ModelsSb sb{branching_rule, sb_candidates, sb_max_iter, sb_reliability, sb_eps, sb_info};
+  return models_run(B, engines, q, l, u, x0, y0, upper0, x_inc0, tree_explor_rule, max_iter_bb, x_out, info, stats, leaf_cap != 0,
+                    leaf_cap, false, nullptr, nullptr, nullptr, nullptr, &sb);
 }
 
 int miosqp_qp_debug_iterate(miosqp_qp_engine *e, int32_t k, double *x, double *z, double *y) {

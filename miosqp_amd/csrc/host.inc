@@ -72,6 +72,12 @@ struct miosqp_qp_engine {
   std::vector<double> tb_host;   // staging: [raw block | inc | upper] in, [inc] out
   std::vector<TreeOut> tb_hout;
   std::vector<TreeRfOut> tb_hrf;
+  // miosqp_qp_solve_trees_sb: per instance the work area, Node.pc of every leaf-store place and the counters of strong /
+  // reliability branching (capacity tb_sb_cap instances of tb_sb_p integer positions)
+  int tb_sb_cap = 0, tb_sb_p = 0;
+  double *tb_sbw = nullptr, *tb_sbpc = nullptr;
+  TreeSbOut *tb_sb = nullptr;
+  std::vector<TreeSbOut> tb_hsb;
   // miosqp_qp_solve_trees_models with this engine first: the call's arena (from this engine's pool) and the pinned mirror
   // of its staged part, capacities in doubles
   double *mm_dev = nullptr, *mm_host = nullptr;

@@ -3,7 +3,9 @@
 // models beyond one workgroup's product form miosqp_qp_tree_form_large, miosqp_qp_solve_trees_models_large; kernels
 // k_tree_m / k_tree_w_m / k_tree_r_m / k_scale_q_models in kernels_tree.inc; argument checks and arena layout in
 // models_plan.hpp).  With round and fix inside the trees (miosqp_qp_solve_trees_models_rf): the models that have it on
-// form up to two more launches, k_tree_rf_m and k_tree_rf_r_m, behind the other three.
+// form up to two more launches, k_tree_rf_m and k_tree_rf_r_m, behind the other three.  With strong / reliability
+// branching inside the trees (miosqp_qp_solve_trees_models_sb): the models with a rule form the launches k_tree_sb_m and
+// k_tree_sb_r_m in the same way.
 extern "C" {
 static int stage_wait(miosqp_qp_engine *e, int k);
 }
@@ -135,12 +137,19 @@ int models_reserve(miosqp_qp_engine *e, size_t total_doubles, size_t up_doubles)
   return 0;
 }
 
+// the per-model settings of strong / reliability branching (miosqp_qp_solve_trees_models_sb), and where the counters go
+struct ModelsSb {
+  const int32_t *rule, *K, *max_iter, *reliability;
+  const double *eps;
+  miosqp_tree_sb_info *info;
+};
+
 int models_run(int32_t B, miosqp_qp_engine *const *engines, const double *const *q, const double *const *l,
                const double *const *u, const double *const *x0, const double *const *y0, const double *upper0,
                const double *const *x_inc0, const int32_t *rule, const int32_t *max_iter_bb, double *const *x_out,
                miosqp_tree_info *info, miosqp_models_stats *stats, bool large = false, int32_t leaf_cap = 0,
                bool with_rf = false, const int32_t *rf_candidates = nullptr, const int32_t *rf_max_iter = nullptr,
-               const int32_t *rf_every = nullptr, miosqp_tree_rf_info *rf_info = nullptr) {
+               const int32_t *rf_every = nullptr, miosqp_tree_rf_info *rf_info = nullptr, const ModelsSb *sb = nullptr) {
   namespace mm = miosqp::models;
   // ---- refused before anything is queued ----
   if (large) {
@@ -164,6 +173,13 @@ int models_run(int32_t B, miosqp_qp_engine *const *engines, const double *const 
   if (with_rf) {  // miosqp_qp_solve_trees_models_rf: the per-model settings of round and fix
     std::string err;
     if (int rc = mm::check_rf(B, rf_candidates, rf_max_iter, rf_every, rf_info, 0, "solve_trees_models_rf", err)) {
+      g_err = err;
+      return rc;
+    }
+  }
+  if (sb) {  // miosqp_qp_solve_trees_models_sb: the per-model settings of strong / reliability branching
+    std::string err;
+    if (int rc = mm::check_sb(B, sb->rule, sb->K, sb->max_iter, sb->reliability, sb->eps, sb->info, 0, "solve_trees_models_sb", err)) {
       g_err = err;
       return rc;
     }
@@ -197,10 +213,13 @@ int models_run(int32_t B, miosqp_qp_engine *const *engines, const double *const 
     }
     // with the heuristic on: the workgroup form (the wave-sized models too), or the reduced form
     if (with_rf && rf_candidates[b] > 0) form = form == 3 ? 5 : 4;
+    // with a branching rule: the same two forms with strong / reliability branching inside
+    if (sb && sb->rule[b] > 0) form = form == 3 ? 7 : 6;
     sh[(size_t)b] = mm::Shape{e->n, e->M, e->d.n_int, form};
   }
-  const mm::Plan P = mm::plan(sh, sizeof(TreeModel), (size_t)TREE_CAP, (size_t)leaf_cap, with_rf ? mm::RF_DOUBLES : 0);
-  if (P.n3 || P.n5) {  // the leaf stores of the reduced form are the large part of an arena: refused by name, not a failed allocation
+  const mm::Plan P = mm::plan(sh, sizeof(TreeModel), (size_t)TREE_CAP, (size_t)leaf_cap, with_rf ? mm::RF_DOUBLES : 0,
+                              sb ? mm::SB_DOUBLES : 0);
+  if (P.n3 || P.n5 || P.n7) {  // the leaf stores of the reduced form are the large part of an arena: refused by name, not a failed allocation
     size_t fr = 0, tot = 0;
     HIPCHK(hipMemGetInfo(&fr, &tot));
     const size_t have = e0->mm_cap * sizeof(double), room = (fr > ((size_t)256 << 20) ? fr - ((size_t)256 << 20) : 0);
@@ -215,6 +234,8 @@ int models_run(int32_t B, miosqp_qp_engine *const *engines, const double *const 
   if (P.n3) HIPCHK(lds_limit_once((const void *)k_tree_r_m, 16));
   if (P.n4) HIPCHK(lds_limit_once((const void *)k_tree_rf_m, 20));
   if (P.n5) HIPCHK(lds_limit_once((const void *)k_tree_rf_r_m, 21));
+  if (P.n6) HIPCHK(lds_limit_once((const void *)k_tree_sb_m, 23));
+  if (P.n7) HIPCHK(lds_limit_once((const void *)k_tree_sb_r_m, 24));
   // every other engine's stream in front of the launches: an update or a lazy build queued there has finished
   for (int b = 1; b < B; b++) {
     if (int rc = stage_wait(engines[b], 0)) return rc;
@@ -225,7 +246,7 @@ int models_run(int32_t B, miosqp_qp_engine *const *engines, const double *const 
   //      update_lin_cost, a lazy build of W or a tripped guard) ----
   double *hs = e0->mm_host, *dv = e0->mm_dev;
   TreeModel *tab_h = reinterpret_cast<TreeModel *>(hs), *tab_d = reinterpret_cast<TreeModel *>(dv);
-  size_t lds_max = 0, lds_max_r = 0, lds_max_rf = 0, lds_max_rf_r = 0;
+  size_t lds_max = 0, lds_max_r = 0, lds_max_rf = 0, lds_max_rf_r = 0, lds_max_sb = 0, lds_max_sb_r = 0;
   for (int b = 0; b < B; b++) {
     miosqp_qp_engine *e = engines[b];
     const mm::Slot &s = P.slot[(size_t)b];
@@ -241,6 +262,7 @@ int models_run(int32_t B, miosqp_qp_engine *const *engines, const double *const 
     else memset(hs + s.inc, 0, sizeof(double) * n);
     memset(hs + s.out, 0, sizeof(double) * mm::OUT_DOUBLES);
     if (with_rf) memset(hs + s.rf, 0, sizeof(double) * mm::RF_DOUBLES);
+    if (sb) memset(hs + s.sb, 0, sizeof(double) * mm::SB_DOUBLES);
     TreeModel &t = tab_h[s.entry];
     t.d = e->d;
     t.d.q = dv + s.q;
@@ -279,22 +301,33 @@ int models_run(int32_t B, miosqp_qp_engine *const *engines, const double *const 
       ta.rf_every = rf_every[b];
       ta.rf_out = reinterpret_cast<TreeRfOut *>(dv + s.rf);
     }
+    if (form == 6 || form == 7) {
+      ta.sb_rule = sb->rule[b];
+      ta.sb_K = sb->K[b];
+      ta.sb_max_iter = sb->max_iter[b];
+      ta.sb_rel = sb->reliability[b];
+      ta.sb_eps = sb->eps[b];
+      ta.sb_work = dv + s.sb_work;
+      ta.sb_pc = dv + s.sb_pc;
+      ta.sb_out = reinterpret_cast<TreeSbOut *>(dv + s.sb);
+    }
     if (mm::reduced_form(form)) {
       ta.leaf_cap = leaf_cap;
       ta.TG1 = miosqp::tree_reduced::TGR;  // rows of Abar in the prologue, the test and the epilogue: as the iteration walks them
       ta.r_dense = tree_r_dense(e);
-      size_t &most = form == 5 ? lds_max_rf_r : lds_max_r;
+      size_t &most = form == 5 ? lds_max_rf_r : form == 7 ? lds_max_sb_r : lds_max_r;
       most = std::max(most, tree_r_lds_bytes(e, leaf_cap, &ta.sp_off, &ta.pv_off));
     }
-    if (form == 2 || form == 4) {  // (after the form is settled: W may have come or gone in tree_form_of)
+    if (form == 2 || form == 4 || form == 6) {  // (after the form is settled: W may have come or gone in tree_form_of)
       const size_t lds = tree_lds_bytes(e, &ta.sp_off);
-      size_t &most = form == 4 ? lds_max_rf : lds_max;
+      size_t &most = form == 4 ? lds_max_rf : form == 6 ? lds_max_sb : lds_max;
       most = std::max(most, lds);
     }
     t.ta = ta;
   }
   static_assert(sizeof(TreeOut) <= mm::OUT_DOUBLES * sizeof(double), "TreeOut fits its place in the arena");
   static_assert(sizeof(TreeRfOut) <= mm::RF_DOUBLES * sizeof(double), "TreeRfOut fits its place in the arena");
+  static_assert(sizeof(TreeSbOut) <= mm::SB_DOUBLES * sizeof(double), "TreeSbOut fits its place in the arena");
   // ---- one upload, the costs scaled, one tree launch per form that has a model, one download, one synchronisation ----
   HIPCHK(hipEventRecord(e0->ev0, e0->stream));
   HIPCHK(hipMemcpyAsync(dv, hs, sizeof(double) * P.up_doubles, hipMemcpyHostToDevice, e0->stream));
@@ -307,6 +340,12 @@ int models_run(int32_t B, miosqp_qp_engine *const *engines, const double *const 
   if (P.n5)
     hipLaunchKernelGGL(k_tree_rf_r_m, dim3((unsigned)P.n5), dim3(RES_THREADS), lds_max_rf_r, e0->stream,
                        tab_d + P.n1 + P.n2 + P.n3 + P.n4);
+  if (P.n6)
+    hipLaunchKernelGGL(k_tree_sb_m, dim3((unsigned)P.n6), dim3(RES_THREADS), lds_max_sb, e0->stream,
+                       tab_d + P.n1 + P.n2 + P.n3 + P.n4 + P.n5);
+  if (P.n7)
+    hipLaunchKernelGGL(k_tree_sb_r_m, dim3((unsigned)P.n7), dim3(RES_THREADS), lds_max_sb_r, e0->stream,
+                       tab_d + P.n1 + P.n2 + P.n3 + P.n4 + P.n5 + P.n6);
   HIPCHK(hipMemcpyAsync(hs + P.down_off, dv + P.down_off, sizeof(double) * P.down_doubles, hipMemcpyDeviceToHost, e0->stream));
   HIPCHK(hipEventRecord(e0->ev1, e0->stream));
   HIPCHK(hipStreamSynchronize(e0->stream));
@@ -338,12 +377,18 @@ int models_run(int32_t B, miosqp_qp_engine *const *engines, const double *const 
       memcpy(&r, hs + s.rf, sizeof r);
       rf_info[b] = miosqp_tree_rf_info{r.calls, r.candidates, r.feasible, r.improved, r.osqp_iter, sh[(size_t)b].form, 0, 0};
     }
+    if (sb) {
+      TreeSbOut r;
+      memcpy(&r, hs + s.sb, sizeof r);
+      sb->info[b] = miosqp_tree_sb_info{r.calls, r.children, r.osqp_iter, sh[(size_t)b].form, 0, 0, 0, 0};
+    }
   }
-  stats->launches = (P.n1 ? 1 : 0) + (P.n2 ? 1 : 0) + (P.n3 ? 1 : 0) + (P.n4 ? 1 : 0) + (P.n5 ? 1 : 0);
+  stats->launches = (P.n1 ? 1 : 0) + (P.n2 ? 1 : 0) + (P.n3 ? 1 : 0) + (P.n4 ? 1 : 0) + (P.n5 ? 1 : 0) + (P.n6 ? 1 : 0) + (P.n7 ? 1 : 0);
   stats->models_wave = P.n1;
   stats->models_group = P.n2;
   stats->pad = P.n3;  // (models run by the reduced form: 0 unless the call came through miosqp_qp_solve_trees_models_large)
-  stats->lds_bytes = (int64_t)std::max(std::max(lds_max, lds_max_r), std::max(lds_max_rf, lds_max_rf_r));
+  stats->lds_bytes = (int64_t)std::max(std::max(std::max(lds_max, lds_max_r), std::max(lds_max_rf, lds_max_rf_r)),
+                                       std::max(lds_max_sb, lds_max_sb_r));
   stats->device_time = 1e-3 * ms;
   stats->run_time = wall_s;
   return 0;

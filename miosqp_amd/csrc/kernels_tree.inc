@@ -24,6 +24,12 @@ struct TreeRfOut {
   int osqp_iter, pad0, pad1, pad2;
 };
 
+// what sb_stats counts, for one tree with strong / reliability branching inside (Workspace.strong_branch)
+struct TreeSbOut {
+  int calls, children, osqp_iter, pad0;
+  int pad1, pad2, pad3, pad4;
+};
+
 struct TreeArgs {
   int rule, max_nodes, max_iter, check_every, TG1, TG2;
   double upper0;
@@ -47,6 +53,14 @@ struct TreeArgs {
   // (0: never fires), their iteration cap, every how many branching nodes; the tree's counters (per instance in a batch)
   int rf_K, rf_max_iter, rf_every;
   TreeRfOut *rf_out;
+  // k_tree_sb, k_tree_sb_m, k_tree_sb_r_m (strong / reliability branching inside the tree, kernels_tree_sb_block.inc):
+  // branching_rule 1 or 2, sb_candidates, the children's iteration cap, sb_reliability, sb_eps; the tree's work area
+  // (tree_sb::work_doubles(n_int) doubles: pseudo-costs, the asking node's candidates and children), Node.pc of every
+  // leaf-store place (tree_sb::PC_DOUBLES each), the tree's counters -- all three per instance in a batch
+  int sb_rule, sb_K, sb_max_iter, sb_rel;
+  double sb_eps;
+  double *sb_work, *sb_pc;
+  TreeSbOut *sb_out;
 };
 
 // workgroup b of a batched launch: the per-instance pointers of Dev and TreeArgs moved to instance b (the staging block
@@ -74,6 +88,17 @@ __device__ __forceinline__ void tree_instance(Dev &d, TreeArgs &ta) {
 // ... and the instance's round-and-fix counters (k_tree_rf)
 __device__ __forceinline__ void tree_instance_rf(Dev &d, TreeArgs &ta) {
   if (ta.batch) ta.rf_out += blockIdx.x;
+  tree_instance(d, ta);
+}
+
+// ... and the instance's work area, Node.pc and counters of strong / reliability branching (k_tree_sb)
+__device__ __forceinline__ void tree_instance_sb(Dev &d, TreeArgs &ta) {
+  if (ta.batch) {
+    const size_t b = blockIdx.x;
+    ta.sb_work += b * miosqp::tree_sb::work_doubles(d.n_int);
+    ta.sb_pc += b * (size_t)TREE_CAP * miosqp::tree_sb::PC_DOUBLES;
+    ta.sb_out += b;
+  }
   tree_instance(d, ta);
 }
 
@@ -179,6 +204,30 @@ __global__ __launch_bounds__(RES_THREADS) void k_tree_rf_m(const TreeModel *__re
 #include "kernels_tree_body.inc"  // the body of k_tree, with round and fix
 }
 #undef TREE_RF
+
+// ------------------------------------------------------------------------------------------
+// The same trees with STRONG or RELIABILITY BRANCHING inside (branching_rule 1 / 2; miosqp_qp_solve_trees_sb,
+// miosqp_qp_solve_trees_models_sb): the body under TREE_SB -- a node that is about to branch chooses its position as
+// Workspace.select_branching does: the workgroup solves the 2K children of its candidates, capped at sb_max_iter
+// iterations, and thread 0 scores them; rule 2 keeps pseudo-costs per tree and solves the unreliable candidates only
+// (kernels_tree_sb_block.inc, tree_sb_logic.hpp).  No LDS beyond k_tree's: the node's xf, yf wait in its place of the
+// leaf store, pseudo-costs, candidates and children's outcomes live in device memory.  Sizes n + M <= 64 run here as
+// well (the workgroup form takes them; there is no wavefront form).
+// ------------------------------------------------------------------------------------------
+#define TREE_SB 1
+__global__ __launch_bounds__(RES_THREADS) void k_tree_sb(Dev d, TreeArgs ta) {
+  extern __shared__ __attribute__((aligned(16))) double sm[];
+  tree_instance_sb(d, ta);
+#include "kernels_tree_body.inc"  // the body of k_tree, with strong / reliability branching
+}
+
+__global__ __launch_bounds__(RES_THREADS) void k_tree_sb_m(const TreeModel *__restrict__ tab) {
+  extern __shared__ __attribute__((aligned(16))) double sm[];
+  const Dev &d = tab[blockIdx.x].d;
+  const TreeArgs &ta = tab[blockIdx.x].ta;
+#include "kernels_tree_body.inc"  // the body of k_tree, with strong / reliability branching
+}
+#undef TREE_SB
 #undef TREE_LIST_CAP
 
 // ------------------------------------------------------------------------------------------
@@ -284,6 +333,16 @@ __global__ __launch_bounds__(RES_THREADS) void k_tree_rf_r_m(const TreeModel *__
 #include "kernels_tree_body.inc"  // the body of k_tree_r_m, with round and fix
 }
 #undef TREE_RF
+
+// ... with strong / reliability branching inside (see k_tree_sb)
+#define TREE_SB 1
+__global__ __launch_bounds__(RES_THREADS) void k_tree_sb_r_m(const TreeModel *__restrict__ tab) {
+  extern __shared__ __attribute__((aligned(16))) double sm[];
+  const Dev &d = tab[blockIdx.x].d;
+  const TreeArgs &ta = tab[blockIdx.x].ta;
+#include "kernels_tree_body.inc"  // the body of k_tree_r_m, with strong / reliability branching
+}
+#undef TREE_SB
 #undef TREE_REDUCED
 #undef TREE_LIST_CAP
 

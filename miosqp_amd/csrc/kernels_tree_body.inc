@@ -2,6 +2,8 @@
 // else): the one body of the kernels.  TREE_LIST_CAP: the leaf list's capacity; TREE_REDUCED (k_tree_r_m): the carve-up, the factor load and the call
 // that runs the relaxation are those of the reduced form -- nothing else differs.  TREE_RF (k_tree_rf, k_tree_rf_m,
 // k_tree_rf_r_m): round and fix on the nodes that are about to branch (kernels_tree_rf_block.inc) -- nothing else differs.
+// TREE_SB (k_tree_sb, k_tree_sb_m, k_tree_sb_r_m): the branching position by strong or reliability branching
+// (kernels_tree_sb_block.inc), the pseudo-cost observation of a node's own solve, and what its children remember.
 // In scope: `sm` (the dynamic LDS block), `d` (Dev) and `ta` (TreeArgs) with final pointers -- kernel arguments moved to
 // the block's instance (k_tree), or references to the block's entry of a table in device memory (k_tree_m).  Everything
 // per block -- shapes, the LDS carve-up, sp_off, lane groupings, search settings, tolerances -- is read from them.
@@ -37,7 +39,7 @@
   int *iiL = reinterpret_cast<int *>(sm + cv.iiL);
 #endif
   // sc[0] upper, sc[1] action, sc[2] slot, sc[3] status, sc[4] lower, sc[5] heur_obj, sc[6] nextvar, sc[7] child0, sc[8] child1
-  // (TREE_RF: sc[15] the candidate just judged is the best so far)
+  // (TREE_RF: sc[15] the candidate just judged is the best so far; TREE_SB: sc[15] candidates whose children are solved)
   const double rinv = d.rho_inv, sigma = d.sigma;
   const int unsolved = MIOSQP_QP_UNSOLVED;
   (void)unsolved;
@@ -74,6 +76,13 @@
   double lower_glob = -1.0 / 0.0;
 #ifdef TREE_RF  // round and fix (kernels_tree_rf_block.inc): nodes that were about to branch, and what rf_stats counts
   int rf_nodes = 0, rf_calls = 0, rf_cand = 0, rf_feas = 0, rf_impr = 0, rf_iter = 0;
+#endif
+#ifdef TREE_SB  // strong / reliability branching (kernels_tree_sb_block.inc): what sb_stats counts
+  int sb_calls = 0, sb_children = 0, sb_iter = 0;
+  if (tid == 0) {  // the tree's pseudo-costs start empty, the root was made by no branching
+    miosqp::tree_sb::start(miosqp::tree_sb::view(ta.sb_work, p));
+    ta.sb_pc[3] = -1.0;
+  }
 #endif
   if (tid == 0) {
     order[0] = 0;
@@ -267,6 +276,9 @@
       if (ok) {
         lower = w_lower; hobj = w_hobj; hviol = w_hviol; int_inf = w_intinf; nextvar = w_next;
       }
+#ifdef TREE_SB  // Node.pc, read at the top of bound_and_branch: before the infeasible and pruned returns
+      miosqp::tree_sb::node_solved(miosqp::tree_sb::view(ta.sb_work, p), ta.sb_pc, slot, ok, lower);
+#endif
       bool prune_now = false;
       if (ok && !(lower > upper)) {
         if (int_inf == 0) {
@@ -310,6 +322,21 @@
       const double lower = sc[4];
       const int nextvar = (int)sc[6];
 #endif
+#ifdef TREE_SB
+      // Workspace.select_branching sits here, where the node picks its position: thread 0's block is closed around it
+      // (the whole workgroup solves the children) and opened again with its values
+      sc[0] = upper;
+      sc[1] = (double)action;
+      sc[4] = lower;
+      sc[6] = (double)nextvar;
+    }
+#include "kernels_tree_sb_block.inc"
+    if (tid == 0) {
+      double upper = sc[0];
+      const int action = (int)sc[1] & 4;  // (the block has written the node's own incumbent)
+      const double lower = sc[4];
+      const int nextvar = (int)sc[6];
+#endif
       int c0 = -1, c1 = -1;
       if (action & 4) {
         if (nfree < 2 || count + 2 > TREE_LIST_CAP) {
@@ -322,6 +349,10 @@
           lf_lower[c0] = lf_lower[c1] = lower;
           order[count++] = c0;  // add_left, then add_right
           order[count++] = c1;
+#ifdef TREE_SB  // branch_children: Node.pc of the two children
+          miosqp::tree_sb::branched(miosqp::tree_sb::Par{ta.sb_rule, ta.sb_K, ta.sb_rel, ta.sb_eps, d.eps_int}, ta.sb_pc, c0, c1, nextvar,
+                                    xf[iiL[nextvar]], lower);
+#endif
           double lg = 1.0 / 0.0;
           for (int k = 0; k < count; k++) lg = fmin(lg, lf_lower[order[k]]);
           sc[9] = lg;
@@ -395,5 +426,11 @@
     r->feasible = rf_feas;
     r->improved = rf_impr;
     r->osqp_iter = rf_iter;
+#endif
+#ifdef TREE_SB
+    TreeSbOut *s = ta.sb_out;
+    s->calls = sb_calls;
+    s->children = sb_children;
+    s->osqp_iter = sb_iter;
 #endif
   }

@@ -7,6 +7,8 @@
 #include <string>
 #include <vector>
 
+#include "tree_sb_logic.hpp"  // the size of a tree's work area under strong / reliability branching
+
 namespace miosqp {
 namespace models {
 
@@ -63,12 +65,53 @@ inline int check_args(int32_t B, const void *const *engines, const int *M, const
 struct Shape {
   int n, M, p;  // variables, rows (general + integer), integer variables
   int form;     // 1: one wavefront, 2: one workgroup, 3: one workgroup in reduced form (miosqp_qp_solve_trees_models_large);
-                // with round and fix inside (miosqp_qp_solve_trees_models_rf) 4: one workgroup, 5: the reduced form
+                // with round and fix inside (miosqp_qp_solve_trees_models_rf) 4: one workgroup, 5: the reduced form;
+                // with strong / reliability branching inside (miosqp_qp_solve_trees_models_sb) 6: one workgroup, 7: reduced
 };
 
 constexpr size_t RF_DOUBLES = 4;  // room of one round-and-fix record (TreeRfOut: 32 bytes)
 
-inline bool reduced_form(int form) { return form == 3 || form == 5; }
+constexpr size_t SB_DOUBLES = 4;  // room of one strong-branching record (TreeSbOut: 32 bytes)
+
+inline bool reduced_form(int form) { return form == 3 || form == 5 || form == 7; }
+
+// what miosqp_qp_solve_trees_models_sb checks beyond check_args: per model the branching rule (0: the most-fractional
+// rule, the model runs as without the entry; 1 strong, 2 reliability branching), and for the models with a rule
+// sb_candidates in 1..32, sb_max_iter >= 1, sb_reliability >= 0 and sb_eps > 0.  rule_min: 0 there, 1 for
+// miosqp_qp_solve_trees_sb (one model, `who` names the entry).
+inline int check_sb(int32_t B, const int32_t *rule, const int32_t *sb_candidates, const int32_t *sb_max_iter,
+                    const int32_t *sb_reliability, const double *sb_eps, const void *sb_info, int rule_min, const std::string &who,
+                    std::string &err) {
+  if (!rule || !sb_candidates || !sb_max_iter || !sb_reliability || !sb_eps || !sb_info) {
+    err = who + ": a NULL argument";
+    return ERR_ARG;
+  }
+  for (int b = 0; b < B; b++) {
+    const std::string of = " of model " + std::to_string(b);
+    if (rule[b] < rule_min || rule[b] > 2) {
+      err = who + ": branching_rule " + std::to_string(rule[b]) + of + " is outside " + std::to_string(rule_min) + "..2";
+      return ERR_ARG;
+    }
+    if (rule[b] == 0) continue;
+    if (sb_candidates[b] < 1 || sb_candidates[b] > tree_sb::MAX_K) {
+      err = who + ": sb_candidates " + std::to_string(sb_candidates[b]) + of + " is outside 1.." + std::to_string(tree_sb::MAX_K);
+      return ERR_ARG;
+    }
+    if (sb_max_iter[b] < 1) {
+      err = who + ": sb_max_iter" + of + " must be at least 1";
+      return ERR_ARG;
+    }
+    if (sb_reliability[b] < 0) {
+      err = who + ": sb_reliability" + of + " must not be negative";
+      return ERR_ARG;
+    }
+    if (!(sb_eps[b] > 0.0)) {
+      err = who + ": sb_eps" + of + " must be positive";
+      return ERR_ARG;
+    }
+  }
+  return 0;
+}
 
 // what miosqp_qp_solve_trees_models_rf checks beyond check_args: per model the candidates per call (0: the heuristic is
 // off for that model), their iteration cap and every how many branching nodes.  K_min: 0 there, 1 for
@@ -115,6 +158,10 @@ struct Slot {
   size_t rf;         // the round-and-fix record (rf_doubles, behind the outcome; 0 without one): uploaded and downloaded
   size_t q;          // the scaled cost (n)
   size_t lf_lo, lf_hi, lf_x, lf_y;  // the leaf store: cap x p, cap x p, cap x n, cap x M
+  // strong / reliability branching (0 without): the record (sb_doubles, behind the outcome and the round-and-fix record:
+  // uploaded and downloaded); for a model of form 6 or 7 the tree's work area (tree_sb::work_doubles(p)) and Node.pc of
+  // every leaf-store place (cap x tree_sb::PC_DOUBLES), behind its leaf store
+  size_t sb = 0, sb_work = 0, sb_pc = 0;
 };
 
 // [ table | raw, qraw of every model | inc, out of every model | q and leaf store of every model ]: the first three parts
@@ -124,6 +171,9 @@ struct Slot {
 // (n5 entries) --, each group in the caller's order.  The leaf store of a model has `tree_cap` places, that of a
 // reduced-form model `leaf_cap_r`.  rf_doubles > 0 (miosqp_qp_solve_trees_models_rf): every model's outcome is followed by
 // a round-and-fix record of that many doubles; with 0, and no model of form 4 or 5, the layout is what it was without them.
+// The two groups with strong / reliability branching inside follow (n6 workgroup, n7 reduced form); sb_doubles > 0
+// (miosqp_qp_solve_trees_models_sb): every model's outcome is followed by a record of that many doubles, and the leaf
+// store of a model of form 6 or 7 by its work area and Node.pc; with 0 and no such model the layout is what it was.
 struct Plan {
   std::vector<Slot> slot;
   int n1 = 0, n2 = 0, n3 = 0, n4 = 0, n5 = 0;
@@ -131,18 +181,23 @@ struct Plan {
   size_t up_doubles = 0;               // what the host stages and uploads: [0, up_doubles)
   size_t down_off = 0, down_doubles = 0;  // what comes back
   size_t total_doubles = 0;
+  int n6 = 0, n7 = 0;
 };
 
 inline size_t round_up(size_t v, size_t to) { return (v + to - 1) / to * to; }
 
-inline Plan plan(const std::vector<Shape> &sh, size_t entry_bytes, size_t tree_cap, size_t leaf_cap_r = 0, size_t rf_doubles = 0) {
+inline Plan plan(const std::vector<Shape> &sh, size_t entry_bytes, size_t tree_cap, size_t leaf_cap_r = 0, size_t rf_doubles = 0,
+                 size_t sb_doubles = 0) {
   Plan P;
   const size_t B = sh.size();
   P.slot.resize(B);
-  for (const Shape &s : sh) (s.form == 1 ? P.n1 : s.form == 3 ? P.n3 : s.form == 4 ? P.n4 : s.form == 5 ? P.n5 : P.n2)++;
-  int k1 = 0, k2 = P.n1, k3 = P.n1 + P.n2, k4 = k3 + P.n3, k5 = k4 + P.n4;
-  for (size_t b = 0; b < B; b++)
-    P.slot[b].entry = sh[b].form == 1 ? k1++ : sh[b].form == 3 ? k3++ : sh[b].form == 4 ? k4++ : sh[b].form == 5 ? k5++ : k2++;
+  for (const Shape &s : sh)
+    (s.form == 1 ? P.n1 : s.form == 3 ? P.n3 : s.form == 4 ? P.n4 : s.form == 5 ? P.n5 : s.form == 6 ? P.n6 : s.form == 7 ? P.n7 : P.n2)++;
+  int k1 = 0, k2 = P.n1, k3 = P.n1 + P.n2, k4 = k3 + P.n3, k5 = k4 + P.n4, k6 = k5 + P.n5, k7 = k6 + P.n6;
+  for (size_t b = 0; b < B; b++) {
+    const int f = sh[b].form;
+    P.slot[b].entry = f == 1 ? k1++ : f == 3 ? k3++ : f == 4 ? k4++ : f == 5 ? k5++ : f == 6 ? k6++ : f == 7 ? k7++ : k2++;
+  }
   P.table_doubles = round_up((B * entry_bytes + 7) / 8, 32);
   size_t at = P.table_doubles;
   for (size_t b = 0; b < B; b++) {
@@ -161,6 +216,8 @@ inline Plan plan(const std::vector<Shape> &sh, size_t entry_bytes, size_t tree_c
     at += OUT_DOUBLES;
     P.slot[b].rf = rf_doubles ? at : 0;
     at += rf_doubles;
+    P.slot[b].sb = sb_doubles ? at : 0;
+    at += sb_doubles;
   }
   P.down_doubles = at - P.down_off;
   P.up_doubles = at;
@@ -178,6 +235,13 @@ inline Plan plan(const std::vector<Shape> &sh, size_t entry_bytes, size_t tree_c
     at += cap * n;
     P.slot[b].lf_y = at;
     at += cap * M;
+    if (sh[b].form == 6 || sh[b].form == 7) {
+      at = round_up(at, 2);
+      P.slot[b].sb_work = at;
+      at += tree_sb::work_doubles(sh[b].p);
+      P.slot[b].sb_pc = at;
+      at += cap * (size_t)tree_sb::PC_DOUBLES;
+    }
   }
   P.total_doubles = at;
   return P;
@@ -191,7 +255,8 @@ inline int check_arena(const Plan &P, const std::vector<Shape> &sh, size_t tree_
   size_t b = 0;
   for (; b + 1 < sh.size(); b++) {
     const size_t cap = reduced_form(sh[b].form) ? leaf_cap_r : tree_cap;
-    if (P.slot[b].lf_y + cap * (size_t)sh[b].M > limit_doubles) break;
+    const size_t end = P.slot[b].sb_pc ? P.slot[b].sb_pc + cap * (size_t)tree_sb::PC_DOUBLES : P.slot[b].lf_y + cap * (size_t)sh[b].M;
+    if (end > limit_doubles) break;
   }
   err = "solve_trees_models_large: the arena of the call (" + std::to_string(P.total_doubles * sizeof(double)) +
         " bytes) is beyond what the device pool can give (" + std::to_string(limit_doubles * sizeof(double)) +

@@ -79,7 +79,7 @@ def _f64(a, size, name):
     return a
 
 
-def solve_trees_models(solvers, q, l, u, x0, y0, upper0, x_inc0, rules, max_iter_bb, leaf_cap=None, rf=None):
+def solve_trees_models(solvers, q, l, u, x0, y0, upper0, x_inc0, rules, max_iter_bb, leaf_cap=None, rf=None, sb=None):
     """One MIQP on each of B DIFFERENT engines, every tree in one launch per kernel form (miosqp_qp_solve_trees_models):
     model b is what `solvers[b].solve_trees(q[b][None], ...)` solves, bit for bit.  Lists of per-model arrays (q, x0: n_b;
     l, u, y0: M_b), upper0: B incumbent values (inf: none), x_inc0: per model an array or None, rules / max_iter_bb: per
@@ -98,9 +98,20 @@ def solve_trees_models(solvers, q, l, u, x0, y0, upper0, x_inc0, rules, max_iter
     `Workspace.primal_heuristic` inside its tree, as `solvers[b].solve_trees_rf(q[b][None], ...)` runs it, in up to two
     more launches (the workgroup form, which takes the wave-sized models too, and with leaf_cap the reduced form).
     Returns ([x_b], [TreeInfo], stats, [TreeRfInfo]): per model calls, candidates, feasible, improved, osqp_iter and form
-    (1 wave, 2 group, 3 reduced, 4 group with round and fix, 5 reduced with it)."""
+    (1 wave, 2 group, 3 reduced, 4 group with round and fix, 5 reduced with it).
+
+    sb (None: the calls above, exactly; not together with `rf`): one entry per model, None (the most-fractional rule for
+    that model: it goes into the launch it goes into without `sb`, with that result bit for bit) or (branching_rule 1 or
+    2, sb_candidates 1..32, sb_max_iter >= 1, sb_reliability >= 0, sb_eps > 0) -- the call goes to
+    miosqp_qp_solve_trees_models_sb, where such a model chooses its branching positions as `Workspace.select_branching`
+    does, as `solvers[b].solve_trees_sb(q[b][None], ...)` runs it, in up to two more launches (the workgroup form, which
+    takes the wave-sized models too, and with leaf_cap the reduced form).  Returns ([x_b], [TreeInfo], stats,
+    [TreeSbInfo]): per model calls, children, osqp_iter and form (1 wave, 2 group, 3 reduced, 6 group with the rule,
+    7 reduced with it)."""
     B = len(solvers)
-    if rf is not None and len(rf) != B:
+    if rf is not None and sb is not None:
+        raise ValueError("solve_trees_models: rf or sb, not both in one call")
+    if (rf is not None and len(rf) != B) or (sb is not None and len(sb) != B):
         raise ValueError("solve_trees_models: one entry per model in every list")
     if leaf_cap is not None and int(leaf_cap) < 2:
         raise ValueError("solve_trees_models: leaf_cap must be at least 2")
@@ -137,6 +148,15 @@ def solve_trees_models(solvers, q, l, u, x0, y0, upper0, x_inc0, rules, max_iter
                                                  _lib.as_i(rl), _lib.as_i(mi), 0 if leaf_cap is None else int(leaf_cap),
                                                  _lib.as_i(rk), _lib.as_i(ri), _lib.as_i(re), ptrs(x), infos, rfs,
                                                  C.byref(stats))
+    elif sb is not None:
+        par = [(0, 1, 1, 0, 1.0) if r is None else r for r in sb]
+        sr, sk, si, sl = (np.array([int(r[c]) for r in par], dtype=np.int32).reshape(B) for c in range(4))
+        se = np.array([float(r[4]) for r in par], dtype=np.float64).reshape(B)
+        rfs = (_lib.TreeSbInfo * max(B, 1))()
+        rc = lib.miosqp_qp_solve_trees_models_sb(B, hs, ptrs(q), ptrs(l), ptrs(u), ptrs(x0), ptrs(y0), _lib.as_d(up), ptrs(xin),
+                                                 _lib.as_i(rl), _lib.as_i(mi), 0 if leaf_cap is None else int(leaf_cap),
+                                                 _lib.as_i(sr), _lib.as_i(sk), _lib.as_i(si), _lib.as_i(sl), _lib.as_d(se),
+                                                 ptrs(x), infos, rfs, C.byref(stats))
     elif leaf_cap is None:
         rc = lib.miosqp_qp_solve_trees_models(B, hs, ptrs(q), ptrs(l), ptrs(u), ptrs(x0), ptrs(y0), _lib.as_d(up), ptrs(xin),
                                               _lib.as_i(rl), _lib.as_i(mi), ptrs(x), infos, C.byref(stats))
@@ -753,6 +773,38 @@ class OSQP(object):
         if rc == 1:
             raise ValueError("Lower bound must be lower than or equal to upper bound")
         return x, list(infos), list(rfs)
+
+    def solve_trees_sb(self, q, l, u, x0, y0, upper0, x_inc0, tree_explor_rule, max_iter_bb, branching_rule, sb_candidates,
+                       sb_max_iter, sb_reliability, sb_eps):
+        """`solve_trees` with strong (branching_rule 1) or reliability branching (2) inside every tree
+        (miosqp_qp_solve_trees_sb, `Workspace.select_branching`): a node that is about to branch has its workgroup solve
+        the 2K children of its candidates, at most sb_max_iter iterations each, and branches on the position the rule
+        picks; rule 2 keeps pseudo-costs per tree, starting empty.  One workgroup per instance, also for n + M <= 64.
+        sb_candidates in 1..32, sb_max_iter >= 1, sb_reliability >= 0, sb_eps > 0 (RuntimeError with the library's text
+        otherwise).  Returns (x B x n, [TreeInfo], [TreeSbInfo]) -- TreeInfo.osqp_iter counts the nodes' iterations,
+        TreeSbInfo has calls, children, osqp_iter per instance -- or None when the engine does not cover this size."""
+        q = np.ascontiguousarray(q, dtype=np.float64)
+        B = q.shape[0]
+        l, u = np.ascontiguousarray(l, dtype=np.float64), np.ascontiguousarray(u, dtype=np.float64)
+        x0, y0 = np.ascontiguousarray(x0, dtype=np.float64), np.ascontiguousarray(y0, dtype=np.float64)
+        if q.shape != (B, self.n) or x0.shape != (B, self.n) or l.shape != (B, self.m) or u.shape != (B, self.m) or y0.shape != (B, self.m):
+            raise ValueError("solve_trees_sb: instance-major arrays (B x n, B x M)")
+        up = np.minimum(np.ascontiguousarray(upper0, dtype=np.float64).reshape(B), 1.7e308)
+        xin = None if x_inc0 is None else np.ascontiguousarray(x_inc0, dtype=np.float64).reshape(B, self.n)
+        x = np.zeros((B, self.n))
+        infos = (_lib.TreeInfo * B)()
+        sbs = (_lib.TreeSbInfo * B)()
+        max_iter_bb = 2 ** 31 - 1 if not np.isfinite(max_iter_bb) else int(min(int(max_iter_bb), 2 ** 31 - 1))
+        rc = self._lib.miosqp_qp_solve_trees_sb(self._h, B, _lib.as_d(q), _lib.as_d(l), _lib.as_d(u), _lib.as_d(x0),
+                                                _lib.as_d(y0), _lib.as_d(up), None if xin is None else _lib.as_d(xin),
+                                                int(tree_explor_rule), max_iter_bb, int(branching_rule), int(sb_candidates),
+                                                int(sb_max_iter), int(sb_reliability), float(sb_eps), _lib.as_d(x), infos, sbs)
+        if rc == -5:
+            return None
+        _check(rc, "solve_trees_sb")
+        if rc == 1:
+            raise ValueError("Lower bound must be lower than or equal to upper bound")
+        return x, list(infos), list(sbs)
 
     def tree_form(self):
         """Which one-launch tree kernel takes this engine (miosqp_qp_tree_form): 0 none -- `solve_trees` would return
