@@ -571,6 +571,51 @@ int miosqp_qp_solve_trees_models_sb(int32_t B, miosqp_qp_engine *const *engines,
                                     const double *sb_eps, double *const *x_out, miosqp_tree_info *info,
                                     miosqp_tree_sb_info *sb_info, miosqp_models_stats *stats);
 
+/* ---- many MIQPs on ONE model beyond one workgroup's product form (opt-in) -----------------------------
+ * miosqp_qp_solve_trees for an engine whose miosqp_qp_tree_form is 0 and whose miosqp_qp_tree_form_large(e, leaf_cap) is
+ * 3: B MIQPs that share P, A (the factor) and differ in q, l, u, warm start and incumbent, workgroup b running tree b in
+ * the reduced form with a leaf list of leaf_cap places -- arguments and layouts as miosqp_qp_solve_trees.  It replaces,
+ * for such a model, what the reference does one MIQP after the other (update_vectors + solve per instance,
+ * miosqp/solver.py:174-212) and what this library offered so far: miosqp_qp_solve_trees_lockstep (a batch per wave of
+ * nodes), or miosqp_qp_solve_trees_models_large over B separately set-up copies of the model (that entry refuses an engine
+ * listed twice).  Everything read per model -- the rows the triangle of L^-1 is loaded from, the packed and dense rows of
+ * Abar, Pbar's rows, D, E, c -- is the engine's own and shared by all workgroups; per instance the call keeps
+ * leaf_cap x (2 n_int + n + M) doubles of leaf store, the staging block, q, the incumbent and the outcome in an arena of
+ * the engine (miosqp_amd/csrc/trees_large_plan.hpp).  Instance b comes out bit for bit as
+ * miosqp_qp_solve_trees_models_large(1, &e, ..., leaf_cap, ...) gives it alone, whatever B is.
+ * One upload, the cost scaling, one tree launch, one download, one synchronisation.
+ * Refused before anything is queued: what miosqp_qp_solve_trees refuses (MIOSQP_EARG); leaf_cap < 2 (MIOSQP_EARG); an
+ * engine with miosqp_qp_tree_form_large(e, leaf_cap) != 3 -- one of form 1 or 2 keeps miosqp_qp_solve_trees --
+ * (MIOSQP_EUNSUPPORTED); l > u in a root (MIOSQP_EBOUNDS); arrays whose size does not fit an address, or beyond what
+ * hipMemGetInfo leaves on the device (MIOSQP_EARG, the text names B and the bytes; no allocation is tried).
+ * info[b].overflow: the tree needed more than leaf_cap leaves at once and stopped; the caller redoes that instance. */
+int miosqp_qp_solve_trees_large(miosqp_qp_engine *e, int32_t B, const double *q, const double *l, const double *u,
+                                const double *x0, const double *y0, const double *upper0, const double *x_inc0,
+                                int32_t tree_explor_rule, int32_t max_iter_bb, int32_t leaf_cap, double *x_out,
+                                miosqp_tree_info *info);
+
+/* miosqp_qp_solve_trees_large with round and fix in every tree: miosqp_qp_solve_trees_rf for such an engine (it replaces
+ * miosqp_qp_solve_trees_lockstep_rf there, or miosqp_qp_solve_trees_models_rf over copies of the model).  rf_candidates in
+ * 1..32, rf_max_iter >= 1, rf_every >= 1 (MIOSQP_EARG otherwise, before anything is queued); rf_info B records, per
+ * instance (form 5), equal to those of miosqp_qp_solve_trees_models_rf for the instance alone. */
+int miosqp_qp_solve_trees_large_rf(miosqp_qp_engine *e, int32_t B, const double *q, const double *l, const double *u,
+                                   const double *x0, const double *y0, const double *upper0, const double *x_inc0,
+                                   int32_t tree_explor_rule, int32_t max_iter_bb, int32_t leaf_cap, int32_t rf_candidates,
+                                   int32_t rf_max_iter, int32_t rf_every, double *x_out, miosqp_tree_info *info,
+                                   miosqp_tree_rf_info *rf_info);
+
+/* miosqp_qp_solve_trees_large with strong (1) or reliability branching (2) in every tree: miosqp_qp_solve_trees_sb for such
+ * an engine (it replaces miosqp_qp_solve_trees_lockstep_sb there, or miosqp_qp_solve_trees_models_sb over copies of the
+ * model).  branching_rule 1 or 2, sb_candidates in 1..32, sb_max_iter >= 1, sb_reliability >= 0, sb_eps > 0 (MIOSQP_EARG
+ * otherwise, before anything is queued); per instance the arena also holds the rule's work area and leaf_cap x 4 doubles
+ * of Node.pc; sb_info B records, per instance (form 7), equal to those of miosqp_qp_solve_trees_models_sb for the
+ * instance alone. */
+int miosqp_qp_solve_trees_large_sb(miosqp_qp_engine *e, int32_t B, const double *q, const double *l, const double *u,
+                                   const double *x0, const double *y0, const double *upper0, const double *x_inc0,
+                                   int32_t tree_explor_rule, int32_t max_iter_bb, int32_t leaf_cap, int32_t branching_rule,
+                                   int32_t sb_candidates, int32_t sb_max_iter, int32_t sb_reliability, double sb_eps,
+                                   double *x_out, miosqp_tree_info *info, miosqp_tree_sb_info *sb_info);
+
 /* ---- polishes of DIFFERENT models in one launch -------------------------------------------------------
  * The polish of the "own P and A per MIQP" pattern: the reference sets up, solves and polishes one model per MIQP
  * (miosqp/solver.py:174-212 per model; `polish` reaches OSQP through qp_settings, miosqp/workspace.py:67-68), and

@@ -197,6 +197,14 @@ SYMBOLS = {
     "miosqp_qp_solve_trees_models_sb": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), dpp, dpp, dpp, dpp, dpp, dp, dpp, ip, ip,
                                                   C.c_int32, ip, ip, ip, ip, dp, dpp, C.POINTER(TreeInfo), C.POINTER(TreeSbInfo),
                                                   C.POINTER(ModelsStats)]),
+    "miosqp_qp_solve_trees_large": (C.c_int, [C.c_void_p, C.c_int32, dp, dp, dp, dp, dp, dp, dp, C.c_int32, C.c_int32, C.c_int32,
+                                              dp, C.POINTER(TreeInfo)]),
+    "miosqp_qp_solve_trees_large_rf": (C.c_int, [C.c_void_p, C.c_int32, dp, dp, dp, dp, dp, dp, dp, C.c_int32, C.c_int32,
+                                                 C.c_int32, C.c_int32, C.c_int32, C.c_int32, dp, C.POINTER(TreeInfo),
+                                                 C.POINTER(TreeRfInfo)]),
+    "miosqp_qp_solve_trees_large_sb": (C.c_int, [C.c_void_p, C.c_int32, dp, dp, dp, dp, dp, dp, dp, C.c_int32, C.c_int32,
+                                                 C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, dp,
+                                                 C.POINTER(TreeInfo), C.POINTER(TreeSbInfo)]),
     "miosqp_qp_polish_models": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), dpp, dpp, dpp, dpp, dpp, C.c_double, dp, ip, ip, dpp,
                                           dpp, C.POINTER(C.c_void_p), C.POINTER(PolishRepairInfo), C.POINTER(PolishModelsStats)]),
     "miosqp_qp_polish_models_fits": (C.c_int, [C.c_void_p]),

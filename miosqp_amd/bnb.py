@@ -26,6 +26,7 @@ from __future__ import print_function
 
 from time import time
 
+import inspect
 import types
 
 import numpy as np
@@ -1253,7 +1254,7 @@ class MIOSQP(object):
                 res['polished'] = True
         return results
 
-    def solve_many(self, instances, polish=False, lockstep=None, ahead=8, *, heuristic=None, branching=None):
+    def solve_many(self, instances, polish=False, lockstep=None, ahead=8, *, heuristic=None, branching=None, **large_options):
         """B MIQPs on this model's factorisation, solved TOGETHER: instance k is what
         `update_vectors(q=, l=, u=)` [+ `set_x0(x0)`] + `solve()` would solve (the reference's MPC pattern,
         /root/reference/miosqp/solver.py:174-212, examples/power_converter/power_converter.py:467-476), for a list of
@@ -1350,11 +1351,31 @@ class MIOSQP(object):
         launch.  The rules do not shrink these trees by much.  Measured (profiles/solve_trees_sb.txt): against
         the same call without the keyword 1.2-1.6 x at one instance, 6-10 x at 8 and 88-167 x at 256 instances of
         (40,60,20) and (50,100,10); against branching_rule 0 in the one-launch trees it LOSES everywhere, 0.13-0.52 x
-        the MIQPs/s."""
+        the MIQPs/s.
+
+        Two further keywords, `large` and `leaf_cap`, are taken by name only (any other name is a TypeError).
+        large=None (the default): as above -- a model beyond the one-launch trees (`tree_form()` 0: n + M > 192, or more
+        than 160 KB of LDS) goes to the lock-step drivers or the sequential path.
+        large="device": where the one-launch attempt would be made at all (the settings above, device_tree, the device
+        digest), `tree_form()` is 0 and the engine's `tree_form_large(leaf_cap)` is 3, every tree runs in ONE launch in
+        the reduced form (`OSQP.solve_trees_large`, miosqp_qp_solve_trees_large): one workgroup per instance, the packed
+        triangle of L^-1 in LDS, a leaf list of leaf_cap places (an int >= 2, 256 by default), the model's factor, Abar
+        and scalings read by all workgroups from the engine's one copy.  Instance k is bit for bit what
+        `solve_models([model], [instances[k]], large="device")` gives.  With heuristic="device" and primal_heuristic 1
+        the entry is `OSQP.solve_trees_large_rf`, with branching="device" and branching_rule 1 or 2
+        `OSQP.solve_trees_large_sb` (`work.trees_rf` / `work.trees_sb` as above); a rule together with the heuristic, or
+        either one without its keyword, makes no large attempt.  Trees that overflow leaf_cap, and a decline, go on as
+        `lockstep` says; `work.trees_info` holds the infos.  With `tree_form()` not 0 the keyword changes nothing; a
+        backend without the entry (the CPU oracle) ignores it; any other value, and a leaf_cap that is not an int >= 2,
+        raise ValueError before any launch.  `leaf_cap` is read by this path alone.  Measured
+        (profiles/solve_many_large.txt) on the four large grid shapes against the same call without the
+        keyword: 5.0-10.3 x at 256 instances, 1.3-3.2 x at 64, 0.68-1.46 x at one; it LOSES at (150,300,20) below 64
+        instances."""
         if not (polish is False or polish is True or (isinstance(polish, str) and polish == "device")):
             raise ValueError('solve_many: polish must be False, True or "device"')
         _heuristic_keyword(heuristic, 'solve_many')
         _branching_keyword(branching, 'solve_many')
+        large, leaf_cap = _large_options(large_options, 'solve_many')
         work, data, st = self.work, self.work.data, self.work.settings
         require_plain_search(st, "solve_many", rule=False, heuristic=False)
         B = len(instances)
@@ -1366,6 +1387,7 @@ class MIOSQP(object):
                         and hasattr(work.solver, 'tree_form') and work.solver.tree_form() != 0)
         in_launch_sb = (branching == "device" and st['branching_rule'] in (1, 2) and one_launch_trees_ok(work, sb=True)
                         and hasattr(work.solver, 'tree_form') and work.solver.tree_form() != 0)
+        in_large = _large_entry(work, large, heuristic, branching, leaf_cap)  # None, or the entry's name
         Q, L, U = self._instance_vectors(instances)
         up = np.full(B, np.inf); XI = np.zeros((B, n)); any_inc = False
         for k, inst in enumerate(instances):
@@ -1376,9 +1398,23 @@ class MIOSQP(object):
         out = [None] * B
         redo = list(range(B))
         declined = True  # the one-launch path: absent, switched off, or it returned None
-        if ok_engine or in_launch_rf or in_launch_sb:
+        if in_large:
+            in_launch_rf, in_launch_sb = in_large == 'solve_trees_large_rf', in_large == 'solve_trees_large_sb'
+        if ok_engine or in_launch_rf or in_launch_sb or in_large:
             t0 = time()
-            if in_launch_sb:
+            if in_large:
+                args = (Q, L, U, np.zeros((B, n)), np.zeros((B, M)), up, XI if any_inc else None, st['tree_explor_rule'],
+                        st['max_iter_bb'])
+                if in_launch_sb:
+                    sb = work.sb
+                    r = work.solver.solve_trees_large_sb(*args, sb['rule'], sb['K'], sb['max_iter'], sb['reliability'],
+                                                         sb['eps'], leaf_cap=leaf_cap)
+                elif in_launch_rf:
+                    r = work.solver.solve_trees_large_rf(*args, work.rf['K'], work.rf['max_iter'], work.rf['every'],
+                                                         leaf_cap=leaf_cap)
+                else:
+                    r = work.solver.solve_trees_large(*args, leaf_cap=leaf_cap)
+            elif in_launch_sb:
                 sb = work.sb
                 r = work.solver.solve_trees_sb(Q, L, U, np.zeros((B, n)), np.zeros((B, M)), up, XI if any_inc else None,
                                                st['tree_explor_rule'], st['max_iter_bb'], sb['rule'], sb['K'],
@@ -1390,7 +1426,9 @@ class MIOSQP(object):
             else:
                 r = work.solver.solve_trees(Q, L, U, np.zeros((B, n)), np.zeros((B, M)), up, XI if any_inc else None,
                                             st['tree_explor_rule'], st['max_iter_bb'])
-            if r is None:
+            if r is None and in_large:
+                work._no_trees_large = True  # (the small forms' own record stays as it is: they were not asked)
+            elif r is None:
                 work._no_trees = True
             else:
                 X, infos = r[0], r[1]
@@ -1490,6 +1528,13 @@ class MIOSQP(object):
             self.polish_many(instances, out, large=polish == "device")
         return out
 
+    # The declared parameters of solve_many, their order and their defaults are pinned (tests/test_solve_trees_sb_cpu.py,
+    # tests/test_lockstep_ahead_cpu.py): `large` and `leaf_cap` are therefore the two names **large_options takes
+    # (`_large_options`; keyword-only by construction, any other name is a TypeError), and the signature shown is the
+    # declared one -- the docstring lists the two.
+    solve_many.__signature__ = inspect.Signature(
+        [par for par in inspect.signature(solve_many).parameters.values() if par.kind is not inspect.Parameter.VAR_KEYWORD])
+
     def update_vectors(self, q=None, l=None, u=None):
         # solver.py:174-205: same factorisation, new root, statistics reset
         work = self.work
@@ -1523,6 +1568,55 @@ def _sb_counters(rec):
 
 
 _BEYOND_ONE_LAUNCH = 'tree_form 0: beyond the one-launch trees'
+
+
+def _large_options(options, who):
+    """the keyword-only options `large` (None or "device") and `leaf_cap` (an int >= 2; 256) of solve_many, taken from
+    the call's remaining keywords and checked: (large, leaf_cap).  TypeError for any other name, as for a call with an
+    unknown keyword."""
+    options = dict(options)
+    large, leaf_cap = options.pop('large', None), options.pop('leaf_cap', 256)
+    if options:
+        raise TypeError("%s() got an unexpected keyword argument %r" % (who, sorted(options)[0]))
+    if large is not None and not (isinstance(large, str) and large == "device"):
+        raise ValueError('%s: large must be None or "device"' % who)
+    if isinstance(leaf_cap, bool) or not isinstance(leaf_cap, (int, np.integer)) or leaf_cap < 2:
+        raise ValueError('%s: leaf_cap must be an int of at least 2' % who)
+    return large, int(leaf_cap)
+
+
+def _large_entry(work, large, heuristic, branching, leaf_cap):
+    """which entry of the one-launch trees in the reduced form `solve_many(large="device")` calls for this workspace
+    ('solve_trees_large', 'solve_trees_large_rf', 'solve_trees_large_sb'), or None: no keyword, a backend without the
+    entries, settings the one-launch attempt is not made with (a rule or the heuristic without its keyword, both
+    together), an engine another form takes (`tree_form()` not 0) or the reduced form does not (`tree_form_large` not 3),
+    or a decline before.  An earlier decline of the small forms (`_no_trees`: what `solve_many` without the keyword
+    leaves on such an engine) is looked past, as `solve_models` does."""
+    solver, st = work.solver, work.settings
+    if large != "device" or getattr(work, '_no_trees_large', False):
+        return None
+    if not all(hasattr(solver, a) for a in ('solve_trees_large', 'tree_form', 'tree_form_large')):
+        return None
+    rule, rf_on = st['branching_rule'], bool(work.rf['on'])
+    if rule == 0 and not rf_on:
+        name, look = 'solve_trees_large', {}
+    elif rule == 0 and rf_on and heuristic == "device":
+        name, look = 'solve_trees_large_rf', dict(rf=True)
+    elif rule in (1, 2) and not rf_on and branching == "device":
+        name, look = 'solve_trees_large_sb', dict(sb=True)
+    else:
+        return None
+    if not hasattr(solver, name):
+        return None
+    declined = getattr(work, '_no_trees', False)
+    work._no_trees = False
+    try:
+        ok = one_launch_trees_ok(work, **look)
+    finally:
+        work._no_trees = declined
+    if not ok or solver.tree_form() != 0 or solver.tree_form_large(leaf_cap) != 3:
+        return None
+    return name
 
 
 def _heuristic_keyword(heuristic, who):

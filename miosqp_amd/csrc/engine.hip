@@ -49,6 +49,7 @@
 #include "tree_rf_logic.hpp"  // round and fix inside the one-launch trees (k_tree_rf*): when it fires, the fixed value, the pick (plain C++; also run on the CPU under tests/)
 #include "tree_sb_logic.hpp"  // strong / reliability branching inside the one-launch trees (k_tree_sb*): candidates, scores, pseudo-costs, the pick (plain C++; also run on the CPU under tests/)
 #include "models_plan.hpp"  // trees of different models in one launch: argument checks and arena layout (plain C++; host_models.inc drives it)
+#include "trees_large_plan.hpp"  // B trees of one model in the reduced form in one launch: the layout of the batch's arena, overflow-checked (plain C++; host_trees_large.inc drives it)
 #include "lockstep_refill.hpp"  // which tree goes into which free column when the columns are refilled between chunks (plain C++; host_refill.inc drives it)
 
 #define QP_INFTY 1e30
@@ -274,7 +275,7 @@ namespace {
 // the dynamic-LDS ceiling of a kernel is a property of (process, device, kernel): raised to the chip's 160 KB once instead of
 // at every set-up (the call costs ~40 us, a fifth of a small problem's set-up)
 hipError_t lds_limit_once(const void *fn, int which) {
-  static bool done[25][64] = {};  // (one row per kernel: 0 .. 13 as before, 14: k_setup_models, 15: k_setup_models_auto, 16: k_tree_r_m, 17: k_setup_models_large, 18: k_setup_models_large_auto, 19: k_tree_rf, 20: k_tree_rf_m, 21: k_tree_rf_r_m, 22: k_tree_sb, 23: k_tree_sb_m, 24: k_tree_sb_r_m)
+  static bool done[28][64] = {};  // (one row per kernel: 0 .. 13 as before, 14: k_setup_models, 15: k_setup_models_auto, 16: k_tree_r_m, 17: k_setup_models_large, 18: k_setup_models_large_auto, 19: k_tree_rf, 20: k_tree_rf_m, 21: k_tree_rf_r_m, 22: k_tree_sb, 23: k_tree_sb_m, 24: k_tree_sb_r_m, 25: k_tree_r, 26: k_tree_rf_r, 27: k_tree_sb_r)
   int dev = 0;
   hipError_t rc = hipGetDevice(&dev);
   if (rc != hipSuccess) return rc;
@@ -2293,6 +2294,8 @@ static int trees_run(miosqp_qp_engine *e, int32_t B, const double *q, const doub
   e->loop_iters += iters;
   return 0;
 }
+
+#include "host_trees_large.inc"  // B trees of ONE model beyond one workgroup's product form in one launch, in the reduced form (C ABI miosqp_qp_solve_trees_large, _rf, _sb)
 
 int miosqp_qp_solve_trees(miosqp_qp_engine *e, int32_t B, const double *q, const double *l, const double *u,
                           const double *x0, const double *y0, const double *upper0, const double *x_inc0,

@@ -78,6 +78,11 @@ struct miosqp_qp_engine {
   double *tb_sbw = nullptr, *tb_sbpc = nullptr;
   TreeSbOut *tb_sb = nullptr;
   std::vector<TreeSbOut> tb_hsb;
+  // miosqp_qp_solve_trees_large (_rf, _sb): the arena of a batch of trees in the reduced form (trees_large_plan.hpp; from
+  // this engine's pool, capacity in doubles, not shared with tb_*: its leaf stores have leaf_cap places) and its staging
+  double *tl_dev = nullptr;
+  size_t tl_cap = 0;
+  std::vector<double> tl_host;
   // miosqp_qp_solve_trees_models with this engine first: the call's arena (from this engine's pool) and the pinned mirror
   // of its staged part, capacities in doubles
   double *mm_dev = nullptr, *mm_host = nullptr;

@@ -64,8 +64,10 @@ struct TreeArgs {
 };
 
 // workgroup b of a batched launch: the per-instance pointers of Dev and TreeArgs moved to instance b (the staging block
-// raw_l | raw_u | raw_x | raw_y holds 3 M + n doubles per instance; the root bounds of an instance are its l, u)
-__device__ __forceinline__ void tree_instance(Dev &d, TreeArgs &ta) {
+// raw_l | raw_u | raw_x | raw_y holds 3 M + n doubles per instance; the root bounds of an instance are its l, u).
+// cap: places of one instance's leaf store -- TREE_CAP, or ta.leaf_cap for the reduced form (k_tree_r); every product is
+// formed in size_t
+__device__ __forceinline__ void tree_instance(Dev &d, TreeArgs &ta, size_t cap = TREE_CAP) {
   if (!ta.batch) return;
   const size_t b = blockIdx.x, n = d.n, M = d.M, p = d.n_int, blk = 3 * M + n;
   d.q += b * n;
@@ -76,30 +78,30 @@ __device__ __forceinline__ void tree_instance(Dev &d, TreeArgs &ta) {
   d.raw_y += b * blk;
   d.root_l = d.raw_l;
   d.root_u = d.raw_u;
-  ta.lf_lo += b * TREE_CAP * p;
-  ta.lf_hi += b * TREE_CAP * p;
-  ta.lf_x += b * TREE_CAP * n;
-  ta.lf_y += b * TREE_CAP * M;
+  ta.lf_lo += b * cap * p;
+  ta.lf_hi += b * cap * p;
+  ta.lf_x += b * cap * n;
+  ta.lf_y += b * cap * M;
   ta.inc_x += b * n;
   ta.out += b;
   ta.upper0 = ta.upper_b[b];
 }
 
 // ... and the instance's round-and-fix counters (k_tree_rf)
-__device__ __forceinline__ void tree_instance_rf(Dev &d, TreeArgs &ta) {
+__device__ __forceinline__ void tree_instance_rf(Dev &d, TreeArgs &ta, size_t cap = TREE_CAP) {
   if (ta.batch) ta.rf_out += blockIdx.x;
-  tree_instance(d, ta);
+  tree_instance(d, ta, cap);
 }
 
 // ... and the instance's work area, Node.pc and counters of strong / reliability branching (k_tree_sb)
-__device__ __forceinline__ void tree_instance_sb(Dev &d, TreeArgs &ta) {
+__device__ __forceinline__ void tree_instance_sb(Dev &d, TreeArgs &ta, size_t cap = TREE_CAP) {
   if (ta.batch) {
     const size_t b = blockIdx.x;
     ta.sb_work += b * miosqp::tree_sb::work_doubles(d.n_int);
-    ta.sb_pc += b * (size_t)TREE_CAP * miosqp::tree_sb::PC_DOUBLES;
+    ta.sb_pc += b * cap * (size_t)miosqp::tree_sb::PC_DOUBLES;
     ta.sb_out += b;
   }
-  tree_instance(d, ta);
+  tree_instance(d, ta, cap);
 }
 
 __host__ __device__ inline size_t tree_lds_doubles(int n, int M, bool wform) {
@@ -341,6 +343,36 @@ __global__ __launch_bounds__(RES_THREADS) void k_tree_sb_r_m(const TreeModel *__
   const Dev &d = tab[blockIdx.x].d;
   const TreeArgs &ta = tab[blockIdx.x].ta;
 #include "kernels_tree_body.inc"  // the body of k_tree_r_m, with strong / reliability branching
+}
+#undef TREE_SB
+
+// ------------------------------------------------------------------------------------------
+// The batch forms of the three kernels above: B MIQPs on ONE such model (miosqp_qp_solve_trees_large, _rf, _sb), workgroup
+// b runs instance b as in k_tree -- arguments by value, the per-instance pointers moved on by tree_instance with a leaf
+// store of ta.leaf_cap places per instance.  Everything read per model (the triangle's source rows, the packed and dense
+// rows of Abar, Pbar's rows, D, E, c) is the engine's own and shared by all workgroups; only q, the staging block, the
+// leaf store, the incumbent, the outcome and the rf / sb areas are per instance.  The body, its LDS and its sums are those
+// of the _m kernels: an instance comes out bit for bit as k_tree_r_m gives it alone.
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(RES_THREADS) void k_tree_r(Dev d, TreeArgs ta) {
+  extern __shared__ __attribute__((aligned(16))) double sm[];
+  tree_instance(d, ta, (size_t)ta.leaf_cap);
+#include "kernels_tree_body.inc"  // the body of k_tree_r_m
+}
+
+#define TREE_RF 1
+__global__ __launch_bounds__(RES_THREADS) void k_tree_rf_r(Dev d, TreeArgs ta) {
+  extern __shared__ __attribute__((aligned(16))) double sm[];
+  tree_instance_rf(d, ta, (size_t)ta.leaf_cap);
+#include "kernels_tree_body.inc"  // the body of k_tree_rf_r_m
+}
+#undef TREE_RF
+
+#define TREE_SB 1
+__global__ __launch_bounds__(RES_THREADS) void k_tree_sb_r(Dev d, TreeArgs ta) {
+  extern __shared__ __attribute__((aligned(16))) double sm[];
+  tree_instance_sb(d, ta, (size_t)ta.leaf_cap);
+#include "kernels_tree_body.inc"  // the body of k_tree_sb_r_m
 }
 #undef TREE_SB
 #undef TREE_REDUCED

@@ -821,6 +821,72 @@ class OSQP(object):
             return 0
         return int(self._lib.miosqp_qp_tree_form_large(self._h, int(leaf_cap)))
 
+    def _trees_large_args(self, who, q, l, u, x0, y0, upper0, x_inc0, tree_explor_rule, max_iter_bb, leaf_cap):
+        """the arrays of solve_trees, checked and laid out, for the three entries of solve_trees_large"""
+        q = np.ascontiguousarray(q, dtype=np.float64)
+        B = q.shape[0]
+        l, u = np.ascontiguousarray(l, dtype=np.float64), np.ascontiguousarray(u, dtype=np.float64)
+        x0, y0 = np.ascontiguousarray(x0, dtype=np.float64), np.ascontiguousarray(y0, dtype=np.float64)
+        if q.shape != (B, self.n) or x0.shape != (B, self.n) or l.shape != (B, self.m) or u.shape != (B, self.m) or y0.shape != (B, self.m):
+            raise ValueError("%s: instance-major arrays (B x n, B x M)" % who)
+        if isinstance(leaf_cap, bool) or int(leaf_cap) != leaf_cap or leaf_cap < 2:
+            raise ValueError("%s: leaf_cap must be an integer of at least 2" % who)
+        up = np.minimum(np.ascontiguousarray(upper0, dtype=np.float64).reshape(B), 1.7e308)
+        xin = None if x_inc0 is None else np.ascontiguousarray(x_inc0, dtype=np.float64).reshape(B, self.n)
+        max_iter_bb = 2 ** 31 - 1 if not np.isfinite(max_iter_bb) else int(min(int(max_iter_bb), 2 ** 31 - 1))
+        keep = (q, l, u, x0, y0, up, xin)  # (the arrays behind the pointers live as long as the call)
+        head = (self._h, B, _lib.as_d(q), _lib.as_d(l), _lib.as_d(u), _lib.as_d(x0), _lib.as_d(y0), _lib.as_d(up),
+                None if xin is None else _lib.as_d(xin), int(tree_explor_rule), max_iter_bb, int(leaf_cap))
+        return types.SimpleNamespace(B=B, head=head, keep=keep, x=np.zeros((B, self.n)), infos=(_lib.TreeInfo * B)())
+
+    def _trees_large_done(self, who, rc, *ret):
+        if rc == -5:
+            return None
+        _check(rc, who)
+        if rc == 1:
+            raise ValueError("Lower bound must be lower than or equal to upper bound")
+        return tuple(ret)
+
+    def solve_trees_large(self, q, l, u, x0, y0, upper0, x_inc0, tree_explor_rule, max_iter_bb, leaf_cap=256):
+        """`solve_trees` for an engine BEYOND one workgroup's product form (miosqp_qp_solve_trees_large): `tree_form()` is 0
+        and `tree_form_large(leaf_cap)` is 3.  B MIQPs on this engine's factor, every tree in one launch, one workgroup
+        per instance in the reduced form (the packed triangle of L^-1 in LDS) with a leaf list of leaf_cap places (an int
+        >= 2; ValueError otherwise); the factor, Abar and the scalings are read by all workgroups from the engine's own
+        arrays.  Arrays and return as `solve_trees`: (x B x n, [TreeInfo]) -- instance b bit for bit what
+        `solve_trees_models([self], ..., leaf_cap=leaf_cap)` gives it alone; TreeInfo.overflow marks a tree that needed
+        more than leaf_cap leaves at once -- or None when the library declines (another form takes the engine, or none).
+        RuntimeError with the library's text when the arrays of B instances are beyond what the device has free."""
+        t = self._trees_large_args("solve_trees_large", q, l, u, x0, y0, upper0, x_inc0, tree_explor_rule, max_iter_bb, leaf_cap)
+        rc = self._lib.miosqp_qp_solve_trees_large(*t.head, _lib.as_d(t.x), t.infos)
+        return self._trees_large_done("solve_trees_large", rc, t.x, list(t.infos))
+
+    def solve_trees_large_rf(self, q, l, u, x0, y0, upper0, x_inc0, tree_explor_rule, max_iter_bb, rf_candidates, rf_max_iter,
+                             rf_every, leaf_cap=256):
+        """`solve_trees_rf` for an engine beyond one workgroup's product form (miosqp_qp_solve_trees_large_rf; see
+        `solve_trees_large`): round and fix inside every tree of the reduced form.  Returns (x B x n, [TreeInfo],
+        [TreeRfInfo]) -- instance b and its counters as `solve_trees_models([self], ..., leaf_cap=leaf_cap, rf=...)` gives
+        them alone -- or None when the library declines."""
+        t = self._trees_large_args("solve_trees_large_rf", q, l, u, x0, y0, upper0, x_inc0, tree_explor_rule, max_iter_bb,
+                                   leaf_cap)
+        rfs = (_lib.TreeRfInfo * t.B)()
+        rc = self._lib.miosqp_qp_solve_trees_large_rf(*t.head, int(rf_candidates), int(rf_max_iter), int(rf_every),
+                                                      _lib.as_d(t.x), t.infos, rfs)
+        return self._trees_large_done("solve_trees_large_rf", rc, t.x, list(t.infos), list(rfs))
+
+    def solve_trees_large_sb(self, q, l, u, x0, y0, upper0, x_inc0, tree_explor_rule, max_iter_bb, branching_rule,
+                             sb_candidates, sb_max_iter, sb_reliability, sb_eps, leaf_cap=256):
+        """`solve_trees_sb` for an engine beyond one workgroup's product form (miosqp_qp_solve_trees_large_sb; see
+        `solve_trees_large`): strong (branching_rule 1) or reliability branching (2) inside every tree of the reduced
+        form.  Returns (x B x n, [TreeInfo], [TreeSbInfo]) -- instance b and its counters as
+        `solve_trees_models([self], ..., leaf_cap=leaf_cap, sb=...)` gives them alone -- or None when the library
+        declines."""
+        t = self._trees_large_args("solve_trees_large_sb", q, l, u, x0, y0, upper0, x_inc0, tree_explor_rule, max_iter_bb,
+                                   leaf_cap)
+        sbs = (_lib.TreeSbInfo * t.B)()
+        rc = self._lib.miosqp_qp_solve_trees_large_sb(*t.head, int(branching_rule), int(sb_candidates), int(sb_max_iter),
+                                                      int(sb_reliability), float(sb_eps), _lib.as_d(t.x), t.infos, sbs)
+        return self._trees_large_done("solve_trees_large_sb", rc, t.x, list(t.infos), list(sbs))
+
     def solve_trees_lockstep(self, q, l, u, x0, y0, upper0, x_inc0, tree_explor_rule, max_iter_bb, capacity=0,
                              node_hviol=0):
         """B MIQPs on this engine's factor for problems of any size (arrays as for solve_trees): the trees advance in lock
